@@ -9,6 +9,11 @@ across ranks (rank r owns SRS block r, SURVEY §8e point-partition); each rank c
 sum, the partial points (64 B each) are all-gathered over RCCL and summed on the device
 (halo_point_sum) -- weak scaling, value = total points of all ranks / max-over-ranks time.
 
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps and prints
+the result line; `--dump-outputs DIR` also writes the last timed step's result (the MSM's affine
+point, 16 u32 limbs as float64) to DIR/msm_point.npy.  Inputs are seeded, so two runs with the same
+arguments compute the same point.  Everything below is measured or checked only with `--full`.
+
 Also measured (reported under "extra"): the 2^22 NTT + iNTT pair (BASELINE.json configs[2]) and, under
 "extra.sizes", the 2^24 MSM (BASELINE.json configs[4] per rank) and the 2^24 NTT + iNTT pair.
 
@@ -124,6 +129,11 @@ def parse():
                     help="A/B: window width of the headline's shifted SRS copies (0 = the library default)")
     ap.add_argument("--tune", action="append", default=[], metavar="KEY=VALUE",
                     help="halo_set_tuning before the run (A/B of path selections; results are identical)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline: the standalone-MSM check, NTT, IPA, prover, "
+                         "other sizes, CPU baselines and oracle checks (the options above select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the result of the last timed step to DIR/msm_point.npy (float64)")
     return ap.parse_args()
 
 
@@ -254,11 +264,11 @@ def main():
         # every step's result must equal the synchronous (non-pipelined) MSM of the same scalars; these
         # standalone MSMs also give k_acc's isolated launch time (the timed region's launches share the
         # GPU with the other stream's front and the previous step's tail)
-        sync_ok = True
+        sync_ok = True if args.full else None
         lat = []
         L.halo_profile_reset()
         L.halo_profile_enable(0 if os.environ.get("HALO_BENCH_NOPROF") == "1" else 1)
-        for i in range(min(nbatch, 4) if check_sync else 1):
+        for i in range((min(nbatch, 4) if check_sync else 1) if args.full else 0):
             torch.cuda.synchronize()
             a0 = time.perf_counter()
             H.check(L.halo_msm_dev(curve, None, ctypes.c_void_p(scalars[i].data_ptr()), n, H.ptr(out), sp))
@@ -268,12 +278,20 @@ def main():
                     sync_ok &= bool(np.array_equal(d_out[j].cpu().numpy().view(np.uint64), out))
         L.halo_profile_enable(0)
         H.check(L.halo_profile_read(b"msm_acc", ctypes.byref(launches), ctypes.byref(acc_ms)))
-        acc_iso_ms = acc_ms.value / max(1, launches.value)
+        acc_iso_ms = acc_ms.value / max(1, launches.value) if args.full else None
         first = d_out[0].cpu().numpy().view(np.uint64).copy() if warmup > 0 else None
+        # what a caller of the timed path receives from its last step: the MSM's affine point (the
+        # combined one at N > 1), 8 u64 limbs
+        last = (d_final if world > 1 else d_out)[total_steps - 1].cpu().numpy().view(np.uint64).copy()
         torch.cuda.synchronize()
-        return elapsed, acc_avg_ms, acc_iso_ms, sync_ok, lat, scalars[0], (seed, first)
+        return elapsed, acc_avg_ms, acc_iso_ms, sync_ok, lat, scalars[0], (seed, first), last
 
-    elapsed, acc_avg_ms, acc_iso_ms, sync_ok, lat, scalars0, check0 = measure_msm(args.logn, args.steps, args.warmup)
+    elapsed, acc_avg_ms, acc_iso_ms, sync_ok, lat, scalars0, check0, last_out = measure_msm(args.logn, args.steps,
+                                                                                          args.warmup)
+    if args.dump_outputs and rank == 0:
+        # the 255-bit coordinates as u32 limbs (x then y, little endian), each exact in float64
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "msm_point.npy"), last_out.view(np.uint32).astype(np.float64))
     window_bits = L.halo_srs_window_bits(curve)
 
     # ---- IPA opening (pcdl::open_without_eval round loop, pcdl.rs:392-438) at 2^logn:
@@ -334,7 +352,7 @@ def main():
                               "same_U": bool(np.array_equal(best[2], fold_path[2]))},
         }
 
-    ipa = measure_ipa(args.logn) if args.ipa else None
+    ipa = measure_ipa(args.logn) if args.full and args.ipa else None
 
     # ---- BASELINE configs[3]: the naive_prover hot path (halo_amd.prover, protocol.rs:64-330) on the
     # device at n = 2^prove_logn, and at 2^prove_cpu_logn beside the C restatement of the same
@@ -425,7 +443,7 @@ def main():
         del a, b, o
         return {"workload": f"Evals pointwise op over 2^{logn} Fp elements (96 B/element)", **res}
 
-    evals = measure_evals(23)
+    evals = measure_evals(23) if args.full else None
 
     # ---- measured HBM copy peak (reported beside the 8 TB/s spec figure): device-to-
     # device copy of 1 GiB, read + write bytes over the copy time
@@ -445,7 +463,7 @@ def main():
         return {"workload": "device-to-device copy of 1 GiB (torch copy kernel)", "ms": ms,
                 "GBps": 2 * nbytes / (ms * 1e-3) / 1e9, "frac_of_spec": 2 * nbytes / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS}
 
-    hbm_copy = measure_copy()
+    hbm_copy = measure_copy() if args.full else None
 
     # ---- variable-base MSM (group.rs:48-50 point_dot_affine over caller bases: GLV digits, no
     # window-shifted copies), pipelined like the headline; bases = the synthetic SRS read back
@@ -490,7 +508,7 @@ def main():
             "k_acc_ms": ams.value / max(1, nl.value),
         }, chk
 
-    varbase, varbase_chk = measure_varbase(args.logn) if args.varbase else (None, None)
+    varbase, varbase_chk = measure_varbase(args.logn) if args.full and args.varbase else (None, None)
 
     # ---- batched commitments (halo_msm_batch_dev; protocol.rs:114,263: 16 commits per round)
     def measure_commit_batch(logn, k=16, reps=5):
@@ -522,7 +540,7 @@ def main():
                             "(one MSM, (polynomial, bucket) keys)", "ms_per_batch": ms,
                 "points_per_s": k * n_ / (ms * 1e-3), "equals_per_msm_path": same}
 
-    commit_batch = measure_commit_batch(16) if args.commit_batch else None
+    commit_batch = measure_commit_batch(16) if args.full and args.commit_batch else None
 
     # ---- the reference's own criterion shapes (crates/accumulation/benches/pcdl.rs:35-79): pcdl_commit
     # and pcdl_open with w = Some over n = 2^2..2^20, Pallas; host buffers in and out as the Rust API
@@ -568,7 +586,7 @@ def main():
             inputs[lg] = (p_, w_, z_, q_, wb_, C, pi)
         return res, inputs, G  # G: the sweep's SRS (S = G_0, H = G_1), kept for the CPU leg
 
-    pcdl_lgs = [int(v) for v in args.pcdl.split(",") if v.strip()] if world == 1 else []
+    pcdl_lgs = [int(v) for v in args.pcdl.split(",") if v.strip()] if args.full and world == 1 else []
     pcdl_sweep, pcdl_inputs, pcdl_sh = measure_pcdl(pcdl_lgs) if pcdl_lgs else (None, None, None)
 
     # ---- BASELINE configs[4] as named: one 2^lg-point MSM window-partitioned across the ranks
@@ -646,17 +664,18 @@ def main():
                 "points_per_s_resident_scalars": n_ / (out["ms_per_msm_resident_scalars"] * 1e-3),
                 "matches_single_gpu": ok, "scaling": "strong", **out}
 
-    ntt_main = measure_ntt(args.ntt_logn)
-    ntt_main["workload"] += " (BASELINE.json configs[2])"
+    ntt_main = measure_ntt(args.ntt_logn) if args.full else None
+    if ntt_main is not None:
+        ntt_main["workload"] += " (BASELINE.json configs[2])"
     sizes = {}
     ntt24_keys = []
     size_checks = {}  # 2^lg MSM: (scalars[0] on the host, SRS seed, result), verified in the CPU leg
-    for lg in [int(v) for v in args.sizes.split(",") if v.strip()]:
+    for lg in [int(v) for v in args.sizes.split(",") if v.strip()] if args.full else []:
         # 8 pipelined MSMs after 4 warm-up ones (round 5 timed 4 after 2: the two scratch sets of each
         # stream's slot not yet grown to this size were allocated inside the timed region, ~9 GB each at
         # 2^24, and the last MSM's exposed tail was a quarter of the region)
         ksz = 8
-        e, a_ms, _, ok, lt, sc0, chk = measure_msm(lg, ksz, 4, check_sync=False)
+        e, a_ms, _, ok, lt, sc0, chk, _ = measure_msm(lg, ksz, 4, check_sync=False)
         if world == 1 and not args.no_cpu:
             size_checks[lg] = (sc0.cpu().numpy().view(np.uint64).copy(), chk)
         del sc0
@@ -675,7 +694,7 @@ def main():
         if world > 1 and (world & (world - 1)) == 0:
             # BASELINE configs[4]: one 2^lg-point MSM partitioned across the ranks (strong scaling)
             lr = lg - (world.bit_length() - 1)
-            e, a_ms, _, ok, lt, _, _ = measure_msm(lr, 4, 2, check_sync=False)
+            e, a_ms, _, ok, lt, _, _, _ = measure_msm(lr, 4, 2, check_sync=False)
             sizes[f"msm_2^{lg}_partitioned"] = {
                 "points_per_s": (1 << lg) * 4 / e,
                 "ms_per_msm": e * 1e3 / 4,
@@ -688,7 +707,7 @@ def main():
 
     # ---- distributed single NTT (four-step, RCCL all-to-all; halo_amd.dist.sharded_ntt), N > 1 only
     dist_ntt = None
-    if world > 1 and args.dist_ntt_logn:
+    if args.full and world > 1 and args.dist_ntt_logn:
         from halo_amd.dist import GpuNttOps, sharded_ntt, torch_alltoall
         lg = args.dist_ntt_logn
         per = (1 << lg) // world
@@ -796,14 +815,14 @@ def main():
                 "transforms_on_rank0": len([t for t in range(T) if t % world == 0]), "scaling": "strong",
                 "roundtrip_bit_exact": bool(ok.item()), "matches_single_gpu": matches}
 
-    batch_ntt = measure_batch_ntt() if args.batch_ntt else None
+    batch_ntt = measure_batch_ntt() if args.full and args.batch_ntt else None
 
     # ---- distributed IPA opening (strided shards, halo_amd.dist.sharded_ipa_rounds), N > 1 only:
     # every rank synthesizes the same 2^logn SRS and then keeps only its shard G[i P + r] resident (with
     # its window-shifted copies), so each shard runs the weighted rounds (GpuWeightedIpaOps); the
     # per-round L_r, R_r are all-gathered on the device and summed there (torch_reduce_lr)
     dist_ipa = None
-    if world > 1 and args.ipa and args.dist_ipa:
+    if args.full and world > 1 and args.ipa and args.dist_ipa:
         from halo_amd import pcdl as PC
         from halo_amd.dist import (GpuWeightedIpaOps, sharded_ipa_rounds, torch_gather_arrays, torch_reduce_lr,
                                    torch_reduce_lr_dev)
@@ -913,7 +932,7 @@ def main():
     cpu = None
     cpu_ntt = cpu_fold = None
     verified = {}
-    if not args.no_cpu and world == 1:
+    if args.full and not args.no_cpu and world == 1:
         cpu = cpu_baseline(L, H, curve, n, scalars0, out_check=True, budget_s=args.cpu_seconds)
         cpu_ntt = cpu_ntt_baseline(L, H, args.ntt_logn, sp, ntt_main)
         cpu_fold = cpu_fold_baseline(L, H, curve, 13, ipa)
@@ -929,7 +948,7 @@ def main():
 
     # after the MSM CPU leg (which reads the MSM's resident SRS back)
     prove = None
-    if args.prove and world == 1:
+    if args.full and args.prove and world == 1:
         main_out = measure_prove(args.prove)
         prove = {
             "workload": f"naive_prover hot path at n = 2^{args.prove} (BASELINE.json configs[3]): 17 iNTT(n) + "
@@ -985,6 +1004,7 @@ def main():
         "steps": args.steps,
         "warmup": args.warmup,
         "ms_per_step": ms_per_step,
+        "full": args.full,
         "higher_is_better": True,
         "scaling": "weak",
         "vs_baseline": None,

@@ -16,14 +16,14 @@ for i in 1 2; do
     echo "== $tag"
     case $what in
       msm)
-        HALO_LIB=$PWD/$lib timeout -k 10 200 python bench.py --no-cpu --sizes "" --ipa 0 --prove 0 --varbase 0 \
+        HALO_LIB=$PWD/$lib timeout -k 10 200 python bench.py --full --no-cpu --sizes "" --ipa 0 --prove 0 --varbase 0 \
           --commit-batch 0 --pcdl "" --steps 20 > $O/$tag.json 2> $O/$tag.err || { tail -20 $O/$tag.err; exit 1; }
         python3 -c "
 import json; d = json.loads(open('$O/$tag.json').read().strip().splitlines()[-1]); e = d['extra']
 print('ms/step %.4f  k_acc %.3f  latency %.3f  ntt pair %.3f' % (d['ms_per_step'], d['roofline']['avg_launch_ms'],
       e['msm_single_latency_ms'], e['ntt']['pair_ms']))" ;;
       msm24)  # headline and the 2^24 sizes leg (8 pipelined after 4 warm-up)
-        HALO_LIB=$PWD/$lib timeout -k 10 300 python bench.py --no-cpu --sizes 24 --ipa 0 --prove 0 --varbase 0 \
+        HALO_LIB=$PWD/$lib timeout -k 10 300 python bench.py --full --no-cpu --sizes 24 --ipa 0 --prove 0 --varbase 0 \
           --commit-batch 0 --batch-ntt 0 --pcdl "" --steps 20 > $O/$tag.json 2> $O/$tag.err || { tail -20 $O/$tag.err; exit 1; }
         python3 -c "
 import json; d = json.loads(open('$O/$tag.json').read().strip().splitlines()[-1]); s = d['extra']['sizes']

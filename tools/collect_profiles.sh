@@ -20,18 +20,18 @@ cd $GRAFT_REPO_ROOT
 O=gpurun_out/evid_${tag}
 rm -rf $O && mkdir -p $O
 LEGS='--varbase 0 --commit-batch 0 --batch-ntt 0 --pcdl'
-timeout -k 10 500 python bench.py > $O/bench_full.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+timeout -k 10 500 python bench.py --full > $O/bench_full.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
 tail -n 1 $O/bench_full.json > $O/bench.json
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o run -- python3 bench.py --no-cpu --sizes "" --ipa 0 --prove 0 $LEGS "" > $O/trace.log 2>&1
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o run -- python3 bench.py --full --no-cpu --sizes "" --ipa 0 --prove 0 $LEGS "" > $O/trace.log 2>&1
 rc=$?; echo "rocprofv3 --kernel-trace exit status: $rc" > $O/trace_exit.txt
 grep -n -i "segmentation\|core dumped\|abort" $O/trace.log >> $O/trace_exit.txt || true
 [ $rc -eq 0 ] || { tail -20 $O/trace.log; exit 1; }
 cp $(find $O/trace -name "*kernel_stats.csv" | head -1) $O/kernel_stats.csv
 grep '^{' $O/trace.log | tail -n 1 > $O/bench_traced.json
-timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_f -o run -- python3 bench.py --no-cpu --sizes "" --ipa 0 --prove 0 $LEGS "" --steps 3 --warmup 1 > /dev/null 2>&1 || exit 1
-timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_w -o run -- python3 bench.py --no-cpu --sizes "" --ipa 0 --prove 0 $LEGS "" --steps 3 --warmup 1 > /dev/null 2>&1 || exit 1
-python3 tools/make_pmc_summary.py $O/pmc_f $O/pmc_w $O/pmc_summary.json "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE (separate passes) of 'python3 bench.py --no-cpu --sizes \"\" --ipa 0 --prove 0 $LEGS \"\" --steps 3 --warmup 1', ${tag}" > /dev/null
+timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_f -o run -- python3 bench.py --full --no-cpu --sizes "" --ipa 0 --prove 0 $LEGS "" --steps 3 --warmup 1 > /dev/null 2>&1 || exit 1
+timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_w -o run -- python3 bench.py --full --no-cpu --sizes "" --ipa 0 --prove 0 $LEGS "" --steps 3 --warmup 1 > /dev/null 2>&1 || exit 1
+python3 tools/make_pmc_summary.py $O/pmc_f $O/pmc_w $O/pmc_summary.json "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE (separate passes) of 'python3 bench.py --full --no-cpu --sizes \"\" --ipa 0 --prove 0 $LEGS \"\" --steps 3 --warmup 1', ${tag}" > /dev/null
 rm -rf $O/trace $O/pmc_f/*/ $O/pmc_w/*/ 2>/dev/null
 bash tools/pmc_valu.sh $O/pmc_summary.json > $O/pmc_valu.log 2>&1 || { tail -5 $O/pmc_valu.log; exit 1; }
 python3 tools/kstats.py $O/kernel_stats.csv > $O/kstats.txt
@@ -41,6 +41,6 @@ bash tools/prof_prove.sh 20 > /dev/null && cp gpurun_out/prof_prove/kstats.txt $
 bash tools/pmc_prove.sh 20 > $O/pmc_prove.log 2>&1 && cp gpurun_out/pmc_prove/prove_valu.json $O/ || { tail -5 $O/pmc_prove.log; exit 1; }
 bash tools/pmc_ntt.sh 22 > $O/pmc_ntt22.txt 2>&1 && bash tools/pmc_ntt.sh 24 > $O/pmc_ntt24.txt 2>&1 || exit 1
 cp $O/pmc_summary.json profiles/pmc_summary.json && cp $O/prove_valu.json profiles/prove_valu.json
-timeout -k 10 500 python bench.py > $O/bench_stamped_full.json 2> $O/bench_stamped.err || { tail -20 $O/bench_stamped.err; exit 1; }
+timeout -k 10 500 python bench.py --full > $O/bench_stamped_full.json 2> $O/bench_stamped.err || { tail -20 $O/bench_stamped.err; exit 1; }
 tail -n 1 $O/bench_stamped_full.json > $O/bench_stamped.json
 head -n 30 $O/kstats.txt

@@ -3,7 +3,7 @@
 # of them, and per-kernel totals over the timed region.  Run through gpurun from the repo root.
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/tl_head24; rm -rf $O; mkdir -p $O
-timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/t -o run -- python3 bench.py --no-cpu --logn 24 --sizes "" --ipa 0 --prove 0 --varbase 0 --commit-batch 0 --batch-ntt 0 --pcdl "" --steps 8 --warmup 4 > $O/log 2>&1 || { tail -20 $O/log; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/t -o run -- python3 bench.py --full --no-cpu --logn 24 --sizes "" --ipa 0 --prove 0 --varbase 0 --commit-batch 0 --batch-ntt 0 --pcdl "" --steps 8 --warmup 4 > $O/log 2>&1 || { tail -20 $O/log; exit 1; }
 f=$(find $O/t -name "*kernel_trace.csv" | head -1)
 python3 - "$f" > $O/timeline.txt <<'PY'
 import csv, sys

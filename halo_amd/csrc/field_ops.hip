@@ -388,7 +388,7 @@ extern "C" int halo_pcdl_hiding_blind(halo_curve_t curve, const halo_fe_t* q, si
     HALO_CHECK(copy_h2d(small + 32, w_bar, 32, s));
     HALO_CHECK(pcdl_pbar_device(curve, st->scratch[0].ptr, d, small, st->scratch[1].ptr, s));
     // C_bar as packed XYZZ, converted on the host (no inversion on the MSM's last lane)
-    HALO_CHECK(msm_srs_device(st, curve, st->scratch[1].ptr, n, small + 32, small + 64, s, false, true));
+    HALO_CHECK(msm_srs_device(st, curve, st->scratch[1].ptr, n, small + 32, small + 64, s, MsmOpts::Sync().xyzz()));
     if (p_bar_out) HALO_CHECK(copy_d2h(p_bar_out, st->scratch[1].ptr, n * 32, s));
     alignas(16) uint64_t buf[16];
     HALO_CHECK(copy_d2h(buf, small + 64, 128, s));

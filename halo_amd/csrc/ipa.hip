@@ -1929,7 +1929,7 @@ extern "C" int halo_pcdl_open_blind(halo_ipa_session* ses, const halo_fe_t* q, c
     } else {
         HALO_CHECK(copy_h2d(sm + SM_WBAR, w_bar, 32, s));
         HALO_CHECK(pcdl_pbar_device(ses->curve, ses->tmp.ptr, d, sm, ses->pbar.ptr, s));  // z at sm[0, 32)
-        HALO_CHECK(msm_srs_device(st, ses->curve, ses->pbar.ptr, n, sm + SM_WBAR, sm + SM_T, s, false, true));
+        HALO_CHECK(msm_srs_device(st, ses->curve, ses->pbar.ptr, n, sm + SM_WBAR, sm + SM_T, s, MsmOpts::Sync().xyzz()));
     }
     HALO_HIP(hipMemcpyAsync(ses->pinned + 128, sm + SM_T, 128, hipMemcpyDeviceToHost, s));
     HALO_HIP(hipStreamSynchronize(s));
@@ -2003,7 +2003,8 @@ extern "C" int halo_pcdl_open_combine(halo_ipa_session* ses, const halo_fe_t* al
         } else {
             HALO_CHECK(pcdl_combine_scalars_device(ses->curve, ses->cs.ptr, ses->pbar.ptr, ses->n, sm + SM_ALPHA,
                                                    sm + SM_W, sm + SM_WBAR, sm + SM_WP, sm + SM_NEGW, s));
-            HALO_CHECK(msm_srs_device(st, ses->curve, ses->pbar.ptr, ses->n, sm + SM_NEGW, sm + SM_T, s, false, true));
+            HALO_CHECK(msm_srs_device(st, ses->curve, ses->pbar.ptr, ses->n, sm + SM_NEGW, sm + SM_T, s,
+                                      MsmOpts::Sync().xyzz()));
             HALO_CHECK(xyzz_add_wrapped_device(ses->curve, sm + SM_T, sm + SM_C, s, false));
         }
         HALO_HIP(hipMemcpyAsync(ses->pinned, sm + SM_WP, 32, hipMemcpyDeviceToHost, s));
@@ -2372,6 +2373,8 @@ static int ipa_round_launch(DeviceState* st, halo_ipa_session* ses) {
         // 2^14 / 2^17 / 2^18 / 2^19 / 2^20 ms, two MSMs vs one: 7.5 / 11.3 / 14.4 / 19.3 / 27.2 vs
         // 6.9 / 10.3 / 13.2 / 17.8 / 29.0 (round 4, after the sort and accumulation changes: 2^20
         // 21.7 vs 22.7 ms)
+        // (the two-MSM form: the even half-blocks of 2^lgm points, dot H' from the GLV table, L / R as XYZZ)
+        const MsmOpts blocks = MsmOpts::Async().blocks(lgm).glv_hide().xyzz().after(hr);
         if (pair) {
             // L and R reach `pinned` from k_bitcombine itself (polled, as the tail rounds): no copy
             const MsmPairIO io{sl, sr, sm + 128, sm + 160, sm + 512, sm + 640};
@@ -2400,18 +2403,15 @@ static int ipa_round_launch(DeviceState* st, halo_ipa_session* ses) {
             }
             HALO_HIP(hipEventRecord(ses->ev_fork, s));
             HALO_HIP(hipStreamWaitEvent(ses->s2, ses->ev_fork, 0));
-            HALO_CHECK(msm_srs_range_device(st, ses->curve, 0, sl, half, ses->htab_ptr, sm + 128, sm + 512, s, true,
-                                            lgm, true, true, hr));
+            HALO_CHECK(msm_srs_range_device(st, ses->curve, 0, sl, half, ses->htab_ptr, sm + 128, sm + 512, s, blocks));
             HALO_CHECK(msm_srs_range_device(st, ses->curve, m, sr, half, ses->htab_ptr, sm + 160, sm + 640, ses->s2,
-                                            true, lgm, true, true, hr));
+                                            blocks));
             HALO_CHECK(msm_join(st, ses->s2));
             HALO_HIP(hipEventRecord(ses->ev_join, ses->s2));
             HALO_HIP(hipStreamWaitEvent(s, ses->ev_join, 0));
         } else {
-            HALO_CHECK(msm_srs_range_device(st, ses->curve, 0, sl, half, ses->htab_ptr, sm + 128, sm + 512, s, true,
-                                            lgm, true, true, hr));
-            HALO_CHECK(msm_srs_range_device(st, ses->curve, m, sr, half, ses->htab_ptr, sm + 160, sm + 640, s, true,
-                                            lgm, true, true, hr));
+            HALO_CHECK(msm_srs_range_device(st, ses->curve, 0, sl, half, ses->htab_ptr, sm + 128, sm + 512, s, blocks));
+            HALO_CHECK(msm_srs_range_device(st, ses->curve, m, sr, half, ses->htab_ptr, sm + 160, sm + 640, s, blocks));
         }
         HALO_CHECK(msm_join(st, s));
         return ipa_copy_out(ses);
@@ -2427,16 +2427,13 @@ static int ipa_round_launch(DeviceState* st, halo_ipa_session* ses) {
     }
     {
         // L and R are independent: the second MSM's accumulation overlaps the first one's tail
+        const MsmOpts lr = MsmOpts::Async().glv_hide().xyzz().after(hr);
         if (ses->srs_round0) {  // G_l = SRS[0, m), G_r = SRS[m, 2m): resident window-shifted copies, no Horner
-            HALO_CHECK(msm_srs_range_device(st, ses->curve, 0, cs + m * 32, m, ses->htab_ptr, sm + 128, sm + 512, s, true,
-                                            32, true, true, hr));
-            HALO_CHECK(msm_srs_range_device(st, ses->curve, m, cs, m, ses->htab_ptr, sm + 160, sm + 640, s, true, 32,
-                                            true, true, hr));
+            HALO_CHECK(msm_srs_range_device(st, ses->curve, 0, cs + m * 32, m, ses->htab_ptr, sm + 128, sm + 512, s, lr));
+            HALO_CHECK(msm_srs_range_device(st, ses->curve, m, cs, m, ses->htab_ptr, sm + 160, sm + 640, s, lr));
         } else {
-            HALO_CHECK(msm_device(st, ses->curve, gs, cs + m * 32, m, ses->htab_ptr, sm + 128, sm + 512, s, true, true,
-                                  true, hr));
-            HALO_CHECK(msm_device(st, ses->curve, gs + m * 64, cs, m, ses->htab_ptr, sm + 160, sm + 640, s, true, true,
-                                  true, hr));
+            HALO_CHECK(msm_device(st, ses->curve, gs, cs + m * 32, m, ses->htab_ptr, sm + 128, sm + 512, s, lr));
+            HALO_CHECK(msm_device(st, ses->curve, gs + m * 64, cs, m, ses->htab_ptr, sm + 160, sm + 640, s, lr));
         }
         HALO_CHECK(msm_join(st, s));
     }
@@ -2672,7 +2669,7 @@ static int ipa_end_enqueue(DeviceState* st, halo_ipa_session* ses) {
             rc = ipa_tail_sums(st, ses, 1, s, ses->cs.ptr, sm + 384);
         else
             rc = msm_srs_range_device(st, ses->curve, 0, ses->w[ses->wcur].ptr, ses->n0, nullptr, nullptr, sm + 256, s,
-                                      false);
+                                      MsmOpts::Sync());
         if (!rc && !ses->tail && hipMemcpyAsync(sm + 320, ses->cs.ptr, 32, hipMemcpyDeviceToDevice, s) != hipSuccess)
             rc = set_error(HALO_EDEVICE, "ipa end copy failed");
     } else if ((rc = ipa_ensure_gs(st, ses))) {
@@ -2924,7 +2921,7 @@ extern "C" int halo_pcdl_decider_commit(halo_curve_t curve, const halo_fe_t* xis
     const int field = (curve == HALO_PALLAS) ? HALO_FP : HALO_FQ;
     HALO_CHECK(hpoly_device(st, field, xis, 1, n_xis, nullptr, st->scratch[7].ptr, s));
     char* d_out = (char*)st->scratch[7].ptr + n * 32;
-    HALO_CHECK(msm_srs_device(st, curve, st->scratch[7].ptr, n, nullptr, d_out, s, false, true));
+    HALO_CHECK(msm_srs_device(st, curve, st->scratch[7].ptr, n, nullptr, d_out, s, MsmOpts::Sync().xyzz()));
     alignas(16) uint64_t xyzz[16];  // converted on the host (msm.hip d2h_point)
     HALO_CHECK(copy_d2h(xyzz, d_out, 128, s));
     host_xyzz_to_wrapped(curve, xyzz, out);

@@ -31,10 +31,7 @@
 
 namespace halo {
 
-// Columns of the bucket reduction grid (k_rowcol): 256 x 256 at 2^16 buckets keeps the row, column
-// and bit-sliced tree depths at ~9 additions each (measured against 32 columns: single-MSM latency
-// 2.15 -> 2.02 ms at 2^20, IPA opening 36.8 -> 35.2 ms; the pipelined step unchanged).
-constexpr int MSM_SEG_L = 256;
+static_assert(MSM_PARTIAL_U4 == PARTIAL_U4, "msm_plan.hpp lays the partials out in curve.hpp's PARTIAL_U4 words");
 
 // ---------------------------------------------------------------------------------------------
 // synthetic bases / scalars (shared host/device definition)
@@ -352,49 +349,7 @@ __global__ __launch_bounds__(64) void k_xyzz_to_aff(const uint4* in, uint4* out,
 // ---------------------------------------------------------------------------------------------
 // host orchestration
 // ---------------------------------------------------------------------------------------------
-// windows of c bits for scalars reduced to [0, p/2] (k_digits): 254 bits + the signed-digit carry
-int msm_windows(int c) { return (255 + c - 1) / c; }
-
-// window bits of the window-shifted SRS copies: one more bit than the plain MSM choice when that
-// saves a window (c = 17 at 2^20: 15 windows instead of 16; the single bucket set of 2^16 buckets
-// keeps the reduction and the 2-pass sort cheap)
-int msm_shifted_window_bits(size_t n) {
-    int c = msm_window_bits(n);
-    if (msm_windows(c + 1) < msm_windows(c) && c + 1 <= 17) c++;
-    // the top window holds only the 255 - (W - 1) c remaining bits, so its digits pile into the
-    // lowest 2^(top - 1) buckets: n / 2^(top - 1) extra entries each, against W n / 2^(c - 1) on
-    // average, and k_merge's longest runs (the latency of a small MSM) grow with that ratio.  Widen the
-    // window until the ratio is at most 1/2 (c = 13 at 2^16: top 8 bits, ratio 1.6 -> c = 15, top 15).
-    auto top_bits = [](int cc) { return 255 - (msm_windows(cc) - 1) * cc; };
-    while (c < 17 && (1 << (c - top_bits(c))) * 2 > msm_windows(c)) c++;
-    return c;
-}
-
-int msm_window_bits(size_t n) {
-    unsigned lg = n > 1 ? ilog2(n - 1) + 1 : 1;
-    int c = (int)lg - 4;
-    return std::max(6, std::min(16, c));
-}
-
 static unsigned grid_for(size_t n, unsigned thr) { return (unsigned)std::max<size_t>(1, (n + thr - 1) / thr); }
-
-// Chunk length K of k_acc for E sorted entries.  Large MSMs (E > 16 x the resident lanes, 256 CUs x
-// 16 waves x 64): >= 4 rounds of resident lanes, 16 <= K <= 64 -- every lane does the same number
-// of mixed additions, and several rounds absorb the CU slots held by the previous MSM's tail kernels,
-// which one exact round would not (measured: K = 60 at 2^20 is 1 round and 15 % slower than K = 16;
-// round 4, pipelined 2^20 step: 2 rounds (K = 30) 1.378, 3 rounds (K = 20) 1.365, 4 rounds 1.354 ms,
-// and 6 / 8 rounds (K = 10 / 8: k_acc 0.87 / 0.85 ms, but twice the chunk partials for k_merge)
-// 1.362 / 1.374 ms).
-// Smaller MSMs are latency-bound (a commitment, an IPA round): their critical path is a lane's K
-// dependent additions in k_acc plus k_merge's run of about E / (NB K) partials per bucket, so K =
-// ceil(sqrt(E / NB)) balances the two -- but at least ceil(E / resident lanes), one round.
-static uint32_t msm_chunk_len(const DeviceState* st, size_t E, size_t NB) {
-    const size_t resident = (size_t)st->num_cu * 16 * 64;
-    if (E > 16 * resident) return (uint32_t)std::max<size_t>(16, std::min<size_t>(64, (E + 4 * resident - 1) / (4 * resident)));
-    size_t k = 1;
-    while (k * k * std::max<size_t>(NB, 1) < E) k++;
-    return (uint32_t)std::min<size_t>(16, std::max<size_t>(k, (E + resident - 1) / resident));
-}
 
 // Four scratch sets in two slots of two, a slot per issuing stream (least recently used slot
 // reassigned): consecutive MSMs of one stream alternate between their slot's two sets (the tail of
@@ -496,20 +451,104 @@ constexpr int curve_id() {
     return std::is_same<Cv, PallasCurve>::value ? HALO_PALLAS : HALO_VESTA;
 }
 
+// ---------------------------------------------------------------------------------------------
+// What the four drivers below share, all from one MsmPlan (msm_plan.hpp) built once per MSM: the
+// scratch reservation, the k_acc launch and the tail's arguments.  Scratch is MsmScratch or
+// BatchScratch; the latter has its own digit and list arrays and no reduction grid (batch_windows).
+// ---------------------------------------------------------------------------------------------
+template <class Scratch>
+constexpr bool has_grid = std::is_same<Scratch, MsmScratch>::value;
+
+// hide_slots: hiding terms kept behind the SW window sums (plan_hide_slot)
+template <class Scratch>
+static int plan_reserve(Scratch& S, const MsmPlan& p, size_t hide_slots) {
+    if constexpr (has_grid<Scratch>) {
+        HALO_CHECK(S.digits.reserve(p.digits_bytes));
+        HALO_CHECK(S.seg_acc.reserve(p.rows_bytes));
+        HALO_CHECK(S.seg_sum.reserve(p.cols_bytes));
+        HALO_CHECK(S.bits.reserve(p.terms_bytes));
+    }
+    HALO_CHECK(S.bstart.reserve(p.bstart_bytes));
+    HALO_CHECK(S.partials.reserve(p.partials_bytes));
+    HALO_CHECK(S.bucket_sums.reserve(p.bucket_sums_bytes));
+    HALO_CHECK(S.window_sums.reserve(p.window_sums_bytes(hide_slots)));
+    return HALO_OK;
+}
+static uint4* plan_hide_slot(const MsmScratch& M, const MsmPlan& p) { return M.window_sums.as<uint4>() + 8 * (size_t)p.SW; }
+
+// k_acc's inputs beside the plan and the scratch set.  The defaults are an MSM over plain bases:
+// entry value = point index, one output, bases tested for the identity.
+struct AccArgs {
+    const uint32_t *keys, *vals, *count;  // the sorted entries and their device count
+    const uint4* bases;
+    uint32_t n_per_window = 1;  // window-shifted bases (stride != 0): entry w n_per_window + i is point
+    uint32_t npw_lg = 0;        // w stride + i; npw_lg = log2 n_per_window, or 0xff when no power of two
+    size_t stride = 0;
+    uint32_t blk_lg = 32;   // < 32: i skips every other block of 2^blk_lg points
+    uint32_t glv_n = 0;     // GLV: entries >= glv_n are phi of point - glv_n
+    uint32_t key_lg = 31;   // pair MSMs: bit key_lg of the key set = the R side, poly_off points on
+    uint32_t poly_off = 0;
+    uint32_t check_q = 1;   // 0: the bases hold no identity point
+    bool profiled = true;   // timed as "msm_acc"
+};
+template <class Cv, class Scratch>
+static int acc_launch(const MsmPlan& p, Scratch& S, const AccArgs& a, hipStream_t s) {
+    ProfScope prof(a.profiled ? "msm_acc" : nullptr, s);
+    uint4* parts = S.partials.template as<uint4>();
+    HALO_LAUNCH(prof, k_acc<Cv>, dim3(grid_for(p.nchunks, 256)), dim3(256), 0, s, a.keys, a.vals, a.count, p.K, a.bases,
+                a.n_per_window, a.npw_lg, a.stride, a.blk_lg, a.glv_n, parts + p.off_first, parts + p.off_last,
+                S.bucket_sums.template as<uint4>(), S.bstart.template as<uint32_t>(), (uint32_t)p.NB, a.key_lg, a.poly_off,
+                a.check_q);
+    HALO_HIP(hipGetLastError());
+    return HALO_OK;
+}
+
+// The tail's arguments but for what is a driver's own (final_*, pair_*, batch_windows).  n: 0 for an
+// empty MSM, whose tail launches nothing.
+template <class Scratch>
+static MsmTailArgs plan_tail_args(const DeviceState* st, const MsmPlan& p, Scratch& S, size_t n, const uint32_t* skeys,
+                                  const uint32_t* scount) {
+    MsmTailArgs ta;
+    uint4* parts = S.partials.template as<uint4>();
+    ta.p = p;
+    ta.num_cu = (uint32_t)st->num_cu;
+    ta.n = n;
+    ta.skeys = skeys;
+    ta.scount = scount;
+    ta.first = parts + p.off_first;
+    ta.last = parts + p.off_last;
+    ta.g1 = parts + p.off_g1;
+    ta.g2 = parts + p.off_g2;
+    ta.bstart = S.bstart.template as<uint32_t>();
+    ta.bucket_sums = S.bucket_sums.template as<uint4>();
+    ta.rows = ta.cols = ta.terms = nullptr;
+    if constexpr (has_grid<Scratch>) {
+        ta.rows = S.seg_acc.template as<uint4>();
+        ta.cols = S.seg_sum.template as<uint4>();
+        ta.terms = S.bits.template as<uint4>();
+    }
+    ta.window_sums = S.window_sums.template as<uint4>();
+    return ta;
+}
+
+// window range (shifted bases only): the windows [w_lo, w_hi) of the scalars (w_hi <= 0: all), over
+// shifted copies that start at window base_w0 (a partially precomputed range)
+struct MsmWindowRange {
+    int w_lo = 0, w_hi = 0, base_w0 = 0;
+};
+
 // bases_int: n internal affine points, or (shifted) W * n window-shifted points (single bucket set).
 template <class Cv>
 static int msm_device_t(DeviceState* st, const uint4* bases_int, bool shifted, size_t shift_stride,
                         const uint4* scalars_ark, size_t n, int c_req, const uint4* hide_table, const uint4* hide_scalar,
-                        uint4* d_out_wrapped, hipStream_t s, bool async, uint32_t blk_lg = 32,
-                        bool hide_glv = false, bool out_xyzz = false, hipEvent_t hide_ready = nullptr,
-                        int preset = -1, int w_lo = 0, int w_hi = 0, int base_w0 = 0) {
+                        uint4* d_out_wrapped, hipStream_t s, const MsmOpts& o, MsmWindowRange wr = {}) {
     MsmPipe& PP = g_msm_pipe[st->device & 63];
     HALO_CHECK(pipe_init(PP));
     // preset: the set the caller already claimed (and waited for) to stage converted bases in
-    const int set = preset >= 0 ? preset : msm_pick_set(PP, s, true);
+    const int set = o.preset >= 0 ? o.preset : msm_pick_set(PP, s, true);
     MsmScratch& M = PP.set[set];
     // the previous user of this scratch set must have finished its tail
-    if (M.tail_pending && preset < 0) HALO_HIP(hipStreamWaitEvent(s, M.tail_done, 0));
+    if (M.tail_pending && o.preset < 0) HALO_HIP(hipStreamWaitEvent(s, M.tail_done, 0));
     const hipStream_t ts = PP.tail[set];
     const size_t nn = std::max<size_t>(n, 1);
     // non-shifted bases: GLV (2n half-size scalars, ~128-bit windows) -- see k_digits_glv
@@ -517,8 +556,8 @@ static int msm_device_t(DeviceState* st, const uint4* bases_int, bool shifted, s
     const size_t NP = glv ? 2 * nn : nn;  // digit entries per window
     const int c = c_req ? c_req : msm_window_bits(NP);
     const int W_all = glv ? (129 + c - 1) / c : msm_windows(c);
-    // window range (shifted bases only): the windows [w_lo, w_hi) of the scalars, over the shifted
-    // copies w_lo.. (the bases pointer is offset below); the partials of a partition add up
+    // the partials of a partition of the windows add up
+    int w_lo = wr.w_lo, w_hi = wr.w_hi;
     if (w_hi <= 0 || glv) {
         w_lo = 0;
         w_hi = W_all;
@@ -526,51 +565,28 @@ static int msm_device_t(DeviceState* st, const uint4* bases_int, bool shifted, s
     if (w_lo < 0 || w_hi > W_all || w_lo >= w_hi)
         return set_error(HALO_EINVAL, "window range [%d, %d) outside [0, %d)", w_lo, w_hi, W_all);
     const int W = w_hi - w_lo;
-    // (the copies start at window base_w0: a partially precomputed range)
-    if (shifted && w_lo != base_w0) bases_int += 4 * (size_t)(w_lo - base_w0) * shift_stride;
+    if (shifted && w_lo != wr.base_w0) bases_int += 4 * (size_t)(w_lo - wr.base_w0) * shift_stride;
     const uint32_t B = 1u << (c - 1);
     // sort geometry: SW windows of SN entries each (shifted: one window over all W * n digits)
     const int SW = shifted ? 1 : W;
-    const size_t SN = shifted ? (size_t)W * nn : NP;
-    const size_t NB = (size_t)SW * B;
-    const uint32_t L = std::min<uint32_t>(MSM_SEG_L, B);
-    const uint32_t logL = ilog2(L);
-    const uint32_t H = B / L;
-    const uint32_t logH = ilog2(H);
-    const uint32_t NT = 1 + logH + logL;  // reduction bit terms per window (<= 64)
-    const uint32_t key_bits = NB > 1 ? ilog2(NB - 1) + 1 : 1;
-    HALO_CHECK(M.digits.reserve((size_t)W * NP * 4));
-    HALO_CHECK(M.bstart.reserve((NB + 1) * 4));
-    const size_t E = (size_t)W * NP;
-    const uint32_t K = msm_chunk_len(st, E, NB);
-    const size_t nchunks = (E + K - 1) / K;
-    const size_t ng1 = nchunks / MSM_GROUP, ng2 = nchunks / (MSM_GROUP * MSM_GROUP);
-    HALO_CHECK(M.partials.reserve((std::max<size_t>(nchunks, 1) * 2 + ng1 + ng2 + 2) * 16 * PARTIAL_U4));
-    uint4* P_first = M.partials.as<uint4>();
-    uint4* P_last = P_first + PARTIAL_U4 * std::max<size_t>(nchunks, 1);
-    uint4* P_g1 = P_last + PARTIAL_U4 * std::max<size_t>(nchunks, 1);
-    uint4* P_g2 = P_g1 + PARTIAL_U4 * (ng1 + 1);
-    HALO_CHECK(M.bucket_sums.reserve(NB * 128));
-    HALO_CHECK(M.seg_acc.reserve((size_t)SW * H * 128));  // row sums
-    HALO_CHECK(M.seg_sum.reserve((size_t)SW * L * 128));  // column sums
-    HALO_CHECK(M.bits.reserve((size_t)SW * NT * 128));
-    HALO_CHECK(M.window_sums.reserve((size_t)(W + 1) * 128));  // + the hiding term's slot
+    const MsmPlan pl = msm_plan((size_t)W * NP, (size_t)SW * B, SW, B, c, st->num_cu, W, shifted ? (size_t)W * nn : NP);
+    HALO_CHECK(plan_reserve(M, pl, 1));  // + the hiding term's slot
 
     // the hiding term (k_hide_term) runs on the tail stream beside the accumulation phase
     uint4* hide_slot = nullptr;
     if (hide_table && hide_scalar) {
-        hide_slot = M.window_sums.as<uint4>() + 8 * (size_t)W;
+        hide_slot = plan_hide_slot(M, pl);
         HALO_HIP(hipEventRecord(M.start, s));
         HALO_HIP(hipStreamWaitEvent(ts, M.start, 0));
-        if (hide_ready) HALO_HIP(hipStreamWaitEvent(ts, hide_ready, 0));  // table built on a side stream
-        hipLaunchKernelGGL(k_hide_term<Cv>, dim3(1), dim3(256), 0, ts, hide_table, hide_scalar, (int)hide_glv,
+        if (o.hide_ready) HALO_HIP(hipStreamWaitEvent(ts, o.hide_ready, 0));  // table built on a side stream
+        hipLaunchKernelGGL(k_hide_term<Cv>, dim3(1), dim3(256), 0, ts, hide_table, hide_scalar, (int)o.hide_glv,
                            hide_slot);
         HALO_HIP(hipGetLastError());
     }
 
     if (n > 0) {
-        // shifted, all windows, W <= 16: digit recoding fused into the sort's first pass
-        const bool fuse = shifted && w_lo == 0 && w_hi == W_all && W_all <= 16 && n < (1ull << 31) / 16;
+        // shifted, all windows: digit recoding fused into the sort's first pass
+        const bool fuse = shifted && w_lo == 0 && w_hi == W_all && msm_fuse_first_pass(1, n, W_all, B, pl.key_bits);
         if (glv)
             hipLaunchKernelGGL(k_digits_glv<Cv>, dim3(grid_for(n, 256)), dim3(256), 0, s, scalars_ark, n, c, W,
                                M.digits.as<uint32_t>());
@@ -581,27 +597,23 @@ static int msm_device_t(DeviceState* st, const uint4* bases_int, bool shifted, s
         uint32_t *skeys = nullptr, *svals = nullptr;
         const uint32_t* scount = nullptr;
         RsFused fz{scalars_ark, n, c, W_all, curve_id<Cv>() == HALO_PALLAS ? HALO_FP : HALO_FQ};
-        HALO_CHECK(msm_radix_sort(M.digits.as<const uint32_t>(), E, SN, B, key_bits, M.sort, &skeys, &svals, &scount,
-                                  nullptr, NB, s, fuse ? &fz : nullptr));
-        const uint32_t nblocks = (uint32_t)grid_for(nchunks, 256);
+        HALO_CHECK(msm_radix_sort(M.digits.as<const uint32_t>(), pl.E, pl.SN, B, pl.key_bits, M.sort, &skeys, &svals,
+                                  &scount, nullptr, pl.NB, s, fuse ? &fz : nullptr));
         // the resident window-shifted SRS without identity points: k_acc skips the bases' identity test
         const SrsState& srs_c = st->srs[curve_id<Cv>()];
         const bool srs_bases = shifted && srs_c.shifted_c != 0 && srs_c.shifted.ptr &&
                                (const char*)bases_int >= srs_c.shifted.as<const char>() &&
                                (const char*)bases_int < srs_c.shifted.as<const char>() + srs_c.shifted.bytes;
-        const uint32_t check_q = (srs_bases && !srs_c.shifted_has_id) ? 0u : 1u;
-        {
-            ProfScope prof("msm_acc", s);
-            HALO_LAUNCH(prof, k_acc<Cv>, dim3(nblocks), dim3(256), 0, s, (const uint32_t*)skeys,
-                        (const uint32_t*)svals, scount, K, bases_int, (uint32_t)nn, is_pow2(nn) ? ilog2(nn) : 0xffu,
-                        (shifted && (shift_stride != nn || blk_lg < 32)) ? shift_stride : (size_t)0, blk_lg,
-                        glv ? (uint32_t)nn : 0u, P_first,
-                        P_last, M.bucket_sums.as<uint4>(), M.bstart.as<uint32_t>(), (uint32_t)NB, 31u, 0u,
-                        check_q);
-        }
+        AccArgs a{skeys, svals, scount, bases_int};
+        a.n_per_window = (uint32_t)nn;
+        a.npw_lg = is_pow2(nn) ? ilog2(nn) : 0xffu;
+        a.stride = (shifted && (shift_stride != nn || o.blk_lg < 32)) ? shift_stride : (size_t)0;
+        a.blk_lg = o.blk_lg;
+        a.glv_n = glv ? (uint32_t)nn : 0u;
+        a.check_q = (srs_bases && !srs_c.shifted_has_id) ? 0u : 1u;
+        HALO_CHECK(acc_launch<Cv>(pl, M, a, s));
         M.skeys = skeys;
         M.scount = scount;
-        HALO_HIP(hipGetLastError());
     } else {
         HALO_HIP(hipMemsetAsync(M.window_sums.ptr, 0, (size_t)SW * 128, s));
     }
@@ -609,52 +621,23 @@ static int msm_device_t(DeviceState* st, const uint4* bases_int, bool shifted, s
     // caller's next MSM
     HALO_HIP(hipEventRecord(M.acc_done, s));
     HALO_HIP(hipStreamWaitEvent(ts, M.acc_done, 0));
-    MsmTailArgs ta;
-    ta.num_cu = (uint32_t)st->num_cu;
-    ta.n = n;
-    ta.skeys = M.skeys;
-    ta.scount = M.scount;
-    ta.K = K;
-    ta.NB = NB;
-    ta.E = E;
-    ta.first = P_first;
-    ta.last = P_last;
-    ta.g1 = P_g1;
-    ta.g2 = P_g2;
-    ta.ng1 = ng1;
-    ta.ng2 = ng2;
-    ta.bstart = M.bstart.as<uint32_t>();
-    ta.bucket_sums = M.bucket_sums.as<uint4>();
-    ta.rows = M.seg_acc.as<uint4>();
-    ta.cols = M.seg_sum.as<uint4>();
-    ta.terms = M.bits.as<uint4>();
-    ta.window_sums = M.window_sums.as<uint4>();
-    ta.L = L;
-    ta.H = H;
-    ta.logH = logH;
-    ta.logL = logL;
-    ta.NT = NT;
-    ta.SW = SW;
-    ta.c = c;
-    ta.hide_table = hide_table;
-    ta.hide_scalar = hide_scalar;
-    ta.out_wrapped = d_out_wrapped;
+    MsmTailArgs ta = plan_tail_args(st, pl, M, n, M.skeys, M.scount);
     // one window set with a nonempty MSM (the tail reaches k_bitcombine): it also finishes the MSM
     const bool fuse = SW == 1 && n > 0;
     if (fuse) {
-        ta.final_mode = out_xyzz ? 2 : 1;
+        ta.final_mode = o.out_xyzz ? 2 : 1;
         ta.final_hide = (const uint4*)hide_slot;
         ta.final_out = (uint4*)d_out_wrapped;
     }
     HALO_CHECK(msm_tail_launch(curve_id<Cv>(), ta, ts));
     if (!fuse)
         HALO_CHECK(msm_final_launch(curve_id<Cv>(), M.window_sums.as<const uint4>(), SW, c, (const uint4*)hide_slot,
-                                    d_out_wrapped, (int)out_xyzz, ts));
+                                    d_out_wrapped, (int)o.out_xyzz, ts));
     HALO_HIP(hipGetLastError());
     HALO_HIP(hipEventRecord(M.tail_done, ts));
     M.tail_pending = true;
     M.owner = s;
-    if (!async) HALO_HIP(hipStreamWaitEvent(s, M.tail_done, 0));
+    if (!o.async) HALO_HIP(hipStreamWaitEvent(s, M.tail_done, 0));
     return HALO_OK;
 }
 
@@ -691,27 +674,10 @@ static int msm_multi_device_t(DeviceState* st, const void* const* scalars, const
     for (size_t p = 0; p < k; p++) ragged |= lens[p] != ld;
     const int c = srs.shifted_c, W = msm_windows(c);
     const uint32_t B = 1u << (c - 1);
-    const size_t SN = (size_t)W * ld, E = k * SN, NB = k * (size_t)B;
-    const int SW = (int)k;
+    const size_t SN = (size_t)W * ld, E = k * SN;
     if (E >= (1ull << 32)) return set_error(HALO_EINVAL, "halo_msm_batch_dev: batch too large");
-    const uint32_t L = std::min<uint32_t>(MSM_SEG_L, B), logL = ilog2(L), H = B / L, logH = ilog2(H);
-    const uint32_t NT = 1 + logH + logL;
-    const uint32_t key_bits = ilog2(NB - 1) + 1;
-    const uint32_t K = msm_chunk_len(st, E, NB);
-    const size_t nchunks = (E + K - 1) / K;
-    const size_t ng1 = nchunks / MSM_GROUP, ng2 = nchunks / (MSM_GROUP * MSM_GROUP);
-    HALO_CHECK(M.digits.reserve(E * 4));
-    HALO_CHECK(M.bstart.reserve((NB + 1) * 4));
-    HALO_CHECK(M.partials.reserve((nchunks * 2 + ng1 + ng2 + 2) * 16 * PARTIAL_U4));
-    HALO_CHECK(M.bucket_sums.reserve(NB * 128));
-    HALO_CHECK(M.seg_acc.reserve((size_t)SW * H * 128));
-    HALO_CHECK(M.seg_sum.reserve((size_t)SW * L * 128));
-    HALO_CHECK(M.bits.reserve((size_t)SW * NT * 128));
-    HALO_CHECK(M.window_sums.reserve((size_t)SW * 128));
-    uint4* P_first = M.partials.as<uint4>();
-    uint4* P_last = P_first + PARTIAL_U4 * nchunks;
-    uint4* P_g1 = P_last + PARTIAL_U4 * nchunks;
-    uint4* P_g2 = P_g1 + PARTIAL_U4 * (ng1 + 1);
+    const MsmPlan pl = msm_plan(E, k * (size_t)B, (int)k, B, c, st->num_cu, W, SN);
+    HALO_CHECK(plan_reserve(M, pl, 0));
     uint32_t* digits = M.digits.as<uint32_t>();
     if (ragged) HALO_HIP(hipMemsetAsync(digits, 0xff, E * 4, s));  // DIGIT_NONE past each length
     for (size_t p = 0; p < k; p++)
@@ -721,46 +687,14 @@ static int msm_multi_device_t(DeviceState* st, const void* const* scalars, const
     HALO_HIP(hipGetLastError());
     uint32_t *skeys = nullptr, *svals = nullptr;
     const uint32_t* scount = nullptr;
-    HALO_CHECK(msm_radix_sort(digits, E, SN, B, key_bits, M.sort, &skeys, &svals, &scount, nullptr, NB, s));
-    {
-        ProfScope prof("msm_acc", s);
-        const uint32_t nblocks = (uint32_t)grid_for(nchunks, 256);
-                HALO_LAUNCH(prof, k_acc<Cv>, dim3(nblocks), dim3(256), 0, s, (const uint32_t*)skeys, (const uint32_t*)svals, scount,
-                    K, srs.shifted.as<const uint4>(), (uint32_t)ld, is_pow2(ld) ? ilog2(ld) : 0xffu, srs.n, 32u, 0u,
-                    P_first, P_last, M.bucket_sums.as<uint4>(), M.bstart.as<uint32_t>(),
-                    (uint32_t)NB, 31u, 0u, srs.shifted_has_id ? 1u : 0u);
-        HALO_HIP(hipGetLastError());
-    }
-    MsmTailArgs ta;
-    ta.num_cu = (uint32_t)st->num_cu;
-    ta.n = E;
-    ta.skeys = skeys;
-    ta.scount = scount;
-    ta.K = K;
-    ta.NB = NB;
-    ta.E = E;
-    ta.first = P_first;
-    ta.last = P_last;
-    ta.g1 = P_g1;
-    ta.g2 = P_g2;
-    ta.ng1 = ng1;
-    ta.ng2 = ng2;
-    ta.bstart = M.bstart.as<uint32_t>();
-    ta.bucket_sums = M.bucket_sums.as<uint4>();
-    ta.rows = M.seg_acc.as<uint4>();
-    ta.cols = M.seg_sum.as<uint4>();
-    ta.terms = M.bits.as<uint4>();
-    ta.window_sums = M.window_sums.as<uint4>();
-    ta.L = L;
-    ta.H = H;
-    ta.logH = logH;
-    ta.logL = logL;
-    ta.NT = NT;
-    ta.SW = SW;
-    ta.c = c;
-    ta.hide_table = nullptr;
-    ta.hide_scalar = nullptr;
-    ta.out_wrapped = nullptr;
+    HALO_CHECK(msm_radix_sort(digits, E, SN, B, pl.key_bits, M.sort, &skeys, &svals, &scount, nullptr, pl.NB, s));
+    AccArgs a{skeys, svals, scount, srs.shifted.as<const uint4>()};
+    a.n_per_window = (uint32_t)ld;
+    a.npw_lg = is_pow2(ld) ? ilog2(ld) : 0xffu;
+    a.stride = srs.n;
+    a.check_q = srs.shifted_has_id ? 1u : 0u;
+    HALO_CHECK(acc_launch<Cv>(pl, M, a, s));
+    const MsmTailArgs ta = plan_tail_args(st, pl, M, E, skeys, scount);
     HALO_CHECK(msm_tail_launch(curve_id<Cv>(), ta, s));
     hipLaunchKernelGGL(k_sums_out<Cv>, dim3(grid_for(k, 64)), dim3(64), 0, s, M.window_sums.as<const uint4>(),
                        (uint32_t)k, d_out);
@@ -798,28 +732,11 @@ static int msm_srs_pairs_t(DeviceState* st, size_t np, const MsmPairIO* io, size
     const int P = (int)(2 * np);  // outputs: L0, R0, L1, R1, ...
     const int c = srs.shifted_c, W = msm_windows(c);
     const uint32_t B = 1u << (c - 1);
-    const size_t SN = (size_t)W * half, E = P * SN, NB = P * (size_t)B;
-    const int SW = P;
+    const size_t SN = (size_t)W * half, E = P * SN;
     if (E >= (1ull << 32)) return set_error(HALO_EINVAL, "msm_srs_pairs: too large");
-    const uint32_t L = std::min<uint32_t>(MSM_SEG_L, B), logL = ilog2(L), H = B / L, logH = ilog2(H);
-    const uint32_t NT = 1 + logH + logL;
-    const uint32_t key_bits = ilog2(NB - 1) + 1;
-    const uint32_t K = msm_chunk_len(st, E, NB);
-    const size_t nchunks = (E + K - 1) / K;
-    const size_t ng1 = nchunks / MSM_GROUP, ng2 = nchunks / (MSM_GROUP * MSM_GROUP);
-    HALO_CHECK(M.digits.reserve(E * 4));
-    HALO_CHECK(M.bstart.reserve((NB + 1) * 4));
-    HALO_CHECK(M.partials.reserve((nchunks * 2 + ng1 + ng2 + 2) * 16 * PARTIAL_U4));
-    HALO_CHECK(M.bucket_sums.reserve(NB * 128));
-    HALO_CHECK(M.seg_acc.reserve((size_t)SW * H * 128));
-    HALO_CHECK(M.seg_sum.reserve((size_t)SW * L * 128));
-    HALO_CHECK(M.bits.reserve((size_t)SW * NT * 128));
-    HALO_CHECK(M.window_sums.reserve((size_t)(2 * SW) * 128));  // + the hiding terms
-    uint4* P_first = M.partials.as<uint4>();
-    uint4* P_last = P_first + PARTIAL_U4 * nchunks;
-    uint4* P_g1 = P_last + PARTIAL_U4 * nchunks;
-    uint4* P_g2 = P_g1 + PARTIAL_U4 * (ng1 + 1);
-    uint4* hide_slot = M.window_sums.as<uint4>() + 8 * SW;
+    const MsmPlan pl = msm_plan(E, P * (size_t)B, P, B, c, st->num_cu, W, SN);
+    HALO_CHECK(plan_reserve(M, pl, P));  // + the hiding terms
+    uint4* hide_slot = plan_hide_slot(M, pl);
     // the hiding terms on the tail stream, beside the front and the accumulation
     HALO_HIP(hipEventRecord(M.start, s));
     HALO_HIP(hipStreamWaitEvent(ts, M.start, 0));
@@ -843,9 +760,8 @@ static int msm_srs_pairs_t(DeviceState* st, size_t np, const MsmPairIO* io, size
     DigitSrcs ds{};
     for (int p = 0; p < P; p++) ds.s[p] = (const uint4*)(p & 1 ? io[p / 2].sr : io[p / 2].sl);
     // the digit recoding fused into the sort's first pass (thread = scalar, round = window), as the
-    // headline MSM's: no digit array written and read back (W <= 16 windows and keys of <= 17 bits, so
-    // the first pass is an 8-bit one)
-    const bool fuse = W <= 16 && key_bits <= 17;
+    // headline MSM's: no digit array written and read back
+    const bool fuse = msm_fuse_first_pass(P, half, W, B, pl.key_bits);
     RsFused fz{nullptr, half, c, W, curve_id<Cv>() == HALO_PALLAS ? HALO_FP : HALO_FQ, P, {}};
     for (int p = 0; p < P; p++) fz.srcs[p] = ds.s[p];
     if (!fuse) {
@@ -855,47 +771,18 @@ static int msm_srs_pairs_t(DeviceState* st, size_t np, const MsmPairIO* io, size
     }
     uint32_t *skeys = nullptr, *svals = nullptr;
     const uint32_t* scount = nullptr;
-    HALO_CHECK(msm_radix_sort(digits, E, SN, B, key_bits, M.sort, &skeys, &svals, &scount, nullptr, NB, s,
+    HALO_CHECK(msm_radix_sort(digits, E, SN, B, pl.key_bits, M.sort, &skeys, &svals, &scount, nullptr, pl.NB, s,
                               fuse ? &fz : nullptr));
-    {
-        ProfScope prof("msm_acc", s);
-        const uint32_t nblocks = (uint32_t)grid_for(nchunks, 256);
-                HALO_LAUNCH(prof, k_acc<Cv>, dim3(nblocks), dim3(256), 0, s, (const uint32_t*)skeys, (const uint32_t*)svals, scount,
-                    K, srs.shifted.as<const uint4>(), (uint32_t)half, ilog2(half), srs.n, lgm, 0u, P_first, P_last,
-                    M.bucket_sums.as<uint4>(), M.bstart.as<uint32_t>(), (uint32_t)NB,
-                    (uint32_t)(c - 1), (uint32_t)m, srs.shifted_has_id ? 1u : 0u);
-        HALO_HIP(hipGetLastError());
-    }
-    MsmTailArgs ta;
-    ta.num_cu = (uint32_t)st->num_cu;
-    ta.n = E;
-    ta.skeys = skeys;
-    ta.scount = scount;
-    ta.K = K;
-    ta.NB = NB;
-    ta.E = E;
-    ta.first = P_first;
-    ta.last = P_last;
-    ta.g1 = P_g1;
-    ta.g2 = P_g2;
-    ta.ng1 = ng1;
-    ta.ng2 = ng2;
-    ta.bstart = M.bstart.as<uint32_t>();
-    ta.bucket_sums = M.bucket_sums.as<uint4>();
-    ta.rows = M.seg_acc.as<uint4>();
-    ta.cols = M.seg_sum.as<uint4>();
-    ta.terms = M.bits.as<uint4>();
-    ta.window_sums = M.window_sums.as<uint4>();
-    ta.L = L;
-    ta.H = H;
-    ta.logH = logH;
-    ta.logL = logL;
-    ta.NT = NT;
-    ta.SW = SW;
-    ta.c = c;
-    ta.hide_table = nullptr;
-    ta.hide_scalar = nullptr;
-    ta.out_wrapped = nullptr;
+    AccArgs a{skeys, svals, scount, srs.shifted.as<const uint4>()};
+    a.n_per_window = (uint32_t)half;
+    a.npw_lg = ilog2(half);
+    a.stride = srs.n;
+    a.blk_lg = lgm;
+    a.key_lg = (uint32_t)(c - 1);  // output = key >> key_lg, its R sides m points on
+    a.poly_off = (uint32_t)m;
+    a.check_q = srs.shifted_has_id ? 1u : 0u;
+    HALO_CHECK(acc_launch<Cv>(pl, M, a, s));
+    MsmTailArgs ta = plan_tail_args(st, pl, M, E, skeys, scount);
     ta.pair_hide = hide_slot;  // k_bitcombine adds the hiding terms and writes the outputs
     ta.pair_outs = outs;
     if (np == 1) {
@@ -965,26 +852,26 @@ int msm_join(DeviceState* st, hipStream_t s) {
 }
 
 int msm_device(DeviceState* st, int curve, const void* bases_int, const void* scalars_ark, size_t n,
-               const void* hide_table, const void* hide_scalar, void* d_out_wrapped, hipStream_t s, bool async,
-               bool hide_glv, bool out_xyzz, hipEvent_t hide_ready, int preset) {
+               const void* hide_table, const void* hide_scalar, void* d_out_wrapped, hipStream_t s, const MsmOpts& o) {
     int rc;
     DISPATCH_CURVE(curve, Cv, {
         rc = msm_device_t<Cv>(st, (const uint4*)bases_int, false, 0, (const uint4*)scalars_ark, n, 0,
-                              (const uint4*)hide_table, (const uint4*)hide_scalar, (uint4*)d_out_wrapped, s, async,
-                              32, hide_glv, out_xyzz, hide_ready, preset);
+                              (const uint4*)hide_table, (const uint4*)hide_scalar, (uint4*)d_out_wrapped, s, o);
     });
     return rc;
 }
 
 // MSM over the resident SRS prefix Gs[0..n): uses the window-shifted copies when present.
 int msm_srs_device(DeviceState* st, int curve, const void* scalars_ark, size_t n, const void* hide_scalar,
-                   void* d_out_wrapped, hipStream_t s, bool async, bool out_xyzz) {
+                   void* d_out_wrapped, hipStream_t s, const MsmOpts& o) {
     SrsState& srs = st->srs[curve];
     if (n > srs.n) return set_error(HALO_ESRSRANGE, "n (%zu) exceeds the resident SRS length (%zu)", n, srs.n);
     const void* table = hide_scalar ? srs.s_table.ptr : nullptr;
     if (hide_scalar && !srs.has_sh) return set_error(HALO_ESRSRANGE, "hiding commitment needs S: upload (S, H)");
-    if (!async && n >= 1 && n <= srs_small_max())
-        return msm_srs_small(st, curve, scalars_ark, n, hide_scalar, d_out_wrapped, s, out_xyzz);
+    if (!o.async && n >= 1 && n <= srs_small_max())
+        return msm_srs_small(st, curve, scalars_ark, n, hide_scalar, d_out_wrapped, s, o.out_xyzz);
+    MsmOpts od = o.async ? MsmOpts::Async() : MsmOpts::Sync();
+    od.out_xyzz = o.out_xyzz;
     int rc;
     // the shifted copies hold W windows of srs.n points each; an MSM of n <= srs.n points uses the
     // prefix of every window (point index w * srs.n + i)
@@ -992,17 +879,15 @@ int msm_srs_device(DeviceState* st, int curve, const void* scalars_ark, size_t n
     DISPATCH_CURVE(curve, Cv, {
         rc = msm_device_t<Cv>(st, use_shifted ? srs.shifted.as<const uint4>() : srs.gs.as<const uint4>(), use_shifted,
                               srs.n, (const uint4*)scalars_ark, n, use_shifted ? srs.shifted_c : 0, (const uint4*)table,
-                              (const uint4*)hide_scalar, (uint4*)d_out_wrapped, s, async, 32, false, out_xyzz, nullptr,
-                              -1);
+                              (const uint4*)hide_scalar, (uint4*)d_out_wrapped, s, od);
     });
     return rc;
 }
 
-int msm_srs_range_device(DeviceState* st, int curve, size_t offset, const void* scalars_ark, size_t n,
-                         const void* hide_table, const void* hide_scalar, void* d_out_wrapped, hipStream_t s,
-                         bool async, uint32_t blk_lg, bool hide_glv, bool out_xyzz,
-                         hipEvent_t hide_ready) {
+int msm_srs_range_device(DeviceState* st, int curve, size_t offset, const void* scalars_ark, size_t n, const void* hide_table,
+                         const void* hide_scalar, void* d_out_wrapped, hipStream_t s, const MsmOpts& o) {
     SrsState& srs = st->srs[curve];
+    const uint32_t blk_lg = o.blk_lg;
     if (!srs.shifted_c) return set_error(HALO_EINVAL, "msm_srs_range_device: no window-shifted SRS");
     // highest point touched: offset + map(n - 1), map(i) = i + (i >> blk_lg) << blk_lg
     const size_t last = n ? (n - 1) + (blk_lg < 32 ? ((n - 1) >> blk_lg) << blk_lg : 0) : 0;
@@ -1014,7 +899,7 @@ int msm_srs_range_device(DeviceState* st, int curve, size_t offset, const void* 
     DISPATCH_CURVE(curve, Cv, {
         rc = msm_device_t<Cv>(st, srs.shifted.as<const uint4>() + 4 * offset, true, srs.n, (const uint4*)scalars_ark, n,
                               srs.shifted_c, (const uint4*)hide_table, (const uint4*)hide_scalar,
-                              (uint4*)d_out_wrapped, s, async, blk_lg, hide_glv, out_xyzz, hide_ready);
+                              (uint4*)d_out_wrapped, s, o);
     });
     return rc;
 }
@@ -1154,26 +1039,15 @@ static int msm_shared_batch_t(DeviceState* st, const uint4* bases, const uint4* 
     const size_t SW = len * (size_t)W, NB = SW * B, E = SW * TS;
     if (E >= (1ull << 32) || T * len >= (1ull << 31) || B > BATCH_B_MAX)
         return set_error(HALO_EINVAL, "msm_shared_batch: batch too large (len %zu, T %zu)", len, T);
-    const uint32_t L = std::min<uint32_t>(MSM_SEG_L, B), logL = ilog2(L), H = B / L, logH = ilog2(H);
-    const uint32_t NT = 1 + logH + logL;
-    const uint32_t K = msm_chunk_len(st, E, NB);
-    const size_t nchunks = (E + K - 1) / K;
-    const size_t ng1 = nchunks / MSM_GROUP, ng2 = nchunks / (MSM_GROUP * MSM_GROUP);
+    const MsmPlan pl = msm_plan(E, NB, (int)SW, B, c, st->num_cu, W, TS);
     HALO_CHECK(S.digits.reserve((size_t)(shifted ? W_s + W : W) * TS * 4));
     HALO_CHECK(S.lists.reserve((size_t)W * TS * 8 + 16));
     HALO_CHECK(S.keys.reserve(E * 4));
     HALO_CHECK(S.vals.reserve(E * 4));
-    HALO_CHECK(S.bstart.reserve((NB + 1) * 4));
-    HALO_CHECK(S.partials.reserve((nchunks * 2 + ng1 + ng2 + 2) * 16 * PARTIAL_U4));
-    HALO_CHECK(S.bucket_sums.reserve(NB * 128));
-    HALO_CHECK(S.window_sums.reserve(SW * 128));
+    HALO_CHECK(plan_reserve(S, pl, 0));
     uint32_t* ent = S.lists.as<uint32_t>();
     uint32_t* ekey = ent + (size_t)W * TS;
     uint32_t* tot = ekey + (size_t)W * TS;
-    uint4* P_first = S.partials.as<uint4>();
-    uint4* P_last = P_first + PARTIAL_U4 * nchunks;
-    uint4* P_g1 = P_last + PARTIAL_U4 * nchunks;
-    uint4* P_g2 = P_g1 + PARTIAL_U4 * (ng1 + 1);
 
     const uint32_t* lists_in = S.digits.as<const uint32_t>();
     if (shifted) {
@@ -1193,39 +1067,12 @@ static int msm_shared_batch_t(DeviceState* st, const uint4* bases, const uint4* 
                        (const uint32_t*)ekey, (const uint32_t*)tot, (uint32_t)len, (uint32_t)(W * B),
                        shifted ? (uint32_t)ilog2(T) : 31u, shifted ? (uint32_t)shift_stride : 0u,
                        S.keys.as<uint32_t>(), S.vals.as<uint32_t>());
-    hipLaunchKernelGGL(k_acc<Cv>, dim3(grid_for(nchunks, 256)), dim3(256), 0, s, S.keys.as<const uint32_t>(),
-                       S.vals.as<const uint32_t>(), (const uint32_t*)(tot + 1), K, bases, 1u, 0u, (size_t)0, 32u, 0u,
-                       P_first, P_last, S.bucket_sums.as<uint4>(), S.bstart.as<uint32_t>(), (uint32_t)NB, 31u, 0u, 1u);
-    HALO_HIP(hipGetLastError());
-    MsmTailArgs ta;
-    ta.num_cu = (uint32_t)st->num_cu;
-    ta.n = T;
-    ta.skeys = S.keys.as<const uint32_t>();
-    ta.scount = tot + 1;
-    ta.K = K;
-    ta.NB = NB;
-    ta.E = E;
-    ta.first = P_first;
-    ta.last = P_last;
-    ta.g1 = P_g1;
-    ta.g2 = P_g2;
-    ta.ng1 = ng1;
-    ta.ng2 = ng2;
-    ta.bstart = S.bstart.as<uint32_t>();
-    ta.bucket_sums = S.bucket_sums.as<uint4>();
-    ta.rows = ta.cols = ta.terms = nullptr;  // k_batch_window_sums needs no grid scratch
-    ta.window_sums = S.window_sums.as<uint4>();
-    ta.L = L;
-    ta.H = H;
-    ta.logH = logH;
-    ta.logL = logL;
-    ta.NT = NT;
-    ta.SW = (int)SW;
-    ta.c = c;
-    ta.hide_table = nullptr;
-    ta.hide_scalar = nullptr;
-    ta.out_wrapped = nullptr;
-    ta.batch_windows = true;
+    // the entry values are point indices already; tot[1]: the entries in total
+    AccArgs a{S.keys.as<const uint32_t>(), S.vals.as<const uint32_t>(), tot + 1, bases};
+    a.profiled = false;
+    HALO_CHECK(acc_launch<Cv>(pl, S, a, s));
+    MsmTailArgs ta = plan_tail_args(st, pl, S, T, S.keys.as<const uint32_t>(), tot + 1);
+    ta.batch_windows = true;  // k_batch_window_sums needs no grid scratch
     HALO_CHECK(msm_tail_launch(curve_id<Cv>(), ta, s));
     hipLaunchKernelGGL(k_batch_horner<Cv>, dim3(grid_for(len, 64)), dim3(64), 0, s, S.window_sums.as<const uint4>(),
                        (uint32_t)len, W, c, out, (int)xyzz_out);
@@ -1835,7 +1682,7 @@ extern "C" int halo_point_dot_projective(halo_curve_t curve, const halo_fe_t* sc
         HALO_HIP(hipGetLastError());
     }
     HALO_CHECK(msm_device(st, curve, st->scratch[1].ptr, st->scratch[2].ptr, n, nullptr, nullptr, st->scratch[3].ptr, s,
-                          false, false, true));
+                          MsmOpts::Sync().xyzz()));
     return d2h_point(curve, st->scratch[3].ptr, out, s);
 }
 
@@ -1864,7 +1711,7 @@ extern "C" int halo_msm(halo_curve_t curve, const halo_wrapped_point_t* bases, s
                             st->scratch[3].ptr, s));
     } else {
         HALO_CHECK(msm_device(st, curve, st->scratch[1].ptr, st->scratch[2].ptr, n, nullptr, nullptr, st->scratch[3].ptr,
-                              s, false, false, true));
+                              s, MsmOpts::Sync().xyzz()));
     }
     return d2h_point(curve, st->scratch[3].ptr, out, s);
 }
@@ -2116,7 +1963,7 @@ extern "C" int halo_msm_srs(halo_curve_t curve, const halo_fe_t* scalars, size_t
     HALO_CHECK(st->scratch[2].reserve(std::max<size_t>(n, 1) * 32));
     HALO_CHECK(st->scratch[3].reserve(128));
     HALO_CHECK(copy_h2d(st->scratch[2].ptr, scalars, n * 32, s));
-    HALO_CHECK(msm_srs_device(st, curve, st->scratch[2].ptr, n, nullptr, st->scratch[3].ptr, s, false, true));
+    HALO_CHECK(msm_srs_device(st, curve, st->scratch[2].ptr, n, nullptr, st->scratch[3].ptr, s, MsmOpts::Sync().xyzz()));
     return d2h_point(curve, st->scratch[3].ptr, out, s);
 }
 
@@ -2132,12 +1979,12 @@ extern "C" int halo_msm_dev(halo_curve_t curve, const void* d_bases, const void*
     ScratchUse su(st, s);
     HALO_CHECK(st->scratch[7].reserve(128));
     if (!d_bases) {
-        HALO_CHECK(msm_srs_device(st, curve, d_scalars, n, nullptr, st->scratch[7].ptr, s, false, true));
+        HALO_CHECK(msm_srs_device(st, curve, d_scalars, n, nullptr, st->scratch[7].ptr, s, MsmOpts::Sync().xyzz()));
     } else {
         HALO_CHECK(st->scratch[6].reserve(std::max<size_t>(n, 1) * 64));
         HALO_CHECK(convert_wrapped_to_internal(curve, d_bases, st->scratch[6].ptr, n, s));
         HALO_CHECK(msm_device(st, curve, st->scratch[6].ptr, d_scalars, n, nullptr, nullptr, st->scratch[7].ptr, s,
-                              false, false, true));
+                              MsmOpts::Sync().xyzz()));
     }
     return d2h_point(curve, st->scratch[7].ptr, out, s);
 }
@@ -2151,7 +1998,7 @@ extern "C" int halo_msm_dev_async(halo_curve_t curve, const void* d_bases, const
     if (!st) return HALO_EDEVICE;
     std::lock_guard<std::mutex> g(st->mu);
     hipStream_t s = (hipStream_t)stream;
-    if (!d_bases) return msm_srs_device(st, curve, d_scalars, n, nullptr, d_out, s, true);
+    if (!d_bases) return msm_srs_device(st, curve, d_scalars, n, nullptr, d_out, s, MsmOpts::Async());
     // the set is claimed once: its previous tail is waited for before the conversion overwrites conv,
     // and the MSM runs on that same set
     int set = -1;
@@ -2159,8 +2006,7 @@ extern "C" int halo_msm_dev_async(halo_curve_t curve, const void* d_bases, const
     HALO_CHECK(msm_claim_set(st, s, &set, &conv));
     HALO_CHECK(conv->reserve(std::max<size_t>(n, 1) * 64));
     HALO_CHECK(convert_wrapped_to_internal(curve, d_bases, conv->ptr, n, s));
-    return msm_device(st, curve, conv->ptr, d_scalars, n, nullptr, nullptr, d_out, s, true, false, false, nullptr,
-                      set);
+    return msm_device(st, curve, conv->ptr, d_scalars, n, nullptr, nullptr, d_out, s, MsmOpts::Async().on_set(set));
 }
 
 namespace halo {
@@ -2183,7 +2029,7 @@ int msm_batch_device(DeviceState* st, int curve, const void* const* d_scalars, c
         return rc;
     }
     for (size_t i = 0; i < k; i++)
-        HALO_CHECK(msm_srs_device(st, curve, d_scalars[i], lens[i], nullptr, (char*)d_out + 64 * i, s, true));
+        HALO_CHECK(msm_srs_device(st, curve, d_scalars[i], lens[i], nullptr, (char*)d_out + 64 * i, s, MsmOpts::Async()));
     return HALO_OK;
 }
 }  // namespace halo
@@ -2222,8 +2068,8 @@ extern "C" int halo_msm_srs_windows_dev(halo_curve_t curve, const void* d_scalar
     int rc;
     DISPATCH_CURVE(curve, Cv, {
         rc = msm_device_t<Cv>(st, srs.shifted.as<const uint4>(), true, srs.n, (const uint4*)d_scalars, n, c, nullptr,
-                              nullptr, (uint4*)d_out, (hipStream_t)stream, true, 32, false, false, nullptr, -1, w_lo,
-                              w_hi, w0);
+                              nullptr, (uint4*)d_out, (hipStream_t)stream, MsmOpts::Async(),
+                              MsmWindowRange{w_lo, w_hi, w0});
     });
     return rc;
 }
@@ -2273,7 +2119,7 @@ extern "C" int halo_pedersen_commit(halo_curve_t curve, const halo_fe_t* w, cons
     char* small = (char*)st->scratch[3].ptr;  // [0, 128) the XYZZ sum, [128, 160) w
     if (w) HALO_CHECK(copy_h2d(small + 128, w, 32, s));
     HALO_CHECK(msm_device(st, curve, st->scratch[1].ptr, st->scratch[2].ptr, n, w ? srs.s_table.ptr : nullptr,
-                          w ? small + 128 : nullptr, small, s, false, false, true));
+                          w ? small + 128 : nullptr, small, s, MsmOpts::Sync().xyzz()));
     return d2h_point(curve, small, out, s);
 }
 
@@ -2311,6 +2157,7 @@ extern "C" int halo_pcdl_commit(halo_curve_t curve, const halo_fe_t* coeffs, siz
     HALO_CHECK(copy_h2d(st->scratch[2].ptr, coeffs, m * 32, s));
     char* small = (char*)st->scratch[3].ptr;  // [0, 128) the XYZZ sum, [128, 160) w
     if (w) HALO_CHECK(copy_h2d(small + 128, w, 32, s));
-    HALO_CHECK(msm_srs_device(st, curve, st->scratch[2].ptr, m, w ? small + 128 : nullptr, small, s, false, true));
+    HALO_CHECK(msm_srs_device(st, curve, st->scratch[2].ptr, m, w ? small + 128 : nullptr, small, s,
+                              MsmOpts::Sync().xyzz()));
     return d2h_point(curve, small, out, s);
 }

@@ -1,21 +1,37 @@
 // Internal interfaces shared between msm.hip, ipa.hip and the multi-GPU glue.
 #pragma once
 #include <vector>
+#include "msm_plan.hpp"
 #include "runtime.hpp"
 
 namespace halo {
 
-int msm_window_bits(size_t n);
+// Options of msm_device / msm_srs_device / msm_srs_range_device.  Sync() / Async() state the one
+// option without a default; the setters name the others at the call site.
+struct MsmOpts {
+    bool async;                       // false: stream s also waits for the reduction tail; true: msm_join does
+    uint32_t blk_lg = 32;             // msm_srs_range_device: half-blocks of 2^blk_lg points (32: contiguous)
+    bool hide_glv = false;            // the hiding table is {2^i P : i < 128}, the scalar GLV-split (k_hide_term)
+    bool out_xyzz = false;            // the result as 128 B packed XYZZ (host_xyzz_to_wrapped), not a WrappedPoint
+    hipEvent_t hide_ready = nullptr;  // event after which the hiding table is complete (built on another stream)
+    int preset = -1;                  // msm_device: the scratch set the caller claimed (msm_claim_set)
+    static MsmOpts Sync() { return MsmOpts(false); }
+    static MsmOpts Async() { return MsmOpts(true); }
+    MsmOpts& blocks(uint32_t lg) { return blk_lg = lg, *this; }
+    MsmOpts& glv_hide() { return hide_glv = true, *this; }
+    MsmOpts& xyzz() { return out_xyzz = true, *this; }
+    MsmOpts& after(hipEvent_t ready) { return hide_ready = ready, *this; }
+    MsmOpts& on_set(int set) { return preset = set, *this; }
+
+private:
+    explicit MsmOpts(bool a) : async(a) {}
+};
+
 // MSM over device-resident internal-format affine bases (64 B each) and ark-format scalars.
 // Writes one ark WrappedPoint (64 B) to d_out_wrapped (device).  Optional hiding term
-// hide_scalar * P where hide_table = {2^i P : i < 256} (internal affine; both device pointers), or
-// with hide_glv {2^i P : i < 128} and the GLV split of the scalar (k_hide_term).  out_xyzz: the
-// result is written as 128 B packed XYZZ instead of an affine WrappedPoint (host_xyzz_to_wrapped).
-// hide_ready: event after which the hiding table is complete (built on another stream).
+// hide_scalar * P where hide_table = {2^i P : i < 256} (internal affine; both device pointers).
 int msm_device(DeviceState* st, int curve, const void* bases_int, const void* scalars_ark, size_t n,
-               const void* hide_table, const void* hide_scalar, void* d_out_wrapped, hipStream_t s,
-               bool async = false, bool hide_glv = false, bool out_xyzz = false, hipEvent_t hide_ready = nullptr,
-               int preset = -1);
+               const void* hide_table, const void* hide_scalar, void* d_out_wrapped, hipStream_t s, const MsmOpts& o);
 // Claims the scratch set the next MSM on stream s will use (s waits for its previous tail) and
 // returns its base-conversion buffer; pass the set to msm_device as `preset`.
 int msm_claim_set(DeviceState* st, hipStream_t s, int* set, DevBuf** conv);
@@ -25,25 +41,21 @@ int msm_batch_device(DeviceState* st, int curve, const void* const* d_scalars, c
                      hipStream_t s);
 // Destroys the MSM pipeline's streams and events (halo_shutdown).
 void msm_shutdown();
-// Releases the pooled IPA sessions (halo_shutdown, ipa.hip).
-void ipa_shutdown();
 // Makes stream s wait for the reduction tails of the async MSMs enqueued on s.
 int msm_join(DeviceState* st, hipStream_t s);
 // Restarts the scratch-set slot assignment (no owners, first sets) when no MSM tail is running.
 void msm_slots_reset(DeviceState* st);
 // MSM over the resident SRS prefix (window-shifted copies when precomputed); optional hiding
-// scalar (ark, device pointer) times S.
+// scalar (ark, device pointer) times S.  Of the options, async and out_xyzz apply.
 int msm_srs_device(DeviceState* st, int curve, const void* scalars_ark, size_t n, const void* hide_scalar,
-                   void* d_out_wrapped, hipStream_t s, bool async = false, bool out_xyzz = false);
+                   void* d_out_wrapped, hipStream_t s, const MsmOpts& o);
 // MSM over the resident SRS range [offset, offset + n) with a caller hiding table (2^i P, i < 256,
 // internal affine) and scalar; uses the window-shifted copies (returns HALO_EINVAL without them).
 // blk_lg < 32: scalar i goes with point offset + i + ((i >> blk_lg) << blk_lg), i.e. the blocks
 // [2b B, 2b B + B) (B = 2^blk_lg) of the range -- the even half-blocks an IPA round's G_l / G_r
 // occupy in the unfolded SRS.
-int msm_srs_range_device(DeviceState* st, int curve, size_t offset, const void* scalars_ark, size_t n,
-                         const void* hide_table, const void* hide_scalar, void* d_out_wrapped, hipStream_t s,
-                         bool async, uint32_t blk_lg = 32, bool hide_glv = false, bool out_xyzz = false,
-                         hipEvent_t hide_ready = nullptr);
+int msm_srs_range_device(DeviceState* st, int curve, size_t offset, const void* scalars_ark, size_t n, const void* hide_table,
+                         const void* hide_scalar, void* d_out_wrapped, hipStream_t s, const MsmOpts& o);
 // Batched MSM with shared scalars: out[i] = sum_{u < T} w[u] bases[i + u len] for i < len
 // (internal affine bases, ark scalars; outputs internal affine, or XYZZ (128 B) when xyzz_out;
 // stream-ordered on s).
@@ -94,6 +106,10 @@ size_t msm_tiny_max();
 // plus_wrapped (device WrappedPoint, or null): added to the result.
 int msm_srs_small(DeviceState* st, int curve, const void* scalars_ark, size_t n, const void* hide_scalar,
                   void* d_out_wrapped, hipStream_t s, bool out_xyzz = false, const void* plus_wrapped = nullptr);
+// ---- not MSM: what ipa.hip, field_ops.hip and the NTT declare here for each other (the pcdl_*
+// steps, the host point / scalar conversions, ntt_device_dispatch) ------------------------------
+// Releases the pooled IPA sessions (halo_shutdown, ipa.hip).
+void ipa_shutdown();
 // The hiding branch of pcdl::open_without_eval on device buffers (field_ops.hip), stream-ordered on s:
 // p_bar = (X - z) q (q: d ark coefficients, z: ark scalar) -> d + 1 ark coefficients;
 // p' = p (len coefficients, zero-padded to n) + alpha p_bar (p' may alias p), w' = w + alpha w_bar,
@@ -125,26 +141,19 @@ int ntt_device_dispatch(DeviceState* st, int field, const void* d_in, void* d_ou
                         size_t batch, int inverse, hipStream_t s, void* d_tmp2 = nullptr, unsigned prune = 0,
                         const std::vector<unsigned>* rad = nullptr);
 
-// chunk-partial group size of the skew guard (msm_tail.hip k_group_sums)
-constexpr uint32_t MSM_GROUP = 64;
-
+// ---- the MSM's reduction tail (msm_tail.hip) ---------------------------------------------------
 // Inputs of the MSM's reduction tail (msm_tail.hip), launched on the tail stream.
 struct MsmOuts8 {
     uint4* o[8];
 };
 struct MsmTailArgs {
-    size_t n, NB, E, ng1, ng2;
+    MsmPlan p;  // K, NB, ng1, ng2 and the reduction grid (SW windows of H x L buckets, NT bit terms)
+    size_t n;   // 0: an empty MSM, the tail launches nothing
     const uint32_t* skeys;
     const uint32_t* scount;
-    uint32_t K;
     uint4 *first, *last, *g1, *g2;
     uint32_t* bstart;
     uint4 *bucket_sums, *rows, *cols, *terms, *window_sums;
-    uint32_t L, H, logH, logL, NT;
-    int SW, c;
-    const uint4* hide_table;
-    const uint4* hide_scalar;
-    uint4* out_wrapped;
     bool batch_windows = false;  // SW windows of 128 buckets: k_batch_window_sums instead of the grid reduction
     // SW == 1 only: k_bitcombine also does k_final's work (+ final_hide, -> final_out as an ark
     // WrappedPoint (1) or packed XYZZ (2)); 0: it writes window_sums and k_final follows

@@ -335,45 +335,45 @@ static unsigned grid_for_t(size_t n, unsigned thr) { return (unsigned)std::max<s
 template <class Cv>
 static int tail_launch_t(const MsmTailArgs& a, hipStream_t ts) {
     if (a.n > 0) {
-        if (a.ng1)
-            hipLaunchKernelGGL(k_group_sums<Cv>, dim3((unsigned)a.ng1), dim3(MSM_GROUP), 0, ts, a.skeys, a.scount, a.K,
+        if (a.p.ng1)
+            hipLaunchKernelGGL(k_group_sums<Cv>, dim3((unsigned)a.p.ng1), dim3(MSM_GROUP), 0, ts, a.skeys, a.scount, a.p.K,
                                1u, (const uint4*)a.first, a.g1);
-        if (a.ng2)
-            hipLaunchKernelGGL(k_group_sums<Cv>, dim3((unsigned)a.ng2), dim3(MSM_GROUP), 0, ts, a.skeys, a.scount, a.K,
+        if (a.p.ng2)
+            hipLaunchKernelGGL(k_group_sums<Cv>, dim3((unsigned)a.p.ng2), dim3(MSM_GROUP), 0, ts, a.skeys, a.scount, a.p.K,
                                MSM_GROUP, (const uint4*)a.g1, a.g2);
         // two lanes per bucket, each summing half of its chunk partials (measured per bucket: one lane
         // 167 us, two 138 us, four 172 us isolated at 2^20)
         constexpr int lanes = 2;
-        hipLaunchKernelGGL((k_merge<Cv, lanes>), dim3(grid_for_t(a.NB * lanes, 256)), dim3(256), 0, ts, (const uint32_t*)a.bstart,
-                           a.scount, a.K, a.NB, (const uint4*)a.first, (const uint4*)a.last,
+        hipLaunchKernelGGL((k_merge<Cv, lanes>), dim3(grid_for_t(a.p.NB * lanes, 256)), dim3(256), 0, ts, (const uint32_t*)a.bstart,
+                           a.scount, a.p.K, a.p.NB, (const uint4*)a.first, (const uint4*)a.last,
                            (const uint4*)a.g1, (const uint4*)a.g2, a.bucket_sums);
         if (a.batch_windows) {
-            const uint32_t B = a.L * a.H;
+            const uint32_t B = a.p.L * a.p.H;
             if (B < 2 * BATCH_SEGS || B > 512 || (B & (B - 1)))
                 return set_error(HALO_EINVAL, "batched window sums: %u buckets per window", B);
             // lanes per window: 8, or 8 buckets per lane above 64 buckets
             const uint32_t segs = std::max(BATCH_SEGS, B / 8);
             auto kws = segs == 8 ? k_batch_window_sums<Cv, 8> : segs == 16 ? k_batch_window_sums<Cv, 16>
                      : segs == 32 ? k_batch_window_sums<Cv, 32> : k_batch_window_sums<Cv, 64>;
-            hipLaunchKernelGGL(kws, dim3(grid_for_t((size_t)a.SW * segs, 256)), dim3(256), 0, ts,
-                               (const uint4*)a.bucket_sums, (uint32_t)a.SW, B, a.window_sums);
+            hipLaunchKernelGGL(kws, dim3(grid_for_t((size_t)a.p.SW * segs, 256)), dim3(256), 0, ts,
+                               (const uint4*)a.bucket_sums, (uint32_t)a.p.SW, B, a.window_sums);
             HALO_HIP(hipGetLastError());
             return HALO_OK;
         }
         // entries per lane: the fewest (1, 2, 4) that keep the grid within one block per CU
         uint32_t epl = 1;
-        while (epl < 4 && 2 * epl <= std::min(a.L, a.H)) {
-            const RowcolShape sh = rowcol_shape(a.L, a.H, epl);
-            if ((size_t)(sh.nrb + sh.ncb) * a.SW <= (size_t)a.num_cu) break;
+        while (epl < 4 && 2 * epl <= std::min(a.p.L, a.p.H)) {
+            const RowcolShape sh = rowcol_shape(a.p.L, a.p.H, epl);
+            if ((size_t)(sh.nrb + sh.ncb) * a.p.SW <= (size_t)a.num_cu) break;
             epl *= 2;
         }
-        const RowcolShape sh = rowcol_shape(a.L, a.H, epl);
-        hipLaunchKernelGGL(k_rowcol<Cv>, dim3(sh.nrb + sh.ncb, a.SW), dim3(256), 0, ts, (const uint4*)a.bucket_sums,
-                           a.L, a.H, epl, a.rows, a.cols);
-        hipLaunchKernelGGL(k_bitterms<Cv>, dim3(a.NT, a.SW), dim3(256), 0, ts, (const uint4*)a.rows,
-                           (const uint4*)a.cols, a.H, a.L, a.logH, a.terms);
-        const int fin = a.SW == 1 ? a.final_mode : 0;
-        hipLaunchKernelGGL(k_bitcombine<Cv>, dim3(a.SW), dim3(64), 0, ts, (const uint4*)a.terms, a.NT, a.logH, a.logL,
+        const RowcolShape sh = rowcol_shape(a.p.L, a.p.H, epl);
+        hipLaunchKernelGGL(k_rowcol<Cv>, dim3(sh.nrb + sh.ncb, a.p.SW), dim3(256), 0, ts, (const uint4*)a.bucket_sums,
+                           a.p.L, a.p.H, epl, a.rows, a.cols);
+        hipLaunchKernelGGL(k_bitterms<Cv>, dim3(a.p.NT, a.p.SW), dim3(256), 0, ts, (const uint4*)a.rows,
+                           (const uint4*)a.cols, a.p.H, a.p.L, a.p.logH, a.terms);
+        const int fin = a.p.SW == 1 ? a.final_mode : 0;
+        hipLaunchKernelGGL(k_bitcombine<Cv>, dim3(a.p.SW), dim3(64), 0, ts, (const uint4*)a.terms, a.p.NT, a.p.logH, a.p.logL,
                            a.window_sums, fin, a.final_hide, a.final_out, a.pair_hide, a.pair_outs, a.pair_host, a.pair_seq);
     }
     HALO_HIP(hipGetLastError());

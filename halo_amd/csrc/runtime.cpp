@@ -111,7 +111,7 @@ static bool g_prof_on = false;
 bool prof_enabled() { return g_prof_on; }
 
 ProfScope::ProfScope(const char* name, hipStream_t stream) {
-    if (!g_prof_on) return;
+    if (!g_prof_on || !name) return;
     s = stream;
     std::lock_guard<std::mutex> g(g_prof_mu);
     for (size_t i = 0; i < g_prof.size(); i++)

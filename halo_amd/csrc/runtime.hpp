@@ -152,7 +152,7 @@ struct ProfScope {
     int slot = -1;
     hipEvent_t a = nullptr, b = nullptr;
     hipStream_t s = nullptr;
-    ProfScope(const char* name, hipStream_t stream);
+    ProfScope(const char* name, hipStream_t stream);  // name null: an untimed launch
     ~ProfScope();
 };
 

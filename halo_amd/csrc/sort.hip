@@ -243,7 +243,8 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_hist(RsIn in, uint32_t ntiles
 // from the scalars here instead of being written by k_digits and read back (32 B of scalar per
 // W = 15 entries instead of 2 x 4 B per entry).  Thread = one scalar, round = window: a tile is
 // RS_THREADS scalars x W windows.  Entry key = |d| - 1, value = (w n + i) | sign, as k_digits + pass 0.
-// (P > 1 outputs: key p B + |d| - 1 has the same low byte as |d| - 1, B being a multiple of 256)
+// (P > 1 outputs: key p B + |d| - 1 has the same low byte as |d| - 1 only when B is a multiple of 256,
+// which msm_radix_sort's check of the fused arguments requires)
 template <class S>
 __global__ __launch_bounds__(RS_THREADS) void k_rs_hist_sc(const RsScalars sc, int c, int W, uint32_t ntiles,
                                                          uint32_t* hist, uint32_t* chunk, uint32_t* ctr,
@@ -553,8 +554,10 @@ int msm_radix_sort(const uint32_t* digits, size_t E, size_t npw, uint32_t B, uin
     for (auto& q : plan) ntmax = std::max(ntmax, tiles_of(q.second));
     // fused first pass: tiles of RS_THREADS scalars x W windows
     const size_t nsc = fused ? fused->n * (size_t)fused->P : 0;
-    if (fused && (fused->P < 1 || fused->P > 8 || fused->W > rs_rounds<8>() || nsc >= (1ull << 31) / 16))
-        return set_error(HALO_EINVAL, "fused sort pass: %d outputs, %d windows, %zu scalars", fused->P, fused->W, nsc);
+    if (fused && (fused->P < 1 || fused->P > 8 || fused->W > rs_rounds<8>() || nsc >= (1ull << 31) / 16 ||
+                  (fused->P > 1 && (B & 255))))
+        return set_error(HALO_EINVAL, "fused sort pass: %d outputs of %u buckets, %d windows, %zu scalars", fused->P, B,
+                         fused->W, nsc);
     const uint32_t ntiles0 = fused ? (uint32_t)std::max<size_t>(1, (nsc + RS_THREADS - 1) / RS_THREADS) : 0u;
     ntmax = std::max(ntmax, ntiles0);
     HALO_CHECK(S.keys[0].reserve(std::max<size_t>(E, 1) * 4));

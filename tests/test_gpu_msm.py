@@ -237,7 +237,7 @@ def test_msm_2p20_all_equal_scalars_shifted(hal):
 @pytest.mark.gpu
 def test_msm_small_chunks_shifted_skew(hal):
     """Latency-bound MSMs over the 2^20 window-shifted SRS take short accumulation chunks (K =
-    ceil(sqrt(entries / buckets)), msm.hip msm_chunk_len): random, all-equal, two-valued and mostly
+    ceil(sqrt(entries / buckets)), msm_plan.hpp msm_chunk_len): random, all-equal, two-valued and mostly
     zero scalars at n = 2^4 .. 2^16, checked against (sum_j s_j k_j) G."""
     c = P.PALLAS
     r = c.scalar

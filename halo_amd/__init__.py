@@ -9,6 +9,8 @@ reference's names, argument meaning and assertion messages:
     halo_amd.poly     -- crates/group/src/poly.rs   (Domain, Evals: NTT / iNTT wrappers)
     halo_amd.pedersen -- crates/accumulation/src/pedersen.rs (commit)
     halo_amd.pcdl     -- crates/accumulation/src/pcdl.rs     (commit, open_without_eval round loop)
+    halo_amd.schnorr  -- crates/schnorr/src/lib.rs (hash_message, PublicKey::verify) and the inner
+                         Poseidon sponge of crates/poseidon, as batches of independent items
 
 Field elements are numpy uint64 arrays of shape (n, 4) in arkworks Montgomery form; points are
 (n, 8) WrappedPoint arrays (x, y Montgomery limbs; (0, 0) = identity).  There is no CPU fallback:
@@ -16,4 +18,4 @@ without the HIP library or a GPU every call raises.
 """
 from . import _lib  # noqa: F401
 
-__all__ = ["_lib", "group", "poly", "pedersen", "pcdl"]
+__all__ = ["_lib", "group", "poly", "pedersen", "pcdl", "schnorr"]

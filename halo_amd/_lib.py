@@ -128,6 +128,13 @@ SIGNATURES = {
     "halo_ipa_end": [_vp, _vp, _vp],
     "halo_ipa_end_multi": [_vp, _sz, _vp, _vp],
     "halo_ipa_fold_host": [ctypes.c_int, _vp, _vp, _vp, _sz, _vp, _vp],
+    "halo_poseidon_set_params": [ctypes.c_int, _vp, _vp],
+    "halo_poseidon_hash_batch": [ctypes.c_int, _vp, _sz, _sz, _vp],
+    "halo_poseidon_hash_batch_dev": [ctypes.c_int, _vp, _sz, _sz, _vp, _vp],
+    "halo_schnorr_hash_batch": [ctypes.c_int, _vp, _vp, _vp, _sz, _sz, _vp],
+    "halo_schnorr_hash_batch_dev": [ctypes.c_int, _vp, _vp, _vp, _sz, _sz, _vp, _vp],
+    "halo_schnorr_verify_batch": [ctypes.c_int, _vp, _vp, _vp, _vp, _sz, _sz, _vp],
+    "halo_schnorr_verify_batch_dev": [ctypes.c_int, _vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp],
     "halo_field_op": [ctypes.c_int, ctypes.c_int, _vp, _vp, _sz, _vp],
     "halo_curve_op": [ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _sz, _vp],
 }

@@ -36,7 +36,7 @@ void clear_error();
 
 // ---- tuning (halo_set_tuning): path selections the parity tests pin; read on every use
 enum TuneKey { TUNE_IPA_WEIGHTED, TUNE_IPA_TAIL, TUNE_IPA_SRS_TAIL_N, TUNE_IPA_MAT_N, TUNE_MSM_MULTI_MAX, TUNE_IPA_POOL_KEEP,
-               TUNE_NTT_BIG_MAX_LOG, TUNE_NTT_EVEN_SPLIT, TUNE_IPA_PAIR_MAX, TUNE_COUNT };
+               TUNE_NTT_BIG_MAX_LOG, TUNE_NTT_EVEN_SPLIT, TUNE_IPA_PAIR_MAX, TUNE_POSEIDON_LANES, TUNE_COUNT };
 long long tuning(TuneKey k);
 
 // ---- device buffers ---------------------------------------------------------------------------
@@ -116,6 +116,12 @@ struct DeviceState {
         DevBuf t;
     };
     std::vector<std::unique_ptr<RTable>> rt;
+    // Poseidon parameters of each field as the kernels read them (schnorr.hip): 174 constants in limb
+    // form, re-uploaded when halo_poseidon_set_params has installed a newer version
+    DevBuf poseidon[2];
+    uint64_t poseidon_ver[2] = {0, 0};
+    DevBuf schnorr_gtab[2];  // per curve: d G and phi(d G), 1 <= d <= 8, XYZZ (the fixed-base table of s G)
+    DevBuf schnorr_e;        // the challenges of a verification batch (canonical words)
     // ScratchUse state: completion event of the last scratch user and its stream
     hipEvent_t scratch_ev = nullptr;
     hipStream_t scratch_last = nullptr;

@@ -2,7 +2,9 @@
  * halo_gpu.h -- C ABI of the MI355X (gfx950) backend for the rasmus-kirk/halo proving hot path.
  *
  * Every entry point replaces one reference function (or the arkworks call inside it) on the path
- * named by BASELINE.json's north_star; the reference interface each one stands in for is cited
+ * named by BASELINE.json's north_star, or on its batched Schnorr verification (crates/plonk/src/main.rs:
+ * 35-47; the Poseidon hashes of that batch run on the device, a single Fiat-Shamir transcript remains
+ * the caller's); the reference interface each one stands in for is cited
  * next to it (paths relative to the reference root).  A Rust `extern "C"` shim that binds these
  * symbols is given in INTEGRATION.md.
  *
@@ -79,7 +81,8 @@ int halo_stream_sync(void* stream);
  * 2^18), "ipa_pool_keep_bytes" (an idle pooled IPA session keeps at most this many bytes of device
  * buffers; default 2^30), "ipa_pair_max" (weighted rounds up to this half-length form L and R as one
  * MSM; default 2^19), "ntt_big_max_log" (NTTs up to 2^this use 11-bit passes; default 22),
- * "ntt_even_split" (1: stages split evenly over the passes; default 0).  Every setting yields the same results; the parity tests pin each path with it.  The
+ * "ntt_even_split" (1: stages split evenly over the passes; default 0), "poseidon_lanes" (lanes per sponge
+ * of the batched Poseidon kernels, 1 or 3; default 0: by batch size).  Every setting yields the same results; the parity tests pin each path with it.  The
  * reference has no counterpart (host-side knob of this backend only).  HALO_EINVAL on an unknown key. */
 int halo_set_tuning(const char* key, long long value);
 int halo_get_tuning(const char* key, long long* value);
@@ -406,6 +409,43 @@ int halo_ipa_end_multi(halo_ipa_session* const* ses, size_t k, halo_wrapped_poin
  * on the left halves. */
 int halo_ipa_fold_host(halo_curve_t curve, halo_wrapped_point_t* gs, halo_fe_t* cs, halo_fe_t* zs,
                        size_t m, const halo_fe_t* xi, const halo_fe_t* xi_inv);
+
+/* ------------------------------------------------------------------ Poseidon and Schnorr batches
+ * The reference's first benchmark verifies 40 000 independent signatures (crates/plonk/src/main.rs:35-47);
+ * each is one Poseidon hash of 5 + msg_len base-field elements and two scalar multiplications.  A
+ * single Fiat-Shamir transcript stays with the caller (serial host logic); these calls run k
+ * independent sponges / verifications as one batch on the device. */
+/* Poseidon parameters of `field` (PastaConfig's POSEIDON_MDS / POSEIDON_ROUND_CONSTANTS,
+ * crates/group/src/poseidon_consts.rs as used by crates/poseidon/src/inner_sponge.rs:3-108): the 3 x 3
+ * MDS matrix row-major and the 55 x 3 round constants, ark Montgomery limbs, canonical.  They are not
+ * compiled into the library; set once per process and field (host-only call; each device copies them on
+ * its next use), before the hashing and Schnorr calls, which otherwise return HALO_EINVAL. */
+int halo_poseidon_set_params(halo_field_t field, const halo_fe_t* mds, const halo_fe_t* rc);
+/* k independent inner sponges (inner_sponge.rs:66-108): row i of `in` (k x len, row-major, len >= 0)
+ * is absorbed into a fresh sponge, which is squeezed once into out[i].  k = 0 touches nothing; `in`
+ * may be NULL when len = 0. */
+int halo_poseidon_hash_batch(halo_field_t field, const halo_fe_t* in, size_t len, size_t k, halo_fe_t* out);
+int halo_poseidon_hash_batch_dev(halo_field_t field, const void* d_in, size_t len, size_t k, void* d_out, void* stream);
+/* hash_message (crates/schnorr/src/lib.rs:24-35) for k (pk, R, message) triples: Sponge::new(
+ * Protocols::SIGNATURE), absorb_g_affine(&[pk, R]) (x then y; the identity as (0, 0)), absorb_fq(message),
+ * challenge() (crates/poseidon/src/outer_sponge.rs:24-43,51-61,86-95) -> k scalars e of `curve` (ark).
+ * msgs: k x msg_len base-field elements of `curve`, row-major; NULL allowed when msg_len = 0. */
+int halo_schnorr_hash_batch(halo_curve_t curve, const halo_wrapped_point_t* pk, const halo_wrapped_point_t* R,
+                            const halo_fe_t* msgs, size_t msg_len, size_t k, halo_fe_t* e_out);
+int halo_schnorr_hash_batch_dev(halo_curve_t curve, const void* d_pk, const void* d_R, const void* d_msgs,
+                                size_t msg_len, size_t k, void* d_e_out, void* stream);
+/* PublicKey::verify (crates/schnorr/src/lib.rs:71-79) for k signatures (R[i], s[i]) on messages
+ * msgs[i] under keys pk[i]: ok_out[i] = 1 iff s G == R + e pk with e = hash_message(pk, R, m) and
+ * G = Affine::generator() = (-1, 2), else 0.  s: scalars of `curve` (ark).  Identity pk, identity R and
+ * s = 0 follow the reference's arithmetic.  A pk or R that is neither the identity (0, 0) nor on the
+ * curve gives 0: the reference's Affine type makes that case unrepresentable (wrappers.rs:606 asserts
+ * is_on_curve on conversion), so it has no verdict there. */
+int halo_schnorr_verify_batch(halo_curve_t curve, const halo_wrapped_point_t* pk, const halo_wrapped_point_t* R,
+                              const halo_fe_t* s, const halo_fe_t* msgs, size_t msg_len, size_t k, uint8_t* ok_out);
+/* The same over device pointers; d_ok: k bytes of device memory.  Asynchronous on `stream` (the first
+ * call per device and curve builds the generator's table and waits for it). */
+int halo_schnorr_verify_batch_dev(halo_curve_t curve, const void* d_pk, const void* d_R, const void* d_s,
+                                  const void* d_msgs, size_t msg_len, size_t k, void* d_ok, void* stream);
 
 /* ------------------------------------------------------------------ measurement hooks
  * When enabled, the library brackets its dominant kernels (MSM bucket accumulation, NTT passes)

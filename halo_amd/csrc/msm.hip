@@ -7,8 +7,9 @@
 // Pipeline (all on the device, no host round trip):
 //   1. digits   : scalar (ark Montgomery) -> canonical -> W signed c-bit digits
 //                 (|d| <= 2^(c-1), W = ceil(256 / c)); key = (window, |d| - 1), value = index|sign.
-//   2. sort     : stable LSD radix sort (8-bit digits, LDS-staged coalesced runs; sort.hip) of the
-//                 W*n (bucket key, point ref) pairs; bucket starts from the sorted keys.
+//   2. sort     : LSD radix sort (8-bit digits, LDS-staged coalesced runs; sort.hip) of the
+//                 W*n (bucket key, point ref) pairs: grouped by key, ascending, the order within a
+//                 key unspecified; bucket starts from the sorted keys.
 //   3. tasks    : every bucket is cut into tasks of <= K entries (skew-proof: an all-equal scalar
 //                 vector becomes n/K equal tasks instead of one serial bucket).
 //   4. acc      : one thread per task sums its points with XYZZ mixed additions (8M + 2S).

@@ -1,4 +1,6 @@
-// Stable LSD radix sort of the MSM's (bucket key, point reference) pairs (part of SURVEY §8 row a3).
+// LSD radix sort of the MSM's (bucket key, point reference) pairs (part of SURVEY §8 row a3).
+// Contract: the pairs come out grouped by key, keys ascending; the order of the pairs of one key is
+// unspecified and may differ from run to run (k_acc's bucket sums do not depend on it).
 //
 // ark-ec's CPU Pippenger scatters every point straight into its bucket (a random read-modify-write
 // per point per window).  On MI355X the buckets are instead formed by sorting the W*n digit entries
@@ -8,8 +10,11 @@
 //   k_rs_hist    : per-tile LDS histogram of the digit -> hist[tile][digit] (coalesced)
 //                  and, by the kernel's last arrivers, the digit-major exclusive prefix of that table
 //                  without transposing it -> every tile's global run start per digit
-//   k_rs_scatter : stable in-tile ranking (each wave ranks its own contiguous quarter of the tile with
-//                  ballots that find equal digits among lanes; per-wave histograms order the waves),
+//   k_rs_scatter : in-tile ranking (each wave ranks its own contiguous eighth of the tile; per-wave
+//                  histograms order the waves): stable, with ballots that find equal digits among
+//                  lanes, where the order of equal digits carries the earlier passes' work, and with
+//                  one returning LDS add per entry where it does not -- the first pass, and every
+//                  wave whose slice is uniform in the bits already sorted;
 //                  the tile is staged in LDS in digit order and written back as contiguous runs per
 //                  digit (coalesced).
 // Pass 0 reads the raw digit array (skipping zero digits) and forms key = window * B + |d| - 1 and
@@ -245,7 +250,10 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_hist(RsIn in, uint32_t ntiles
 // RS_THREADS scalars x W windows.  Entry key = |d| - 1, value = (w n + i) | sign, as k_digits + pass 0.
 // (P > 1 outputs: key p B + |d| - 1 has the same low byte as |d| - 1 only when B is a multiple of 256,
 // which msm_radix_sort's check of the fused arguments requires)
-template <class S>
+// C: the window width when it is one of the widths the resident SRS copies use (16, 17: the
+// recoding's word indices and shifts are then constants and its loop unrolled, digits_core.hpp), or 0
+// for a run-time c.
+template <class S, int C>
 __global__ __launch_bounds__(RS_THREADS) void k_rs_hist_sc(const RsScalars sc, int c, int W, uint32_t ntiles,
                                                          uint32_t* hist, uint32_t* chunk, uint32_t* ctr,
                                                          uint32_t* count) {
@@ -255,7 +263,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_hist_sc(const RsScalars sc, i
     const uint32_t g = blockIdx.x * RS_THREADS + threadIdx.x;
     if (g < sc.P * sc.n) {
         uint32_t p, i;
-        scalar_signed_digits<S>(rs_scalar(sc, g, p, i), c, W, [&](int, uint32_t d) {
+        scalar_signed_digits<S, 0, C>(rs_scalar(sc, g, p, i), c, W, [&](int, uint32_t d) {
             if (d != DIGIT_NONE) atomicAdd(&h[d & 255u], 1u);
         });
     }
@@ -266,8 +274,9 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_hist_sc(const RsScalars sc, i
 // Each wave owns a contiguous eighth of the tile (1024 entries, 16 rounds of 64), so ranking is
 // wave-local (ballots + a wave-private LDS run counter per digit) and the workgroup needs only
 // three barriers: after the per-wave histograms, after the prefix, after staging.
-// SF: void, or the scalar field of a fused first pass (k_rs_hist_sc's entries, in.sc != null)
-template <int BITS, class SF = void, bool PASS0 = false>
+// SF: void, or the scalar field of a fused first pass (k_rs_hist_sc's entries, in.sc != null), with
+// its window width C as in k_rs_hist_sc
+template <int BITS, class SF = void, bool PASS0 = false, int C = 0>
 __global__ __launch_bounds__(RS_THREADS) void k_rs_scatter(RsIn in, const uint32_t* tile_off, const uint32_t* chunk_off,
                                                            uint32_t* keys_out, uint32_t* vals_out) {
     constexpr int ROUNDS = rs_rounds<BITS>();
@@ -308,12 +317,11 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_scatter(RsIn in, const uint32
             uint32_t p, i;
             const uint4* src = rs_scalar(in.sc, g, p, i);
             const uint32_t koff = p * in.sc.B;
-            scalar_signed_digits<SF, R>(src, in.c, in.W, [&](int w, uint32_t d) {
-                if (d != DIGIT_NONE) {
-                    K[w] = koff + (d & 0x7fffffffu);
-                    V[w] = ((uint32_t)w * in.sc.n + i) | (d & 0x80000000u);
-                    validmask |= 1u << w;
-                }
+            scalar_signed_digits<SF, R, C>(src, in.c, in.W, [&](int w, uint32_t d) {
+                // (no branch: K and V of a zero digit are never read, validmask guards every use)
+                K[w] = koff + (d & 0x7fffffffu);
+                V[w] = ((uint32_t)w * in.sc.n + i) | (d & 0x80000000u);
+                validmask |= (uint32_t)(d != DIGIT_NONE) << w;
             });
         }
     } else {
@@ -327,6 +335,25 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_scatter(RsIn in, const uint32
             V[r] = 0;
             if (rs_decode<PASS0>(in, wbase + (size_t)r * 64 + lane, limit, A[r], Bv[r], K[r], V[r])) validmask |= 1u << r;
         }
+    }
+    // May this wave rank equal digits in any order?  An LSD pass must leave its output ordered by the
+    // key's low shift + BITS bits, which is why equal digits keep their input order (the order by the low
+    // shift bits, made by the passes before).  But if every entry of the wave's slice has the same low shift
+    // bits, two entries of the slice with equal digits agree in all shift + BITS low bits, and either
+    // order satisfies the invariant -- for a middle pass as for the last one, where such entries have the
+    // same key and k_acc's bucket sums do not depend on their order.  After a pass over the low byte a run
+    // of one low-byte value is far longer than a slice at the sizes that matter (E / 256 entries against
+    // 1024), so nearly every wave qualifies; a wave that does not (a slice across a boundary between two
+    // runs, a partial slice, the third pass of a wide key) ranks stably as before.  Waves of one tile may
+    // decide differently: each owns a range of its own per digit.  The decision is wave-uniform (one ballot).
+    bool any_order = PASS0 || !std::is_void<SF>::value;
+    if constexpr (!PASS0 && std::is_void<SF>::value) {
+        const uint32_t first = __builtin_amdgcn_readfirstlane(K[0]);
+        uint32_t diff = 0;
+#pragma unroll
+        for (int r = 0; r < R; r++) diff |= K[r] ^ first;
+        diff &= (1u << in.shift) - 1u;
+        any_order = __ballot(diff != 0 || validmask != (1u << R) - 1u) == 0;
     }
     if (tid < BINS) {
         goff[tid] = tile_off[(size_t)blockIdx.x * BINS + tid] + chunk_off[(size_t)(blockIdx.x / RS_CH) * BINS + tid];
@@ -382,8 +409,9 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_scatter(RsIn in, const uint32
     // The first pass needs no stability (the second, by the high byte, must keep the first's order,
     // but the order of equal full keys is free: k_acc's bucket sums do not depend on it), so it ranks
     // with the wave-private run counter's returning LDS add -- one ds_add_rtn per entry instead of the
-    // eight-ballot match below (~40 VALU per round).
-    if constexpr (PASS0 || !std::is_void<SF>::value) {
+    // eight-ballot match below (~40 VALU per round).  So does every wave of a later pass whose slice is
+    // uniform in the bits already sorted (any_order, above).
+    if (any_order) {
 #pragma unroll
         for (int r = 0; r < R; r++) {
             if (!((validmask >> r) & 1u)) continue;
@@ -542,6 +570,17 @@ static std::vector<std::pair<uint32_t, uint32_t>> rs_plan(uint32_t key_bits, boo
     return P;
 }
 
+// the two launches of a fused first pass for the window width C (0: run-time in.c)
+template <class SF, int C>
+static void rs_launch_fused(const RsIn& in, uint32_t nt, uint32_t* hist, uint32_t* offs, SortScratch& S, int cur,
+                            hipStream_t s) {
+    hipLaunchKernelGGL((k_rs_hist_sc<SF, C>), dim3(nt), dim3(RS_THREADS), 0, s, in.sc, in.c, in.W, nt, hist, offs,
+                       S.ctr.as<uint32_t>(), S.count.as<uint32_t>());
+    hipLaunchKernelGGL((k_rs_scatter<8, SF, false, C>), dim3(nt), dim3(RS_THREADS), RS_STAGE_BYTES, s, in,
+                       (const uint32_t*)hist, (const uint32_t*)offs, S.keys[cur].as<uint32_t>(),
+                       S.vals[cur].as<uint32_t>());
+}
+
 int msm_radix_sort(const uint32_t* digits, size_t E, size_t npw, uint32_t B, uint32_t key_bits, SortScratch& S,
                    uint32_t** keys_out, uint32_t** vals_out, const uint32_t** count_out, uint32_t* bstart, size_t NB,
                    hipStream_t s, const RsFused* fused) {
@@ -554,8 +593,10 @@ int msm_radix_sort(const uint32_t* digits, size_t E, size_t npw, uint32_t B, uin
     for (auto& q : plan) ntmax = std::max(ntmax, tiles_of(q.second));
     // fused first pass: tiles of RS_THREADS scalars x W windows
     const size_t nsc = fused ? fused->n * (size_t)fused->P : 0;
+    // (W <= ceil(255 / c): the scalars are folded below 2^254, no window lies beyond that)
     if (fused && (fused->P < 1 || fused->P > 8 || fused->W > rs_rounds<8>() || nsc >= (1ull << 31) / 16 ||
-                  (fused->P > 1 && (B & 255))))
+                  (fused->P > 1 && (B & 255)) || fused->c < 1 || fused->c > 31 ||
+                  fused->W > (255 + fused->c - 1) / fused->c))
         return set_error(HALO_EINVAL, "fused sort pass: %d outputs of %u buckets, %d windows, %zu scalars", fused->P, B,
                          fused->W, nsc);
     const uint32_t ntiles0 = fused ? (uint32_t)std::max<size_t>(1, (nsc + RS_THREADS - 1) / RS_THREADS) : 0u;
@@ -598,12 +639,15 @@ int msm_radix_sort(const uint32_t* digits, size_t E, size_t npw, uint32_t B, uin
             in.sc.B = B;
             in.c = fused->c;
             in.W = fused->W;
+            // the widths of the resident SRS copies (msm_shifted_window_bits: 17 from 2^20 points up, 16 just
+            // below) have a recoding of their own; every other c takes the run-time one
             DISPATCH_FIELD(fused->field, SF, {
-                hipLaunchKernelGGL(k_rs_hist_sc<SF>, dim3(nt), dim3(RS_THREADS), 0, s, in.sc, in.c, in.W, nt,
-                                   hist, offs, S.ctr.as<uint32_t>(), S.count.as<uint32_t>());
-                hipLaunchKernelGGL((k_rs_scatter<8, SF>), dim3(nt), dim3(RS_THREADS), RS_STAGE_BYTES, s, in,
-                                   (const uint32_t*)hist, (const uint32_t*)offs, S.keys[cur].as<uint32_t>(),
-                                   S.vals[cur].as<uint32_t>());
+                if (in.c == 17 && in.W == digits_windows<17>())
+                    rs_launch_fused<SF, 17>(in, nt, hist, offs, S, cur, s);
+                else if (in.c == 16 && in.W == digits_windows<16>())
+                    rs_launch_fused<SF, 16>(in, nt, hist, offs, S, cur, s);
+                else
+                    rs_launch_fused<SF, 0>(in, nt, hist, offs, S, cur, s);
             });
         } else {
             // pass 0 also stores the number of valid (nonzero-digit) entries

@@ -12,7 +12,10 @@ struct SortScratch {
 int device_exclusive_scan(const uint32_t* in, size_t n, uint32_t* out, DevBuf& tmp, hipStream_t s);
 
 // Sorts the MSM digit entries (digits[e], DIGIT_NONE entries dropped) by key =
-// (e / npw) * B + (|d| - 1), stable; values = (e mod npw) | sign.  key_bits = bits of the largest
+// (e / npw) * B + (|d| - 1); values = (e mod npw) | sign.  The entries come out grouped by key, keys
+// ascending; the order of the entries of one key is unspecified (the sort is not stable: its first
+// pass, and later passes wherever the earlier ones left nothing to keep, rank equal digits in arrival
+// order).  key_bits = bits of the largest
 // key.  Fills bstart[0..NB] when bstart is not null (bucket b's entries are [bstart[b], bstart[b+1])
 // of the sorted arrays).
 // Fused first pass (window-shifted MSM, one bucket set, W <= 16): the entries come from the scalars

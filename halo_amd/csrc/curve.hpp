@@ -226,6 +226,49 @@ HALO_DEV XYZZ<F> xyzz_madd_run(const XYZZ<F>& p, bool& fresh, const Affine<F>& q
     return r;
 }
 
+// xyzz_madd_run for an accumulator known to be affine (ZZ = ZZZ = 1, X < 2p: a lane's first entry as
+// the fresh branch above copied it), i.e. k_acc's second addition of a chunk: U2 = x2, S2 = +-y2,
+// ZZ3 = PP and ZZZ3 = PPP need no multiplication by one (2M + 1 fe_mul2 + 2S instead of 6M + 1 + 2S).
+// Same values mod p as xyzz_madd_run.  Bounds: P = x2 - X1 + 2p < 4p (X1 < 2p), R = +-y2 - Y1 + 4p < 6p
+// (y2 + Y1 < 4p), X3 < 8p, T = Q - X3 + 8p < 10p, every one normalized by its subtraction's carry
+// chain; P^2 < 16p^2, R^2 < 36p^2 and R T + PPP (2p - Y1) < 64p^2 stay below p 2^261.  P < 4p is a
+// multiple of p only if its low limb is < 4 (p = 1 mod 2^29); then PP = 0 decides.
+template <class F>
+HALO_DEV XYZZ<F> xyzz_madd_run_aff(const XYZZ<F>& p, bool& fresh, const Affine<F>& q, uint32_t negmask, bool check_q) {
+    if (check_q && aff_is_id(q)) return p;
+    if (fresh) {
+        fresh = false;
+        XYZZ<F> r;
+        r.X = q.x;
+        r.Y = negmask ? fe_neg(q.y) : q.y;
+        r.ZZ = fe_one<F>();
+        r.ZZZ = fe_one<F>();
+        return r;
+    }
+    const Fe<F> P = fe_sub_k<2>(q.x, p.X);               // < 4p
+    const Fe<F> R = fe_sub_k_sgn<4>(q.y, p.Y, negmask);  // < 6p
+    const Fe<F> PP = fe_sqr(P);
+    const Fe<F> R2 = fe_sqr(R);
+    const Fe<F> PPP = fe_mul(P, PP);
+    const Fe<F> Q = fe_mul(p.X, PP);
+    XYZZ<F> r;
+    r.X = fe_sub_k<6>(R2, fe_add_nc(PPP, fe_add_nc(Q, Q)));  // < 8p
+    const Fe<F> T = fe_sub_k<8>(Q, r.X);                       // < 10p
+    r.Y = fe_mul2(R, T, PPP, fe_sub_k<2>(fe_zero<F>(), p.Y));
+    r.ZZ = PP;
+    r.ZZZ = PPP;
+    if (P.v[0] < 4u && fe_is_zero(PP)) {  // x2 == X1: q = +-p, off the common path
+        if (fe_is_zero(fe_reduce_8p(R))) {
+            Affine<F> qs = q;
+            if (negmask) qs.y = fe_neg(q.y);
+            return xyzz_mdbl(qs);
+        }
+        fresh = true;
+        return xyzz_id<F>();
+    }
+    return r;
+}
+
 // X of an xyzz_madd_acc accumulator back below 2p (storage needs < 2^256; the general formulas < 2p)
 template <class F>
 HALO_DEV XYZZ<F> xyzz_settle(const XYZZ<F>& p) {
@@ -258,6 +301,45 @@ HALO_DEV XYZZ<F> xyzz_add(const XYZZ<F>& p, const XYZZ<F>& q) {
     r.Y = fe_sub(fe_mul(R, fe_sub_k<2>(Q, r.X)), fe_mul(S1, PPP));
     r.ZZ = ZZ3;
     r.ZZZ = fe_mul(fe_mul(p.ZZZ, q.ZZZ), PPP);
+    return r;
+}
+
+// Accumulation form of xyzz_add for a lane that sums a run of points (the tail's serial chains), same
+// values mod p with what xyzz_madd_acc saves over xyzz_madd:
+//   * X is carried lazily: both operands may hold X in [0, 8p) (normalized limbs) and so does the sum;
+//     callers reduce with xyzz_settle before storing or handing the point to a formula that needs X < 2p;
+//   * Y3 = R (Q - X3) + PPP (2p - S1) is one product sum with a single Montgomery reduction;
+//   * the exceptional case q = +-p (P = U2 - U1 = 0 mod p) is screened by P's low limb: P = U2 - U1 + 2p
+//     with U1, U2 < 2p lies in (0, 4p) with normalized limbs, and a multiple k p, k < 4, has the low limb
+//     k (p = 1 mod 2^29), so the full ZZ3 test runs only when that limb is < 4.
+// Bounds: U1 = X1 ZZ2 and U2 = X2 ZZ1 have one operand < 8p (product < 16p^2), so U1, U2, S1, S2 < 2p;
+// P, R < 4p; X3 = R^2 - PPP - 2Q + 6p < 8p; T = Q - X3 + 8p < 10p; R T + PPP (2p - S1) < 40p^2 + 4p^2
+// stays below p 2^261 (~127p^2), and every fe_mul2 input is normalized by its subtraction's carry chain.
+template <class F>
+HALO_DEV XYZZ<F> xyzz_add_acc(const XYZZ<F>& p, const XYZZ<F>& q) {
+    if (xyzz_is_id(q)) return p;
+    if (xyzz_is_id(p)) return q;
+    const Fe<F> U1 = fe_mul(p.X, q.ZZ);
+    const Fe<F> U2 = fe_mul(q.X, p.ZZ);
+    const Fe<F> S1 = fe_mul(p.Y, q.ZZZ);
+    const Fe<F> S2 = fe_mul(q.Y, p.ZZZ);
+    const Fe<F> P = fe_sub_k<2>(U2, U1);  // < 4p
+    const Fe<F> R = fe_sub_k<2>(S2, S1);  // < 4p
+    const Fe<F> PP = fe_sqr(P);
+    const Fe<F> R2 = fe_sqr(R);
+    const Fe<F> ZZ3 = fe_mul(fe_mul(p.ZZ, q.ZZ), PP);
+    const Fe<F> PPP = fe_mul(P, PP);
+    const Fe<F> Q = fe_mul(U1, PP);
+    XYZZ<F> r;
+    r.X = fe_sub_k<6>(R2, fe_add_nc(PPP, fe_add_nc(Q, Q)));  // < 8p
+    const Fe<F> T = fe_sub_k<8>(Q, r.X);                       // < 10p
+    r.Y = fe_mul2(R, T, PPP, fe_sub_k<2>(fe_zero<F>(), S1));
+    r.ZZ = ZZ3;
+    r.ZZZ = fe_mul(fe_mul(p.ZZZ, q.ZZZ), PPP);
+    if (P.v[0] < 4u && fe_is_zero(ZZ3)) {  // U2 == U1: q = +-p (ZZ1, ZZ2 != 0), off the common path
+        if (fe_is_zero_4p(R)) return xyzz_dbl(xyzz_settle(p));
+        return xyzz_id<F>();
+    }
     return r;
 }
 

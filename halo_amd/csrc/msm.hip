@@ -164,8 +164,8 @@ __global__ void k_digits_glv(const uint4* scalars, size_t n, int c, int W, uint3
 // first segment's sum goes to first[t], its last segment's (when there are >= 2) to last[t], and the
 // buckets strictly inside the chunk are complete, so they go straight to bucket_sums.  k_merge then
 // completes the buckets that straddle chunk boundaries.
-// k_acc's register budget is sized for 4 workgroups per CU (the compiler's own allocation, 116 VGPRs;
-// 5 / 6 per CU measured slower).
+// k_acc's register budget is sized for 4 workgroups per CU (the compiler's own allocation, 107 VGPRs
+// with the peeled second entry; 5 / 6 per CU measured slower).
 constexpr int ACC_MIN_BLOCKS = 4;
 // npw_lg: log2 n_per_window when it is a power of two (the window of a shifted entry is a shift,
 // not a division), else 0xff.
@@ -197,9 +197,13 @@ __device__ __forceinline__ void acc_chunk(size_t t, uint32_t cnt, const uint32_t
     bool first_done = false;
     XYZZ<F> acc = xyzz_id<F>();
     bool fresh = true;  // acc is the identity (xyzz_madd_run)
-    for (uint32_t e = (uint32_t)beg; e < end; e++) {
-        const uint32_t k = keys[e];
-        if (k != cur) {  // bucket boundary inside the chunk
+    // one entry: the bucket boundary before it, its base point, the addition.  pos: 0 = the chunk's first
+    // entry (key cur, acc the identity: a copy), 1 = its second (acc the identity or the affine copy of the
+    // first), 2 = any later one.
+    auto step = [&](uint32_t e, auto pos) {
+        constexpr int POS = decltype(pos)::value;
+        const uint32_t k = POS == 0 ? cur : keys[e];
+        if (POS != 0 && k != cur) {  // bucket boundary inside the chunk
             for (uint32_t b = cur + 1; b <= k; b++) bstart[b] = e;
             if (!first_done) {
                 partial_store(first + PARTIAL_U4 * t, acc);
@@ -224,8 +228,29 @@ __device__ __forceinline__ void acc_chunk(size_t t, uint32_t cnt, const uint32_t
         if (phi) idx -= glv_n;
         Affine<F> p = aff_load<F>(bases + 4 * idx);
         if (phi) p.x = fe_mul(p.x, fe_from_const<F>(Cv::K::BETA));
-        acc = xyzz_madd_run(acc, fresh, p, (v & 0x80000000u) ? ~0u : 0u, check_q);
-    }
+        const uint32_t negmask = (v & 0x80000000u) ? ~0u : 0u;
+        if constexpr (POS == 0) {  // acc is the identity: the copy that xyzz_madd_run's fresh branch makes
+            if (!(check_q && aff_is_id(p))) {
+                fresh = false;
+                acc.X = p.x;
+                acc.Y = negmask ? fe_neg(p.y) : p.y;
+                acc.ZZ = fe_one<F>();
+                acc.ZZZ = fe_one<F>();
+            }
+        } else if constexpr (POS == 1) {
+            acc = xyzz_madd_run_aff(acc, fresh, p, negmask, check_q);
+        } else {
+            acc = xyzz_madd_run(acc, fresh, p, negmask, check_q);
+        }
+    };
+    // The first two entries are peeled: every lane of the wave is at its second entry together, whose
+    // accumulator is the affine copy of the first (ZZ = ZZZ = 1), so that addition runs without the four
+    // multiplications by one.  A lane whose second entry opens a new bucket stores its one-point first
+    // segment and starts fresh in that step, as in the loop.
+    uint32_t e = (uint32_t)beg;
+    step(e++, std::integral_constant<int, 0>{});
+    if (e < end) step(e++, std::integral_constant<int, 1>{});
+    for (; e < end; e++) step(e, std::integral_constant<int, 2>{});
     partial_store((first_done ? last : first) + PARTIAL_U4 * t, acc);
     if (end == cnt)
         for (uint32_t b = cur + 1; b <= NB; b++) bstart[b] = cnt;

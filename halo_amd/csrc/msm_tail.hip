@@ -70,6 +70,8 @@ __global__ __launch_bounds__(256) void k_merge(const uint32_t* bstart, const uin
     XYZZ<F> acc = xyzz_id<F>();
     if (active) {
         // this lane's sources: chunks (t0, t1] split in LN contiguous parts [t, tb]
+        // (measured and left out: counting chunk t0's partial as lane 0's first source, so that 16 sources
+        // split 7 + 7 additions instead of 8 + 6 -- inside the noise of the step, DESIGN_HISTORY.md)
         const uint32_t total = t1 - t0, per = (total + LN - 1) / LN;
         uint32_t t = t0 + 1 + j * per;
         const uint32_t tb = min(t1, t0 + (j + 1) * per);
@@ -98,13 +100,14 @@ __global__ __launch_bounds__(256) void k_merge(const uint32_t* bstart, const uin
                 const XYZZ<F> cur = nxt;
                 const bool more = t <= tb;
                 if (more) nxt = partial_load<F>(next_src());
-                acc = xyzz_add(acc, cur);
+                acc = xyzz_add_acc(acc, cur);
                 if (!more) break;
             }
         }
     }
-    for (int m = 1; m < LN; m <<= 1) acc = xyzz_add(acc, xyzz_shfl_xor(acc, m));
-    if (active && j == 0) xyzz_store(bucket_sums + 8 * b, acc);
+    // (xyzz_add_acc: X stays lazy through the chain and the join, settled at the store)
+    for (int m = 1; m < LN; m <<= 1) acc = xyzz_add_acc(acc, xyzz_shfl_xor(acc, m));
+    if (active && j == 0) xyzz_store(bucket_sums + 8 * b, xyzz_settle(acc));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -149,14 +152,14 @@ __global__ __launch_bounds__(256) void k_rowcol(const uint4* bucket_sums, uint32
     if (blockIdx.x < sh.nrb) {  // (uniform per block) rows: groups of gr lanes
         const uint32_t h = blockIdx.x * sh.rpb + tid / sh.gr, l0 = tid % sh.gr;
         if (h < H)
-            for (uint32_t l = l0; l < L; l += sh.gr) v = xyzz_add(v, xyzz_load<F>(bs + 8 * ((size_t)h * L + l)));
-        v = block_group_sum<F>(v, sh.gr, red);
+            for (uint32_t l = l0; l < L; l += sh.gr) v = xyzz_add_acc(v, xyzz_load<F>(bs + 8 * ((size_t)h * L + l)));
+        v = block_group_sum<F>(xyzz_settle(v), sh.gr, red);
         if (l0 == 0 && h < H) xyzz_store(rows + 8 * ((size_t)w * H + h), v);
     } else {  // columns: groups of gc lanes
         const uint32_t l = (blockIdx.x - sh.nrb) * sh.cpb + tid / sh.gc, h0 = tid % sh.gc;
         if (l < L)
-            for (uint32_t h = h0; h < H; h += sh.gc) v = xyzz_add(v, xyzz_load<F>(bs + 8 * ((size_t)h * L + l)));
-        v = block_group_sum<F>(v, sh.gc, red);
+            for (uint32_t h = h0; h < H; h += sh.gc) v = xyzz_add_acc(v, xyzz_load<F>(bs + 8 * ((size_t)h * L + l)));
+        v = block_group_sum<F>(xyzz_settle(v), sh.gc, red);
         if (h0 == 0 && l < L) xyzz_store(cols + 8 * ((size_t)w * L + l), v);
     }
 }
@@ -179,9 +182,9 @@ __global__ __launch_bounds__(256) void k_bitterms(const uint4* rows, const uint4
     XYZZ<F> acc = xyzz_id<F>();
     for (uint32_t j = tid; j < cnt; j += 256) {
         if (k != 0 && !((j >> bit) & 1u)) continue;
-        acc = xyzz_add(acc, xyzz_load<F>(src + 8 * j));
+        acc = xyzz_add_acc(acc, xyzz_load<F>(src + 8 * j));
     }
-    acc = block_group_sum<F>(acc, 256, red);
+    acc = block_group_sum<F>(xyzz_settle(acc), 256, red);
     if (tid == 0) xyzz_store(out + 8 * ((size_t)w * NT + k), acc);
 }
 
@@ -280,9 +283,11 @@ __global__ __launch_bounds__(256) void k_batch_window_sums(const uint4* bucket_s
         const uint4* bs = bucket_sums + 8 * (w * B + (size_t)k * G);
         XYZZ<F> R = xyzz_id<F>(), S = xyzz_id<F>();
         for (int j = (int)G - 1; j >= 0; j--) {
-            R = xyzz_add(R, xyzz_load<F>(bs + 8 * j));
-            S = xyzz_add(S, R);
+            R = xyzz_add_acc(R, xyzz_load<F>(bs + 8 * j));
+            S = xyzz_add_acc(S, R);
         }
+        R = xyzz_settle(R);
+        S = xyzz_settle(S);
         if (k) {
             XYZZ<F> X = R;
             for (uint32_t g = G; g > 1; g >>= 1) X = xyzz_dbl(X);  // G R

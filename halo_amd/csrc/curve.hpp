@@ -185,37 +185,64 @@ HALO_DEV XYZZ<F> xyzz_madd_acc(const XYZZ<F>& p, const Affine<F>& q, uint32_t ne
 // tracks whether the accumulator is the identity (`fresh`) instead of testing ZZ, the base point's
 // identity test runs only when the bases may hold one (check_q), and the exceptional case q = +-acc
 // (P = U2 - X1 = 0 mod p) is screened by P's low limb: P < 10p with normalized limbs is a multiple of
-// p only if that limb is < 10 (p = 1 mod 2^29), so the full ZZ3 test runs (almost) never.  Same
-// formula and results as xyzz_madd_acc.
+// p only if that limb is < 10 (p = 1 mod 2^29), so the full ZZ3 test runs (almost) never.
+//
+// Three carry chains per addition instead of xyzz_madd_acc's five.  The running sum is the point
+// (X, s Yt, ZZ, ZZZ) with the sign s apart (sneg: 0 for +1, ~0u for -1; (X, -Y, ZZ, ZZZ) is the negative
+// of (X, Y, ZZ, ZZZ)) and X signed-lazy (fields.hpp: int32 limbs below 2^30 in magnitude, value in
+// (-4p, 4p)); Yt, ZZ, ZZZ < 2p.  Adding (x2, sigma y2), m = sigma s:
+//   U2 = x2 ZZ, S2 = y2 ZZZ
+//   P  = U2 - X + 4p                  chain 1, in (0, 10p): X is only ever this subtrahend
+//   Rn = m S2 - Yt + 4p               chain 2, in (0, 6p); Rn = s R
+//   PP = P^2, R2 = Rn^2 = R^2, PPP = P PP, V = U2 PP, and Q = X PP = V - PPP limb-wise
+//   X3 = R2 - Q - V                   limb-wise: no chain, no multiple of p, never multiplied
+//   Tn = X3 - Q + 6p                  chain 3, in (0, 12p); Tn = -(Q - X3) = R2 + 2 PPP - 3 V + 6p
+//   Y3 = R (Q - X3) - s Yt PPP = -s (Rn Tn + Yt PPP): Yt3 = Rn Tn + Yt PPP (one fe_mul2), s3 = -s
+// so neither 2p - Y1 nor a normalized X3 is formed.  Inside the chains a limb's sum stays in int32, just:
+// U2_i - X_i + 4p_i + c <= (2^29 - 1) + (2^30 - 2) + (2^29 - 1) + 3 and X3_i - Q_i + 6p_i + c <=
+// 3 (2^29 - 1) + (2^29 - 1) + 3, both 2^31 - 1 at most (so c <= 3), and >= -2^30 - 2^29 - 3 below.
+// Rn Tn + Yt PPP < 72p^2 + 4p^2 < p 2^261 with all four operands normalized, P^2 < 100p^2.
+// xyzz_run_out settles X and applies s for a store.  tests/test_acc_three_chains.py models the step limb
+// by limb on adversarial operands.
 template <class F>
-HALO_DEV XYZZ<F> xyzz_madd_run(const XYZZ<F>& p, bool& fresh, const Affine<F>& q, uint32_t negmask, bool check_q) {
+HALO_DEV XYZZ<F> xyzz_madd_run(const XYZZ<F>& p, uint32_t& sneg, bool& fresh, const Affine<F>& q, uint32_t negmask,
+                               bool check_q) {
     if (check_q && aff_is_id(q)) return p;
     if (fresh) {
         fresh = false;
+        sneg = negmask;
+        // An empty statement that keeps this copy a block of its own.  Without it the branch holds nothing
+        // but register copies, the compiler folds them into the merge after the addition, and every
+        // addition pays ~50 v_mov for a copy that a quarter of k_acc's steps need (measured: 26 597
+        // instead of 26 105 VALU per wave).
+        asm volatile("" : "+v"(sneg));
         XYZZ<F> r;
         r.X = q.x;
-        r.Y = negmask ? fe_neg(q.y) : q.y;
+        r.Y = q.y;
         r.ZZ = fe_one<F>();
         r.ZZZ = fe_one<F>();
         return r;
     }
     const Fe<F> U2 = fe_mul(q.x, p.ZZ);
     const Fe<F> S2 = fe_mul(q.y, p.ZZZ);
-    const Fe<F> P = fe_sub_k<8>(U2, p.X);              // < 10p
-    const Fe<F> R = fe_sub_k_sgn<4>(S2, p.Y, negmask);  // < 6p
+    const Fe<F> P = fe_sub_k<4>(U2, p.X);                      // (0, 10p)
+    const Fe<F> R = fe_sub_k_sgn<4>(S2, p.Y, negmask ^ sneg);  // Rn, (0, 6p)
     const Fe<F> PP = fe_sqr(P);
     const Fe<F> R2 = fe_sqr(R);
     const Fe<F> ZZ3 = fe_mul(p.ZZ, PP);
     const Fe<F> PPP = fe_mul(P, PP);
-    const Fe<F> Q = fe_mul(p.X, PP);
+    const Fe<F> V = fe_mul(U2, PP);
+    const Fe<F> Q = fe_sub_nc(V, PPP);  // |limb| < 2^29
     XYZZ<F> r;
-    r.X = fe_sub_k<6>(R2, fe_add_nc(PPP, fe_add_nc(Q, Q)));  // < 8p
-    const Fe<F> T = fe_sub_k<8>(Q, r.X);                       // < 10p
-    r.Y = fe_mul2(R, T, PPP, fe_sub_k<2>(fe_zero<F>(), p.Y));
+    r.X = fe_sub_nc(fe_sub_nc(R2, Q), V);    // R2 + PPP - 2V: |limb| < 2^30
+    const Fe<F> T = fe_sub_k<6>(r.X, Q);     // Tn, (0, 12p)
+    r.Y = fe_mul2(R, T, p.Y, PPP);
     r.ZZ = ZZ3;
     r.ZZZ = fe_mul(p.ZZZ, PPP);
     if (P.v[0] < 10u && fe_is_zero(ZZ3)) {  // U2 == X1: q = +-p, off the common path
-        if (fe_is_zero(fe_reduce_8p(R))) {
+        const bool dbl = fe_is_zero(fe_reduce_8p(R));
+        sneg = 0;
+        if (dbl) {
             Affine<F> qs = q;
             if (negmask) qs.y = fe_neg(q.y);
             return xyzz_mdbl(qs);
@@ -223,48 +250,74 @@ HALO_DEV XYZZ<F> xyzz_madd_run(const XYZZ<F>& p, bool& fresh, const Affine<F>& q
         fresh = true;
         return xyzz_id<F>();
     }
+    sneg = ~sneg;
     return r;
 }
 
 // xyzz_madd_run for an accumulator known to be affine (ZZ = ZZZ = 1, X < 2p: a lane's first entry as
 // the fresh branch above copied it), i.e. k_acc's second addition of a chunk: U2 = x2, S2 = +-y2,
 // ZZ3 = PP and ZZZ3 = PPP need no multiplication by one (2M + 1 fe_mul2 + 2S instead of 6M + 1 + 2S).
-// Same values mod p as xyzz_madd_run.  Bounds: P = x2 - X1 + 2p < 4p (X1 < 2p), R = +-y2 - Y1 + 4p < 6p
-// (y2 + Y1 < 4p), X3 < 8p, T = Q - X3 + 8p < 10p, every one normalized by its subtraction's carry
-// chain; P^2 < 16p^2, R^2 < 36p^2 and R T + PPP (2p - Y1) < 64p^2 stay below p 2^261.  P < 4p is a
-// multiple of p only if its low limb is < 4 (p = 1 mod 2^29); then PP = 0 decides.
+// The same step as xyzz_madd_run with V = x2 PP.  Bounds: P = x2 - X1 + 2p in (0, 4p) (X1 < 2p, normalized),
+// Rn = m y2 - Yt + 4p in (0, 6p), X3 and Tn as there; P^2 < 16p^2, Rn^2 < 36p^2 and Rn Tn + Yt PPP < 76p^2
+// stay below p 2^261.  P < 4p is a multiple of p only if its low limb is < 4 (p = 1 mod 2^29); then
+// PP = 0 decides.
 template <class F>
-HALO_DEV XYZZ<F> xyzz_madd_run_aff(const XYZZ<F>& p, bool& fresh, const Affine<F>& q, uint32_t negmask, bool check_q) {
+HALO_DEV XYZZ<F> xyzz_madd_run_aff(const XYZZ<F>& p, uint32_t& sneg, bool& fresh, const Affine<F>& q, uint32_t negmask,
+                                   bool check_q) {
     if (check_q && aff_is_id(q)) return p;
     if (fresh) {
         fresh = false;
+        sneg = negmask;
+        asm volatile("" : "+v"(sneg));  // keeps the copy a block of its own, as in xyzz_madd_run
         XYZZ<F> r;
         r.X = q.x;
-        r.Y = negmask ? fe_neg(q.y) : q.y;
+        r.Y = q.y;
         r.ZZ = fe_one<F>();
         r.ZZZ = fe_one<F>();
         return r;
     }
-    const Fe<F> P = fe_sub_k<2>(q.x, p.X);               // < 4p
-    const Fe<F> R = fe_sub_k_sgn<4>(q.y, p.Y, negmask);  // < 6p
+    const Fe<F> P = fe_sub_k<2>(q.x, p.X);                      // (0, 4p)
+    const Fe<F> R = fe_sub_k_sgn<4>(q.y, p.Y, negmask ^ sneg);  // Rn, (0, 6p)
     const Fe<F> PP = fe_sqr(P);
     const Fe<F> R2 = fe_sqr(R);
     const Fe<F> PPP = fe_mul(P, PP);
-    const Fe<F> Q = fe_mul(p.X, PP);
+    const Fe<F> V = fe_mul(q.x, PP);
+    const Fe<F> Q = fe_sub_nc(V, PPP);  // |limb| < 2^29
     XYZZ<F> r;
-    r.X = fe_sub_k<6>(R2, fe_add_nc(PPP, fe_add_nc(Q, Q)));  // < 8p
-    const Fe<F> T = fe_sub_k<8>(Q, r.X);                       // < 10p
-    r.Y = fe_mul2(R, T, PPP, fe_sub_k<2>(fe_zero<F>(), p.Y));
+    r.X = fe_sub_nc(fe_sub_nc(R2, Q), V);  // R2 + PPP - 2V: |limb| < 2^30
+    const Fe<F> T = fe_sub_k<6>(r.X, Q);   // Tn, (0, 12p)
+    r.Y = fe_mul2(R, T, p.Y, PPP);
     r.ZZ = PP;
     r.ZZZ = PPP;
     if (P.v[0] < 4u && fe_is_zero(PP)) {  // x2 == X1: q = +-p, off the common path
-        if (fe_is_zero(fe_reduce_8p(R))) {
+        const bool dbl = fe_is_zero(fe_reduce_8p(R));
+        sneg = 0;
+        if (dbl) {
             Affine<F> qs = q;
             if (negmask) qs.y = fe_neg(q.y);
             return xyzz_mdbl(qs);
         }
         fresh = true;
         return xyzz_id<F>();
+    }
+    sneg = ~sneg;
+    return r;
+}
+
+// A running sum of xyzz_madd_run as a plain XYZZ for a store: X + 4p through one carry chain (normalized,
+// in (0, 8p): what partial_load and xyzz_settle take) and Y = Yt, or 2p - Yt in (0, 2p] when s = -1, by one
+// chain with the sign folded in (as fe_sub_k_sgn; 2p itself only from Yt = 0, which no product gives
+// -- Rn, Tn > 0 -- and no curve point has; it is normalized, below 2^256 and 0 mod p all the same).
+template <class F>
+HALO_DEV XYZZ<F> xyzz_run_out(const XYZZ<F>& p, uint32_t sneg) {
+    XYZZ<F> r = p;
+    r.X = fe_sub_k<4>(p.X, fe_zero<F>());
+    int32_t c = 0;
+#pragma unroll
+    for (int i = 0; i < NLIMB; i++) {
+        const int32_t x = (int32_t)((p.Y.v[i] ^ sneg) - sneg) + (int32_t)(F::P2[i] & sneg) + c;
+        r.Y.v[i] = (i == NLIMB - 1) ? (uint32_t)x : ((uint32_t)x & LIMB_MASK);
+        c = x >> LIMB_BITS;
     }
     return r;
 }

@@ -164,8 +164,8 @@ __global__ void k_digits_glv(const uint4* scalars, size_t n, int c, int W, uint3
 // first segment's sum goes to first[t], its last segment's (when there are >= 2) to last[t], and the
 // buckets strictly inside the chunk are complete, so they go straight to bucket_sums.  k_merge then
 // completes the buckets that straddle chunk boundaries.
-// k_acc's register budget is sized for 4 workgroups per CU (the compiler's own allocation, 107 VGPRs
-// with the peeled second entry; 5 / 6 per CU measured slower).
+// k_acc's register budget is sized for 4 workgroups per CU (the compiler's own allocation, 117 VGPRs
+// with the peeled second entry and the three-chain addition; 5 / 6 per CU measured slower).
 constexpr int ACC_MIN_BLOCKS = 4;
 // npw_lg: log2 n_per_window when it is a power of two (the window of a shifted entry is a shift,
 // not a division), else 0xff.
@@ -197,6 +197,7 @@ __device__ __forceinline__ void acc_chunk(size_t t, uint32_t cnt, const uint32_t
     bool first_done = false;
     XYZZ<F> acc = xyzz_id<F>();
     bool fresh = true;  // acc is the identity (xyzz_madd_run)
+    uint32_t sneg = 0;  // the sign xyzz_madd_run carries beside acc: the sum is (X, -Y, ZZ, ZZZ) when ~0u
     // one entry: the bucket boundary before it, its base point, the addition.  pos: 0 = the chunk's first
     // entry (key cur, acc the identity: a copy), 1 = its second (acc the identity or the affine copy of the
     // first), 2 = any later one.
@@ -206,13 +207,14 @@ __device__ __forceinline__ void acc_chunk(size_t t, uint32_t cnt, const uint32_t
         if (POS != 0 && k != cur) {  // bucket boundary inside the chunk
             for (uint32_t b = cur + 1; b <= k; b++) bstart[b] = e;
             if (!first_done) {
-                partial_store(first + PARTIAL_U4 * t, acc);
+                partial_store(first + PARTIAL_U4 * t, xyzz_run_out(acc, sneg));
                 first_done = true;
             } else {
-                xyzz_store(bucket_sums + 8 * (size_t)cur, xyzz_settle(acc));
+                xyzz_store(bucket_sums + 8 * (size_t)cur, xyzz_settle(xyzz_run_out(acc, sneg)));
             }
             acc = xyzz_id<F>();
             fresh = true;
+            sneg = 0;
             cur = k;
         }
         const uint32_t v = vals[e];
@@ -232,15 +234,16 @@ __device__ __forceinline__ void acc_chunk(size_t t, uint32_t cnt, const uint32_t
         if constexpr (POS == 0) {  // acc is the identity: the copy that xyzz_madd_run's fresh branch makes
             if (!(check_q && aff_is_id(p))) {
                 fresh = false;
+                sneg = negmask;
                 acc.X = p.x;
-                acc.Y = negmask ? fe_neg(p.y) : p.y;
+                acc.Y = p.y;
                 acc.ZZ = fe_one<F>();
                 acc.ZZZ = fe_one<F>();
             }
         } else if constexpr (POS == 1) {
-            acc = xyzz_madd_run_aff(acc, fresh, p, negmask, check_q);
+            acc = xyzz_madd_run_aff(acc, sneg, fresh, p, negmask, check_q);
         } else {
-            acc = xyzz_madd_run(acc, fresh, p, negmask, check_q);
+            acc = xyzz_madd_run(acc, sneg, fresh, p, negmask, check_q);
         }
     };
     // The first two entries are peeled: every lane of the wave is at its second entry together, whose
@@ -251,7 +254,7 @@ __device__ __forceinline__ void acc_chunk(size_t t, uint32_t cnt, const uint32_t
     step(e++, std::integral_constant<int, 0>{});
     if (e < end) step(e++, std::integral_constant<int, 1>{});
     for (; e < end; e++) step(e, std::integral_constant<int, 2>{});
-    partial_store((first_done ? last : first) + PARTIAL_U4 * t, acc);
+    partial_store((first_done ? last : first) + PARTIAL_U4 * t, xyzz_run_out(acc, sneg));
     if (end == cnt)
         for (uint32_t b = cur + 1; b <= NB; b++) bstart[b] = cnt;
 }

@@ -2,9 +2,11 @@
 // field library).
 #include "curve.hpp"
 #include "dispatch.hpp"
+#include "field_ops.hpp"
 #include "glv.hpp"
-#include "runtime.hpp"
 #include "msm.hpp"
+#include "points.hpp"
+#include "runtime.hpp"
 #include "tree.hpp"
 
 namespace halo {

@@ -23,8 +23,11 @@
 #include <thread>
 
 #include "dispatch.hpp"
+#include "field_ops.hpp"
 #include "glv.hpp"
 #include "msm.hpp"
+#include "ntt.hpp"
+#include "points.hpp"
 #include "runtime.hpp"
 #include "tree.hpp"
 
@@ -289,14 +292,6 @@ __global__ __launch_bounds__(64) void k_pow2_xyzz_from_wrapped(const uint4* P_wr
     }
 }
 
-// XYZZ -> internal affine, one inversion per lane (all lanes in parallel)
-template <class Cv>
-__global__ __launch_bounds__(64) void k_xyzz_to_aff_ipa(const uint4* in, uint4* out, int count) {
-    using F = typename Cv::Base;
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < count) aff_store(out + 4 * i, xyzz_to_aff(xyzz_load<F>(in + 8 * i)));
-}
-
 template <class Cv>
 __global__ void k_copy_first_wrapped(const uint4* gs_int, const uint4* cs, uint4* out_U, uint4* out_c) {
     using F = typename Cv::Base;
@@ -309,8 +304,6 @@ __global__ void k_copy_first_wrapped(const uint4* gs_int, const uint4* cs, uint4
 // ---------------------------------------------------------------------------------------------
 // host helpers
 // ---------------------------------------------------------------------------------------------
-static unsigned gridn(size_t n, unsigned t) { return (unsigned)std::max<size_t>(1, (n + t - 1) / t); }
-
 // dot product of two device ark vectors -> device ark scalar (out_ark), using tmp (>= 2048*32 B)
 static int dot_device(int field, const void* x, const void* y, size_t n, void* out_ark, void* tmp, hipStream_t s) {
     const size_t per_block = std::max<size_t>(RED_THREADS * 8, (n + 1023) / 1024);
@@ -1326,7 +1319,7 @@ extern "C" int halo_construct_powers(halo_field_t field, const halo_fe_t* z, siz
     HALO_CHECK(copy_h2d(b, z, 32, s));
     const size_t run = 16;
     DISPATCH_FIELD(field, F, {
-        hipLaunchKernelGGL(k_powers<F>, dim3(gridn((n + run - 1) / run, 128)), dim3(128), 0, s, (const uint4*)b, n, run,
+        hipLaunchKernelGGL(k_powers<F>, dim3(grid_for((n + run - 1) / run, 128)), dim3(128), 0, s, (const uint4*)b, n, run,
                            (uint4*)(b + 32));
     });
     HALO_HIP(hipGetLastError());
@@ -1455,7 +1448,7 @@ extern "C" int halo_poly_mul(halo_field_t field, const halo_fe_t* a, size_t la, 
     HALO_CHECK(ntt_device_dispatch(st, field, A, FA, T, logn, 1, 0, s));
     HALO_CHECK(ntt_device_dispatch(st, field, Bv, FB, T, logn, 1, 0, s));
     DISPATCH_FIELD(field, F, {
-        hipLaunchKernelGGL(k_pointwise_mul<F>, dim3(gridn(N, 256)), dim3(256), 0, s, (uint4*)FA, (const uint4*)FB, N);
+        hipLaunchKernelGGL(k_pointwise_mul<F>, dim3(grid_for(N, 256)), dim3(256), 0, s, (uint4*)FA, (const uint4*)FB, N);
     });
     HALO_HIP(hipGetLastError());
     HALO_CHECK(ntt_device_dispatch(st, field, FA, A, T, logn, 1, 1, s));
@@ -1521,10 +1514,9 @@ static int ipa_h_table(DeviceState* st, int curve, const halo_wrapped_point_t* H
     DISPATCH_CURVE(curve, Cv, {
         hipLaunchKernelGGL(k_pow2_xyzz_from_wrapped<Cv>, dim3(1), dim3(64), 0, s, (const uint4*)(tmp + IPA_HTAB * 128),
                            (uint4*)tmp, IPA_HTAB);
-        hipLaunchKernelGGL(k_xyzz_to_aff_ipa<Cv>, dim3(IPA_HTAB / 64), dim3(64), 0, s, (const uint4*)tmp,
-                           ht->t.as<uint4>(), IPA_HTAB);
     });
     HALO_HIP(hipGetLastError());
+    HALO_CHECK(xyzz_to_affine_device(curve, tmp, ht->t.ptr, IPA_HTAB, s));
     HALO_HIP(hipStreamSynchronize(s));  // sessions on other streams read it
     memcpy(ht->key, Hpt, 64);
     *out = ht->t.ptr;
@@ -1609,7 +1601,7 @@ static int ipa_setup(DeviceState* st, halo_ipa_session* ses, int curve, size_t n
         // products) plus `run`; small n is latency-bound (short runs), large n throughput-bound
         const size_t run = n <= 4096 ? 2 : 16;
         DISPATCH_CURVE(curve, Cv, {
-            hipLaunchKernelGGL(k_powers<typename Cv::Scalar>, dim3(gridn((n + run - 1) / run, 128)), dim3(128), 0, s,
+            hipLaunchKernelGGL(k_powers<typename Cv::Scalar>, dim3(grid_for((n + run - 1) / run, 128)), dim3(128), 0, s,
                                (const uint4*)sm, n, run, ses->zs.as<uint4>());
         });
         HALO_HIP(hipGetLastError());
@@ -1657,10 +1649,9 @@ static int ipa_start(DeviceState* st, halo_ipa_session* ses, const halo_wrapped_
     uint4* chain = ses->htab.as<uint4>() + 4 * IPA_HTAB;  // XYZZ scratch after the affine table
     DISPATCH_CURVE(ses->curve, Cv, {
         hipLaunchKernelGGL(k_pow2_xyzz_from_wrapped<Cv>, dim3(1), dim3(64), 0, hs, (const uint4*)(sm + 64), chain, IPA_HTAB);
-        hipLaunchKernelGGL(k_xyzz_to_aff_ipa<Cv>, dim3(IPA_HTAB / 64), dim3(64), 0, hs, (const uint4*)chain,
-                           ses->htab.as<uint4>(), IPA_HTAB);
     });
     HALO_HIP(hipGetLastError());
+    HALO_CHECK(xyzz_to_affine_device(ses->curve, chain, ses->htab.ptr, IPA_HTAB, hs));
     HALO_HIP(hipEventRecord(ses->htab_ready, hs));
     ses->htab_waited = false;
     return HALO_OK;
@@ -1919,7 +1910,7 @@ extern "C" int halo_pcdl_open_blind(halo_ipa_session* ses, const halo_fe_t* q, c
         ArkScalarPair wb;
         memcpy(&wb.v[0], w_bar, 32);
         DISPATCH_CURVE(ses->curve, Cv, {
-            hipLaunchKernelGGL(k_pbar_small<Cv>, dim3(gridn(n, 256)), dim3(256), 0, s, ses->tmp.as<const uint4>(), d,
+            hipLaunchKernelGGL(k_pbar_small<Cv>, dim3(grid_for(n, 256)), dim3(256), 0, s, ses->tmp.as<const uint4>(), d,
                                (const uint4*)sm, wb, (uint4*)(sm + SM_WBAR), ses->pbar.as<uint4>(), (uint32_t*)scr,
                                (uint8_t*)(scr + o_side));  // z at sm[0, 32)
         });
@@ -1987,7 +1978,7 @@ extern "C" int halo_pcdl_open_combine(halo_ipa_session* ses, const halo_fe_t* al
             memcpy(a.w, w, 32);
             memcpy(a.C, C, 64);
             DISPATCH_CURVE(ses->curve, Cv, {
-                hipLaunchKernelGGL(k_combine_small<Cv>, dim3(gridn(ses->n, 256)), dim3(256), 0, s, a, ses->cs.as<uint4>(),
+                hipLaunchKernelGGL(k_combine_small<Cv>, dim3(grid_for(ses->n, 256)), dim3(256), 0, s, a, ses->cs.as<uint4>(),
                                    ses->pbar.as<uint4>(), ses->n, (const uint4*)(sm + SM_WBAR), (uint4*)(sm + SM_WP),
                                    (uint4*)(sm + SM_NEGW), (uint4*)(sm + SM_C), (uint32_t*)scr, (uint8_t*)(scr + o_side));
             });
@@ -2068,9 +2059,9 @@ static int ipa_enter_tail(DeviceState* st, halo_ipa_session* ses, hipStream_t s)
         HALO_CHECK(ipa_ensure_gs(st, ses));
         HALO_CHECK(ses->own_table.reserve((size_t)TAIL_TBL * TAIL_MUL * n0 * 128));
         DISPATCH_CURVE(ses->curve, Cv, {
-            hipLaunchKernelGGL(k_tail_table<Cv>, dim3(gridn((size_t)TAIL_TABLE_LANES * n0, 64)), dim3(64), 0, s, ses->gs.as<const uint4>(),
+            hipLaunchKernelGGL(k_tail_table<Cv>, dim3(grid_for((size_t)TAIL_TABLE_LANES * n0, 64)), dim3(64), 0, s, ses->gs.as<const uint4>(),
                                (int)ses->gs_xyzz, n0, ses->own_table.as<uint4>());
-            hipLaunchKernelGGL(k_tail_mults<Cv>, dim3(gridn((size_t)TAIL_MLANES * TAIL_TBL * n0, 64)), dim3(64), 0, s, n0,
+            hipLaunchKernelGGL(k_tail_mults<Cv>, dim3(grid_for((size_t)TAIL_MLANES * TAIL_TBL * n0, 64)), dim3(64), 0, s, n0,
                                ses->own_table.as<uint4>());
         });
         HALO_HIP(hipGetLastError());
@@ -2137,7 +2128,7 @@ static int ipa_tail_sums(const DeviceState* st, halo_ipa_session* ses, int mode,
             const uint32_t tpl = tail_terms_per_lane(st, 2 * nbs1);
             const size_t nbs = (TAIL_WIN * (n0 / 2) + TAIL_THREADS * tpl - 1) / (TAIL_THREADS * tpl), nblk = 2 * nbs;
             DISPATCH_CURVE(ses->curve, Cv, {
-                hipLaunchKernelGGL(k_tail_digits<Cv>, dim3(gridn(n0, 256) + 2), dim3(256), 0, s, ses->cs.as<const uint4>(),
+                hipLaunchKernelGGL(k_tail_digits<Cv>, dim3(grid_for(n0, 256) + 2), dim3(256), 0, s, ses->cs.as<const uint4>(),
                                    ses->zs.as<const uint4>(), ses->w[ses->wcur].as<const uint4>(), n0, m, f,
                                    ses->scal.as<uint32_t>(), ses->side.as<uint8_t>(), ra.xi0_ark, ra.dots_ark,
                                    (uint32_t*)(sm + SM_HKW));
@@ -2176,7 +2167,7 @@ static int ipa_tail_sums(const DeviceState* st, halo_ipa_session* ses, int mode,
     const size_t nblk = (TAIL_WIN * n0 + TAIL_THREADS * tpl - 1) / (TAIL_THREADS * tpl);
     uint4* out = (uint4*)(sm + 256);
     DISPATCH_CURVE(ses->curve, Cv, {
-        hipLaunchKernelGGL(k_tail_scalars<Cv>, dim3(gridn(n0, 256)), dim3(256), 0, s, ses->cs.as<const uint4>(),
+        hipLaunchKernelGGL(k_tail_scalars<Cv>, dim3(grid_for(n0, 256)), dim3(256), 0, s, ses->cs.as<const uint4>(),
                            ses->w[ses->wcur].as<const uint4>(), n0, 2 * m, m, 1, ses->scal.as<uint32_t>(),
                            ses->side.as<uint8_t>());
         hipLaunchKernelGGL(k_tail_msm<Cv>, dim3((unsigned)nblk), dim3(TAIL_THREADS), 0, s, ses->table, ses->table_ld,
@@ -2268,9 +2259,9 @@ int halo::srs_small_table(DeviceState* st, int curve, hipStream_t s) {
     if (srs.small_ev) HALO_HIP(hipStreamWaitEvent(s, srs.small_ev, 0));  // the old table's last small MSM
     HALO_CHECK(srs.small_tab->reserve((size_t)TAIL_TBL * TAIL_MUL * n0 * 128));
     DISPATCH_CURVE(curve, Cv, {
-        hipLaunchKernelGGL(k_tail_table<Cv>, dim3(gridn((size_t)TAIL_TABLE_LANES * n0, 64)), dim3(64), 0, s, srs.gs.as<const uint4>(), 0, n0,
+        hipLaunchKernelGGL(k_tail_table<Cv>, dim3(grid_for((size_t)TAIL_TABLE_LANES * n0, 64)), dim3(64), 0, s, srs.gs.as<const uint4>(), 0, n0,
                            srs.small_tab->as<uint4>());
-        hipLaunchKernelGGL(k_tail_mults<Cv>, dim3(gridn((size_t)TAIL_MLANES * TAIL_TBL * n0, 64)), dim3(64), 0, s, n0,
+        hipLaunchKernelGGL(k_tail_mults<Cv>, dim3(grid_for((size_t)TAIL_MLANES * TAIL_TBL * n0, 64)), dim3(64), 0, s, n0,
                            srs.small_tab->as<uint4>());
     });
     HALO_HIP(hipGetLastError());
@@ -2289,7 +2280,7 @@ int halo::msm_srs_small(DeviceState* st, int curve, const void* scalars_ark, siz
     size_t o_side, o_part, nblk;
     HALO_CHECK(small_msm_scratch(st, curve, n, s, &scr, &o_side, &o_part, &nblk));
     DISPATCH_CURVE(curve, Cv, {
-        hipLaunchKernelGGL(k_tail_scalars<Cv>, dim3(gridn(n, 256)), dim3(256), 0, s, (const uint4*)nullptr,
+        hipLaunchKernelGGL(k_tail_scalars<Cv>, dim3(grid_for(n, 256)), dim3(256), 0, s, (const uint4*)nullptr,
                            (const uint4*)scalars_ark, n, (size_t)1, (size_t)0, 1, (uint32_t*)scr, (uint8_t*)(scr + o_side));
     });
     HALO_HIP(hipGetLastError());
@@ -2350,7 +2341,7 @@ static int ipa_round_launch(DeviceState* st, halo_ipa_session* ses) {
         const char* sl = cs + m * 32;     // round 0 (w = [1]): the scalars are c_r, c_l themselves
         const char* sr = cs;
         char* sb = (char*)ses->scal.ptr;
-        const unsigned nbk = gridn(half, 256), ndot = std::min(nbk, 256u);
+        const unsigned nbk = grid_for(half, 256), ndot = std::min(nbk, 256u);
         HALO_CHECK(ses->tmp.reserve((size_t)ndot * 64));
         const bool pair = half <= (size_t)tuning(TUNE_IPA_PAIR_MAX);
         WeightedDots wd{(const uint4*)cs, (const uint4*)zs, m, ses->tmp.as<uint4>(), (uint32_t*)(sm + SM_CTR + 8),
@@ -2481,7 +2472,7 @@ static int ipa_fold_now(DeviceState* st, halo_ipa_session* ses, const halo_fe_t*
         memcpy(&x.v[2], xi_inv, 32);
         ses->srs_round0 = false;
         DISPATCH_CURVE(ses->curve, Cv, {
-            hipLaunchKernelGGL(k_tail_fold<Cv>, dim3(gridn(std::max(m, ses->wlen), 256)), dim3(256), 0, s,
+            hipLaunchKernelGGL(k_tail_fold<Cv>, dim3(grid_for(std::max(m, ses->wlen), 256)), dim3(256), 0, s,
                                ses->cs.as<uint4>(), ses->zs.as<uint4>(), m, x, ses->w[ses->wcur].as<const uint4>(),
                                ses->w[ses->wcur ^ 1].as<uint4>(), ses->wlen);
         });
@@ -2503,7 +2494,7 @@ static int ipa_fold_now(DeviceState* st, halo_ipa_session* ses, const halo_fe_t*
     {
         DISPATCH_CURVE(ses->curve, Cv, {
             ProfScope prof("ipa_fold", s);
-            HALO_LAUNCH(prof, k_ipa_fold<Cv>, dim3(gridn(m, FOLD_THREADS)), dim3(FOLD_THREADS), 0, s, ses->gs.as<uint4>(),
+            HALO_LAUNCH(prof, k_ipa_fold<Cv>, dim3(grid_for(m, FOLD_THREADS)), dim3(FOLD_THREADS), 0, s, ses->gs.as<uint4>(),
                         ses->cs.as<uint4>(), ses->zs.as<uint4>(), m, (const uint4*)(sm + 384),
                         (const uint4*)(sm + 416));
         });
@@ -2772,7 +2763,7 @@ extern "C" int halo_ipa_fold_host(halo_curve_t curve, halo_wrapped_point_t* gs, 
     HALO_CHECK(copy_h2d(sm + 32, xi_inv, 32, s));
     HALO_CHECK(convert_wrapped_to_internal(curve, st->scratch[0].ptr, st->scratch[1].ptr, 2 * m, s));
     DISPATCH_CURVE(curve, Cv, {
-        hipLaunchKernelGGL(k_ipa_fold<Cv>, dim3(gridn(m, 128)), dim3(128), 0, s, st->scratch[1].as<uint4>(),
+        hipLaunchKernelGGL(k_ipa_fold<Cv>, dim3(grid_for(m, 128)), dim3(128), 0, s, st->scratch[1].as<uint4>(),
                            st->scratch[2].as<uint4>(), st->scratch[3].as<uint4>(), m, (const uint4*)sm,
                            (const uint4*)(sm + 32));
     });
@@ -2845,9 +2836,9 @@ static int hpoly_device(DeviceState* st, int field, const halo_fe_t* xis, size_t
     HALO_CHECK(copy_h2d(d_xis, xis, k * n_xis * 32, s));
     if (alphas) HALO_CHECK(copy_h2d(d_alpha, alphas, k * 32, s));
     DISPATCH_FIELD(field, F, {
-        hipLaunchKernelGGL(k_hpoly_tables<F>, dim3(gridn(k * (nlo + nhi), 128)), dim3(128), 0, s, (const uint4*)d_xis, k,
+        hipLaunchKernelGGL(k_hpoly_tables<F>, dim3(grid_for(k * (nlo + nhi), 128)), dim3(128), 0, s, (const uint4*)d_xis, k,
                            lg_n, lb, (const uint4*)d_alpha, t_lo, t_hi);
-        hipLaunchKernelGGL(k_hpoly_coeffs<F>, dim3(gridn((size_t)1 << lg_n, 256)), dim3(256), 0, s, (const uint4*)t_lo,
+        hipLaunchKernelGGL(k_hpoly_coeffs<F>, dim3(grid_for((size_t)1 << lg_n, 256)), dim3(256), 0, s, (const uint4*)t_lo,
                            (const uint4*)t_hi, k, lg_n, lb, (uint4*)d_out);
     });
     HALO_HIP(hipGetLastError());
@@ -2922,7 +2913,7 @@ extern "C" int halo_pcdl_decider_commit(halo_curve_t curve, const halo_fe_t* xis
     HALO_CHECK(hpoly_device(st, field, xis, 1, n_xis, nullptr, st->scratch[7].ptr, s));
     char* d_out = (char*)st->scratch[7].ptr + n * 32;
     HALO_CHECK(msm_srs_device(st, curve, st->scratch[7].ptr, n, nullptr, d_out, s, MsmOpts::Sync().xyzz()));
-    alignas(16) uint64_t xyzz[16];  // converted on the host (msm.hip d2h_point)
+    alignas(16) uint64_t xyzz[16];  // converted on the host (points.hip d2h_point)
     HALO_CHECK(copy_d2h(xyzz, d_out, 128, s));
     host_xyzz_to_wrapped(curve, xyzz, out);
     return HALO_OK;
@@ -2987,7 +2978,7 @@ extern "C" int halo_trace_commit_batch(halo_curve_t curve, const halo_fe_t* eval
     uint4* A = st->scratch[0].as<uint4>();
     uint4* B = st->scratch[1].as<uint4>();
     HALO_CHECK(copy_h2d(A, evals, bytes, s));
-    hipLaunchKernelGGL(k_rotate_right, dim3(gridn(k * n, 256)), dim3(256), 0, s, (const uint4*)A, B, k, n);
+    hipLaunchKernelGGL(k_rotate_right, dim3(grid_for(k * n, 256)), dim3(256), 0, s, (const uint4*)A, B, k, n);
     HALO_HIP(hipGetLastError());
     // batched in-place iNTT of the k rows of B (ping-pong through scratch 2 and 3)
     HALO_CHECK(ntt_device_dispatch(st, field, B, B, st->scratch[2].ptr, log_n, k, 1, s, st->scratch[3].ptr));

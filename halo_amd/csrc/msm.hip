@@ -17,6 +17,13 @@
 //   6. reduce   : per window, segments of L buckets -> (sum_t t B_t, sum_t B_t) by running sums;
 //                 one workgroup per window forms sum_j (acc_j + jL sum_j) and tree-reduces in LDS.
 //   7. final    : Horner over the windows (+ w * S for hiding commitments), XYZZ -> affine -> ark.
+//
+// This file: the digit kernels, k_acc and the hiding-term kernels; the scratch-set pipeline (MsmScratch /
+// MsmPipe); the four drivers behind one MsmPlan (msm_plan.hpp) with the batch kernels; and the ABI entries
+// that run or describe an MSM (halo_msm*, halo_srs_windows, halo_point_dot_projective,
+// halo_pedersen_commit, halo_pcdl_commit).  The sort is in sort.hip, the reduction tail in msm_tail.hip,
+// the resident SRS and its window-shifted copies in srs.hip, the point conversions and sums in
+// points.hip, the host field arithmetic in host_mont.hpp.
 #include <algorithm>
 #include <type_traits>
 #include <vector>
@@ -26,6 +33,7 @@
 #include "dispatch.hpp"
 #include "glv.hpp"
 #include "msm.hpp"
+#include "points.hpp"
 #include "runtime.hpp"
 #include "sort.hpp"
 #include "tree.hpp"
@@ -33,57 +41,6 @@
 namespace halo {
 
 static_assert(MSM_PARTIAL_U4 == PARTIAL_U4, "msm_plan.hpp lays the partials out in curve.hpp's PARTIAL_U4 words");
-
-// ---------------------------------------------------------------------------------------------
-// synthetic bases / scalars (shared host/device definition)
-// ---------------------------------------------------------------------------------------------
-__host__ __device__ inline uint64_t splitmix64(uint64_t& x) {
-    uint64_t z = (x += 0x9e3779b97f4a7c15ull);
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-    return z ^ (z >> 31);
-}
-__host__ __device__ inline void synth_scalar(uint64_t seed, uint64_t j, uint64_t out[4]) {
-    uint64_t st = seed ^ (j * 0xd1b54a32d192ed03ull);
-    for (int i = 0; i < 4; i++) out[i] = splitmix64(st);
-    out[3] &= 0x1fffffffffffffffull;  // < 2^253 < p
-    if ((out[0] | out[1] | out[2] | out[3]) == 0) out[0] = 1;
-}
-
-// ---------------------------------------------------------------------------------------------
-// conversion / generation kernels
-// ---------------------------------------------------------------------------------------------
-template <class F>
-__global__ void k_wrapped_to_internal(const uint4* in, uint4* out, size_t n) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    aff_store(out + 4 * i, aff_from_wrapped<F>(in + 4 * i));
-}
-
-template <class F>
-__global__ void k_internal_to_wrapped(const uint4* in, uint4* out, size_t n) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    aff_to_wrapped(out + 4 * i, aff_load<F>(in + 4 * i));
-}
-
-template <class Cv>
-__global__ __launch_bounds__(64) void k_synth_bases(uint4* out, size_t n, uint64_t seed) {
-    using F = typename Cv::Base;
-    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n) return;
-    uint64_t k[4];
-    synth_scalar(seed, j, k);
-    uint32_t w[8];
-    for (int i = 0; i < 4; i++) {
-        w[2 * i] = (uint32_t)k[i];
-        w[2 * i + 1] = (uint32_t)(k[i] >> 32);
-    }
-    Affine<F> G;
-    G.x = fe_from_const<F>(Cv::K::GX);
-    G.y = fe_from_const<F>(Cv::K::GY);
-    aff_store(out + 4 * j, xyzz_to_aff(xyzz_scalar_mul(G, w)));
-}
 
 // ---------------------------------------------------------------------------------------------
 // 1. digits
@@ -334,52 +291,9 @@ __global__ __launch_bounds__(256) void k_hide_terms(const uint4* hide_table, Hid
     hide_term_block<Cv>(hide_table, hs.sc[blockIdx.x], glv, hide_out + 8 * blockIdx.x);
 }
 
-
-// ---------------------------------------------------------------------------------------------
-// SRS precomputation: window-shifted bases 2^(c w) G_i (w < W) and the hiding table 2^i S
-// ---------------------------------------------------------------------------------------------
-// copies w in [w_lo, w_hi) -> out[(w - w_lo) n + i] (a rank of a window partition holds only its own)
-template <class Cv>
-__global__ __launch_bounds__(64) void k_shift_windows(const uint4* gs, size_t n, int c, int w_lo, int w_hi, uint4* out,
-                                                      uint32_t* has_id) {
-    using F = typename Cv::Base;
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const Affine<F> g = aff_load<F>(gs + 4 * i);
-    if (aff_is_id(g)) has_id[0] = 1u;  // (every copy of an identity is the identity; a prime-order
-                                       // group has no other point with 2^(c w) g = 0)
-    if (w_lo == 0) aff_store(out + 4 * i, g);
-    XYZZ<F> p = xyzz_from_aff(g);
-    for (int w = 1; w < w_hi; w++) {
-        for (int k = 0; k < c; k++) p = xyzz_dbl(p);
-        if (w >= w_lo) aff_store(out + 4 * ((size_t)(w - w_lo) * n + i), xyzz_to_aff(p));
-    }
-}
-
-template <class Cv>
-__global__ __launch_bounds__(64) void k_pow2_points(const uint4* P_int, uint4* out_xyzz, int count) {
-    using F = typename Cv::Base;
-    if (threadIdx.x != 0) return;
-    XYZZ<F> p = xyzz_from_aff(aff_load<F>(P_int));
-    for (int i = 0; i < count; i++) {
-        xyzz_store(out_xyzz + 8 * i, p);
-        p = xyzz_dbl(p);
-    }
-}
-
-template <class Cv>
-__global__ __launch_bounds__(64) void k_xyzz_to_aff(const uint4* in, uint4* out, int count) {
-    using F = typename Cv::Base;
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= count) return;
-    aff_store(out + 4 * i, xyzz_to_aff(xyzz_load<F>(in + 8 * i)));
-}
-
 // ---------------------------------------------------------------------------------------------
 // host orchestration
 // ---------------------------------------------------------------------------------------------
-static unsigned grid_for(size_t n, unsigned thr) { return (unsigned)std::max<size_t>(1, (n + thr - 1) / thr); }
-
 // Four scratch sets in two slots of two, a slot per issuing stream (least recently used slot
 // reassigned): consecutive MSMs of one stream alternate between their slot's two sets (the tail of
 // k overlaps k+1), two concurrent streams (two IPA openings in lockstep) never wait for each
@@ -745,7 +659,7 @@ static int msm_multi_device_t(DeviceState* st, const void* const* scalars, const
 template <class Cv>
 static int msm_srs_pairs_t(DeviceState* st, size_t np, const MsmPairIO* io, size_t half, uint32_t lgm,
                            const uint4* hide_table, hipStream_t s, hipEvent_t hide_ready, const MsmPreHide* pre_hide,
-                           uint32_t* host_emit, uint32_t seq) {
+                           uint32_t* emit_host, uint32_t seq) {
     SrsState& srs = st->srs[curve_id<Cv>()];
     const size_t m = (size_t)1 << lgm;
     if (!srs.shifted_c) return set_error(HALO_EINVAL, "msm_srs_pairs: no window-shifted SRS");
@@ -815,7 +729,7 @@ static int msm_srs_pairs_t(DeviceState* st, size_t np, const MsmPairIO* io, size
     ta.pair_hide = hide_slot;  // k_bitcombine adds the hiding terms and writes the outputs
     ta.pair_outs = outs;
     if (np == 1) {
-        ta.pair_host = host_emit;
+        ta.pair_host = emit_host;
         ta.pair_seq = seq;
     }
     HALO_HIP(hipStreamWaitEvent(s, M.front_done, 0));  // the hiding terms (done beside the front)
@@ -829,10 +743,10 @@ static int msm_srs_pairs_t(DeviceState* st, size_t np, const MsmPairIO* io, size
 
 int msm_srs_pairs_device(DeviceState* st, int curve, size_t np, const MsmPairIO* io, size_t half, uint32_t lgm,
                          const void* hide_table, hipStream_t s, hipEvent_t hide_ready, const MsmPreHide* pre_hide,
-                         uint32_t* host_emit, uint32_t seq) {
+                         uint32_t* emit_host, uint32_t seq) {
     int rc;
     DISPATCH_CURVE(curve, Cv, {
-        rc = msm_srs_pairs_t<Cv>(st, np, io, half, lgm, (const uint4*)hide_table, s, hide_ready, pre_hide, host_emit,
+        rc = msm_srs_pairs_t<Cv>(st, np, io, half, lgm, (const uint4*)hide_table, s, hide_ready, pre_hide, emit_host,
                                  seq);
     });
     return rc;
@@ -1119,549 +1033,6 @@ int msm_shared_batch(DeviceState* st, int curve, const void* bases_int, const vo
     return rc;
 }
 
-// ---------------------------------------------------------------------------------------------
-// Host-side XYZZ -> affine (the IPA's per-round L and R, and every entry point that returns one point
-// to the host): the lane-side conversion is a ~30 us dependent chain on one lane (fe_inv) at the end
-// of the reduction tail; on the host it is a few microseconds.  A packed internal coordinate is an integer < 2p congruent to v 2^261, so
-// x = X / ZZ and y = Y / ZZZ need no change of representation; 4 x 64-bit Montgomery arithmetic
-// (R = 2^256) then yields x R mod p, which is the ark word form directly.
-// ---------------------------------------------------------------------------------------------
-namespace {
-struct HostMont {
-    uint64_t p[4], pinv, r2[4], one[4], inv_fix[4];
-    uint32_t p32[8];
-    explicit HostMont(const uint64_t (&m)[4]) {
-        for (int i = 0; i < 4; i++) p[i] = m[i];
-        uint64_t inv = 1;  // p[0]^-1 mod 2^64 by Newton's iteration
-        for (int i = 0; i < 6; i++) inv *= 2 - p[0] * inv;
-        pinv = 0 - inv;
-        uint64_t x[4] = {1, 0, 0, 0};
-        for (int i = 0; i < 512; i++) {  // 2^256 mod p (= one), then 2^512 mod p (= r2)
-            dbl(x);
-            if (i == 255)
-                for (int k = 0; k < 4; k++) one[k] = x[k];
-        }
-        for (int k = 0; k < 4; k++) r2[k] = x[k];
-        for (int k = 0; k < 8; k++) p32[k] = (uint32_t)(p[k >> 1] >> (32 * (k & 1)));
-        mul(r2, r2, inv_fix);  // R^3 = 2^768 mod p (inv)
-    }
-    bool geq_p(const uint64_t (&a)[4]) const {
-        for (int i = 3; i >= 0; i--)
-            if (a[i] != p[i]) return a[i] > p[i];
-        return true;
-    }
-    void sub_p(uint64_t (&a)[4]) const {
-        unsigned __int128 b = 0;
-        for (int i = 0; i < 4; i++) {
-            const unsigned __int128 d = (unsigned __int128)a[i] - p[i] - b;
-            a[i] = (uint64_t)d;
-            b = (d >> 64) & 1;
-        }
-    }
-    void dbl(uint64_t (&a)[4]) const {  // a < p (p < 2^255): 2a < 2^256
-        uint64_t c = 0;
-        for (int i = 0; i < 4; i++) {
-            const uint64_t t = (a[i] << 1) | c;
-            c = a[i] >> 63;
-            a[i] = t;
-        }
-        if (geq_p(a)) sub_p(a);
-    }
-    void mul(const uint64_t (&a)[4], const uint64_t (&b)[4], uint64_t (&out)[4]) const {  // a b R^-1 mod p (CIOS)
-        uint64_t t[6] = {0, 0, 0, 0, 0, 0};
-        for (int i = 0; i < 4; i++) {
-            unsigned __int128 c = 0;
-            for (int j = 0; j < 4; j++) {
-                c += (unsigned __int128)a[j] * b[i] + t[j];
-                t[j] = (uint64_t)c;
-                c >>= 64;
-            }
-            c += t[4];
-            t[4] = (uint64_t)c;
-            t[5] = (uint64_t)(c >> 64);
-            const uint64_t m = t[0] * pinv;
-            c = ((unsigned __int128)m * p[0] + t[0]) >> 64;
-            for (int j = 1; j < 4; j++) {
-                c += (unsigned __int128)m * p[j] + t[j];
-                t[j - 1] = (uint64_t)c;
-                c >>= 64;
-            }
-            c += t[4];
-            t[3] = (uint64_t)c;
-            t[4] = t[5] + (uint64_t)(c >> 64);
-        }
-        uint64_t r[4] = {t[0], t[1], t[2], t[3]};
-        if (t[4] || geq_p(r)) sub_p(r);
-        for (int i = 0; i < 4; i++) out[i] = r[i];
-    }
-    // Montgomery domain (a = x R mod p, a < p): Pornin's optimized binary GCD, the same algorithm as the
-    // device's fe_inv (fields.hpp: 17 rounds of 30 steps on 62-bit approximations, each round's 2x2
-    // factors applied to a, b and, with a Montgomery division by 2^30, to the coefficients u, v).  It
-    // leaves v = a^-1 = x^-1 R^-1 (the invariants a = x u, b = x v mod p survive the rounds' common
-    // division by 2^30); one product with inv_fix = R^3 makes it x^-1 R.
-    // (Host: about 3x faster than the Fermat chain a^(p-2), 384 products, and 1.7x faster than a
-    // plain binary extended Euclid.)
-    static int bitlen8(const uint32_t (&a)[8]) {
-        for (int i = 7; i >= 0; i--)
-            if (a[i]) return 32 * i + 32 - __builtin_clz(a[i]);
-        return 0;
-    }
-    static uint32_t align30(uint32_t hi, uint32_t lo, int s) { return (uint32_t)((((uint64_t)hi << 32) | lo) >> s); }
-    static uint64_t approx(const uint32_t (&a)[8], int n) {  // (a mod 2^30) + 2^30 floor(a / 2^(n - 32))
-        const int s = n - 32, i = s >> 5;
-        const uint32_t lo = a[i], hi = i + 1 < 8 ? a[i + 1] : 0u;
-        return (uint64_t)(a[0] & 0x3fffffffu) | ((uint64_t)align30(hi, lo, s & 31) << 30);
-    }
-    static bool lin(const uint32_t (&a)[8], const uint32_t (&b)[8], int64_t f, int64_t g, uint32_t (&r)[8]) {
-        uint32_t t[8];
-        int64_t c = 0;
-        for (int i = 0; i < 8; i++) {  // |a f + b g| / 2^30, exact; returns the sign
-            const int64_t x = (int64_t)a[i] * f + (int64_t)b[i] * g + c;
-            t[i] = (uint32_t)x;
-            c = x >> 32;
-        }
-        const bool neg = c < 0;
-        uint64_t br = 1;
-        for (int i = 0; i < 8; i++) {
-            const uint32_t sh = align30(i < 7 ? t[i + 1] : (uint32_t)c, t[i], 30);
-            const uint64_t ng = (uint64_t)(~sh) + br;
-            br = ng >> 32;
-            r[i] = neg ? (uint32_t)ng : sh;
-        }
-        return neg;
-    }
-    void lin_mod(const uint32_t (&u)[8], const uint32_t (&v)[8], int64_t f, int64_t g, uint32_t (&r)[8]) const {
-        uint32_t t[8];
-        int64_t c = 0;
-        for (int i = 0; i < 8; i++) {  // (u f + v g) / 2^30 mod p (p = 1 mod 2^32)
-            const int64_t x = (int64_t)u[i] * f + (int64_t)v[i] * g + c;
-            t[i] = (uint32_t)x;
-            c = x >> 32;
-        }
-        const uint32_t q = (0u - t[0]) & 0x3fffffffu;
-        int64_t c2 = 0;
-        for (int i = 0; i < 8; i++) {
-            const int64_t x = (int64_t)t[i] + (int64_t)((uint64_t)q * p32[i]) + c2;
-            t[i] = (uint32_t)x;
-            c2 = x >> 32;
-        }
-        const int64_t top = c + c2;
-        uint32_t s[8];
-        for (int i = 0; i < 8; i++) s[i] = align30(i < 7 ? t[i + 1] : (uint32_t)top, t[i], 30);
-        int32_t hi = (int32_t)(top >> 30);
-        for (int k = 0; k < 2 && hi < 0; k++) {
-            uint64_t cy = 0;
-            for (int i = 0; i < 8; i++) {
-                const uint64_t x = (uint64_t)s[i] + p32[i] + cy;
-                s[i] = (uint32_t)x;
-                cy = x >> 32;
-            }
-            hi += (int32_t)cy;
-        }
-        uint64_t bw = 0;
-        uint32_t w[8];
-        for (int i = 0; i < 8; i++) {
-            const uint64_t x = (uint64_t)s[i] - p32[i] - bw;
-            w[i] = (uint32_t)x;
-            bw = (x >> 32) & 1u;
-        }
-        for (int i = 0; i < 8; i++) r[i] = bw == 0 ? w[i] : s[i];
-    }
-    void inv(const uint64_t (&x)[4], uint64_t (&out)[4]) const {
-        uint32_t a[8], b[8], u[8], v[8];
-        for (int i = 0; i < 8; i++) {
-            a[i] = (uint32_t)(x[i >> 1] >> (32 * (i & 1)));
-            b[i] = p32[i];
-            u[i] = i == 0 ? 1u : 0u;
-            v[i] = 0u;
-        }
-        for (int it = 0; it < 17; it++) {  // ceil((2 * 255 - 1) / 30) rounds: b = gcd = 1
-            const int n = std::max(std::max(bitlen8(a), bitlen8(b)), 62);
-            uint64_t ab = approx(a, n), bb = approx(b, n);
-            int32_t f0 = 1, g0 = 0, f1 = 0, g1 = 1;
-            for (int j = 0; j < 30; j++) {
-                const bool odd = ab & 1u;
-                const bool sw = odd && ab < bb;
-                const uint64_t ta = sw ? bb : ab, tb = sw ? ab : bb;
-                const int32_t tf0 = sw ? f1 : f0, tg0 = sw ? g1 : g0, tf1 = sw ? f0 : f1, tg1 = sw ? g0 : g1;
-                ab = (odd ? ta - tb : ta) >> 1;
-                bb = tb;
-                f0 = odd ? tf0 - tf1 : tf0;
-                g0 = odd ? tg0 - tg1 : tg0;
-                f1 = tf1 * 2;
-                g1 = tg1 * 2;
-            }
-            uint32_t na[8], nb[8], nu[8], nv[8];
-            if (lin(a, b, f0, g0, na)) {
-                f0 = -f0;
-                g0 = -g0;
-            }
-            if (lin(a, b, f1, g1, nb)) {
-                f1 = -f1;
-                g1 = -g1;
-            }
-            lin_mod(u, v, f0, g0, nu);
-            lin_mod(u, v, f1, g1, nv);
-            for (int i = 0; i < 8; i++) {
-                a[i] = na[i];
-                b[i] = nb[i];
-                u[i] = nu[i];
-                v[i] = nv[i];
-            }
-        }
-        uint64_t r[4];
-        for (int i = 0; i < 4; i++) r[i] = (uint64_t)v[2 * i] | ((uint64_t)v[2 * i + 1] << 32);
-        mul(r, inv_fix, out);
-    }
-};
-
-template <class F>
-void host_xyzz_to_wrapped_t(const void* xyzz, void* wrapped) {
-    static const HostMont M(F::MODULUS64);
-    const uint64_t* q = (const uint64_t*)xyzz;
-    uint64_t c[4][4];  // X, Y, ZZ, ZZZ reduced below p
-    for (int k = 0; k < 4; k++) {
-        for (int i = 0; i < 4; i++) c[k][i] = q[4 * k + i];
-        if (M.geq_p(c[k])) M.sub_p(c[k]);
-    }
-    uint64_t* out = (uint64_t*)wrapped;
-    if (!(c[2][0] | c[2][1] | c[2][2] | c[2][3])) {  // ZZ = 0: the identity, WrappedPoint (0, 0)
-        for (int i = 0; i < 8; i++) out[i] = 0;
-        return;
-    }
-    uint64_t m[4][4], t[4], iv[4], u[4], x[4], y[4];
-    for (int k = 0; k < 4; k++) M.mul(c[k], M.r2, m[k]);  // to the Montgomery domain
-    M.mul(m[2], m[3], t);
-    M.inv(t, iv);  // (ZZ ZZZ)^-1
-    M.mul(m[0], m[3], u);
-    M.mul(u, iv, x);  // X / ZZ, times R
-    M.mul(m[1], m[2], u);
-    M.mul(u, iv, y);  // Y / ZZZ, times R
-    for (int i = 0; i < 4; i++) {
-        out[i] = x[i];
-        out[4 + i] = y[i];
-    }
-}
-// k points with one inversion (Montgomery's trick over the ZZ ZZZ products; k <= 16)
-template <class F>
-void host_xyzz_to_wrapped2_t(const void* const* xyzz, void* const* wrapped, int k) {
-    static const HostMont M(F::MODULUS64);
-    uint64_t m[16][4][4], t[16][4], pre[17][4];
-    bool id[16];
-    for (int j = 0; j < 4; j++) pre[0][j] = M.one[j];
-    for (int i = 0; i < k; i++) {
-        const uint64_t* q = (const uint64_t*)xyzz[i];
-        uint64_t c[4][4];
-        for (int a = 0; a < 4; a++) {
-            for (int j = 0; j < 4; j++) c[a][j] = q[4 * a + j];
-            if (M.geq_p(c[a])) M.sub_p(c[a]);
-        }
-        id[i] = !(c[2][0] | c[2][1] | c[2][2] | c[2][3]);
-        for (int a = 0; a < 4; a++) M.mul(c[a], M.r2, m[i][a]);
-        if (id[i])
-            for (int j = 0; j < 4; j++) t[i][j] = M.one[j];
-        else
-            M.mul(m[i][2], m[i][3], t[i]);
-        M.mul(pre[i], t[i], pre[i + 1]);
-    }
-    uint64_t inv[4];
-    M.inv(pre[k], inv);  // (prod_i ZZ_i ZZZ_i)^-1
-    for (int i = k - 1; i >= 0; i--) {
-        uint64_t iv[4], u[4], x[4], y[4];
-        M.mul(inv, pre[i], iv);  // (ZZ_i ZZZ_i)^-1
-        M.mul(inv, t[i], inv);
-        uint64_t* out = (uint64_t*)wrapped[i];
-        if (id[i]) {
-            for (int j = 0; j < 8; j++) out[j] = 0;
-            continue;
-        }
-        M.mul(m[i][0], m[i][3], u);
-        M.mul(u, iv, x);
-        M.mul(m[i][1], m[i][2], u);
-        M.mul(u, iv, y);
-        for (int j = 0; j < 4; j++) {
-            out[j] = x[j];
-            out[4 + j] = y[j];
-        }
-    }
-}
-}  // namespace
-
-void host_xyzz_to_wrapped2(int curve, const void* const* xyzz, void* const* wrapped, int k) {
-    if (curve == HALO_PALLAS)
-        host_xyzz_to_wrapped2_t<PallasCurve::Base>(xyzz, wrapped, k);
-    else
-        host_xyzz_to_wrapped2_t<VestaCurve::Base>(xyzz, wrapped, k);
-}
-
-template <class S>
-static bool host_scalar_inverse_t(const void* x_ark, void* out_ark) {
-    static const HostMont M(S::MODULUS64);
-    uint64_t x[4];
-    for (int i = 0; i < 4; i++) x[i] = ((const uint64_t*)x_ark)[i];
-    if (M.geq_p(x)) M.sub_p(x);
-    if (!(x[0] | x[1] | x[2] | x[3])) return false;
-    uint64_t r[4];
-    M.inv(x, r);  // Montgomery-domain inverse: (x R)^-1 R^2 = x^-1 R, the ark form of x^-1
-    for (int i = 0; i < 4; i++) ((uint64_t*)out_ark)[i] = r[i];
-    return true;
-}
-bool host_scalar_inverse(int curve, const void* x_ark, void* out_ark) {
-    return curve == HALO_PALLAS ? host_scalar_inverse_t<PallasCurve::Scalar>(x_ark, out_ark)
-                                : host_scalar_inverse_t<VestaCurve::Scalar>(x_ark, out_ark);
-}
-
-void host_xyzz_to_wrapped(int curve, const void* xyzz, void* wrapped) {
-    if (curve == HALO_PALLAS)
-        host_xyzz_to_wrapped_t<PallasCurve::Base>(xyzz, wrapped);
-    else
-        host_xyzz_to_wrapped_t<VestaCurve::Base>(xyzz, wrapped);
-}
-
-// Host-output entry points: the MSM leaves its sum as 128-B packed XYZZ on the device, and the affine
-// conversion (one inversion) runs on the host after the copy -- not as a one-lane chain at the end
-// of the reduction tail.
-static int d2h_point(int curve, const void* d_xyzz, halo_wrapped_point_t* out, hipStream_t s) {
-    alignas(16) uint64_t buf[16];
-    HALO_CHECK(copy_d2h(buf, d_xyzz, 128, s));
-    host_xyzz_to_wrapped(curve, buf, out);
-    return HALO_OK;
-}
-
-int convert_wrapped_to_internal(int curve, const void* in, void* out, size_t n, hipStream_t s) {
-    if (!n) return HALO_OK;
-    DISPATCH_CURVE(curve, Cv, {
-        hipLaunchKernelGGL(k_wrapped_to_internal<typename Cv::Base>, dim3(grid_for(n, 256)), dim3(256), 0, s,
-                           (const uint4*)in, (uint4*)out, n);
-    });
-    HALO_HIP(hipGetLastError());
-    return HALO_OK;
-}
-
-int convert_internal_to_wrapped(int curve, const void* in, void* out, size_t n, hipStream_t s) {
-    if (!n) return HALO_OK;
-    DISPATCH_CURVE(curve, Cv, {
-        hipLaunchKernelGGL(k_internal_to_wrapped<typename Cv::Base>, dim3(grid_for(n, 256)), dim3(256), 0, s,
-                           (const uint4*)in, (uint4*)out, n);
-    });
-    HALO_HIP(hipGetLastError());
-    return HALO_OK;
-}
-
-// hiding table 2^i S (i < 256), internal affine
-static int build_s_table(DeviceState* st, int curve, hipStream_t s) {
-    SrsState& srs = st->srs[curve];
-    HALO_CHECK(srs.s_table.reserve(256 * 64));
-    HALO_CHECK(st->scratch[7].reserve(256 * 128 + 64));
-    char* tmp = (char*)st->scratch[7].ptr;
-    HALO_CHECK(copy_h2d(tmp + 256 * 128, srs.S, 64, s));
-    DISPATCH_CURVE(curve, Cv, {
-        hipLaunchKernelGGL(k_pow2_points<Cv>, dim3(1), dim3(64), 0, s, (const uint4*)(tmp + 256 * 128), (uint4*)tmp,
-                           256);
-        hipLaunchKernelGGL(k_xyzz_to_aff<Cv>, dim3(4), dim3(64), 0, s, (const uint4*)tmp, srs.s_table.as<uint4>(), 256);
-    });
-    HALO_HIP(hipGetLastError());
-    return HALO_OK;
-}
-
-// The window-shifted copies 2^(c w) G_i for w in [w_lo, w_hi) (c = 0: the default width for the SRS
-// length; w_hi = 0: every window).  The full set serves every SRS MSM; a partial range (one rank of a
-// window-partitioned MSM, BASELINE configs[4]) serves halo_msm_srs_windows_dev over that range only.
-int srs_precompute_windows(DeviceState* st, int curve, hipStream_t s, int c, int w_lo, int w_hi) {
-    SrsState& srs = st->srs[curve];
-    if (!srs.n) return set_error(HALO_ESRSRANGE, "no resident SRS to precompute");
-    if (c == 0) c = msm_shifted_window_bits(srs.n);
-    if (c < 2 || c > 20) return set_error(HALO_EINVAL, "window bits %d outside [2, 20]", c);
-    const int W = msm_windows(c);
-    if (w_hi == 0) w_hi = W;
-    if (w_lo < 0 || w_hi > W || w_lo >= w_hi)
-        return set_error(HALO_EINVAL, "window range [%d, %d) outside [0, %d)", w_lo, w_hi, W);
-    srs.shifted_c = srs.part_c = 0;  // nothing valid while the copies are rewritten
-    // asynchronous MSMs (halo_msm_srs_windows_dev, the pipelined MSM sets) and weighted IPA rounds on
-    // other streams may still be reading the copies: drain the device before they are rewritten or
-    // reallocated (a precompute is a setup step, never on a timed path)
-    HALO_HIP(hipDeviceSynchronize());
-    HALO_CHECK(srs.shifted.reserve((size_t)(w_hi - w_lo) * srs.n * 64));
-    ScratchUse su(st, s);
-    HALO_CHECK(st->scratch[7].reserve(4));
-    uint32_t* flag = st->scratch[7].as<uint32_t>();
-    HALO_HIP(hipMemsetAsync(flag, 0, 4, s));
-    DISPATCH_CURVE(curve, Cv, {
-        hipLaunchKernelGGL(k_shift_windows<Cv>, dim3(grid_for(srs.n, 64)), dim3(64), 0, s, srs.gs.as<const uint4>(),
-                           srs.n, c, w_lo, w_hi, srs.shifted.as<uint4>(), flag);
-    });
-    HALO_HIP(hipGetLastError());
-    uint32_t has_id = 1;
-    HALO_HIP(hipMemcpyAsync(&has_id, flag, 4, hipMemcpyDeviceToHost, s));
-    HALO_HIP(hipStreamSynchronize(s));
-    srs.shifted_has_id = has_id != 0;
-    if (w_lo == 0 && w_hi == W) {
-        srs.shifted_c = c;
-    } else {
-        srs.part_c = c;
-        srs.part_w0 = w_lo;
-        srs.part_w1 = w_hi;
-    }
-    return HALO_OK;
-}
-
-}  // namespace halo
-
-using namespace halo;
-
-namespace halo {
-// one block per row: row b sums the k WrappedPoints at pts_wrapped + 4 k b into out_wrapped + 4 b
-template <class Cv>
-__global__ __launch_bounds__(256) void k_point_sum(const uint4* pts_wrapped, size_t k, uint4* out_wrapped) {
-    using F = typename Cv::Base;
-    __shared__ uint4 red[256 * 8];
-    pts_wrapped += 4 * k * (size_t)blockIdx.x;
-    out_wrapped += 4 * (size_t)blockIdx.x;
-    XYZZ<F> acc = xyzz_id<F>();
-    for (size_t i = threadIdx.x; i < k; i += 256) acc = xyzz_madd(acc, aff_from_wrapped<F>(pts_wrapped + 4 * i));
-    xyzz_store(red + 8 * threadIdx.x, acc);
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off)
-            xyzz_store(red + 8 * threadIdx.x,
-                       xyzz_add(xyzz_load<F>(red + 8 * threadIdx.x), xyzz_load<F>(red + 8 * (threadIdx.x + off))));
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) aff_to_wrapped(out_wrapped, xyzz_to_aff(xyzz_load<F>(red)));
-}
-
-// Sum of k packed XYZZ points (stride_bytes apart) -> packed XYZZ (no affine conversion on the device)
-template <class Cv>
-__global__ __launch_bounds__(256) void k_point_sum_xyzz(const uint4* pts, size_t k, size_t stride_u4, uint4* out) {
-    using F = typename Cv::Base;
-    __shared__ uint4 red[256 * 8];
-    XYZZ<F> acc = xyzz_id<F>();
-    for (size_t i = threadIdx.x; i < k; i += 256) acc = xyzz_add(acc, xyzz_load<F>(pts + stride_u4 * i));
-    xyzz_store(red + 8 * threadIdx.x, acc);
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off)
-            xyzz_store(red + 8 * threadIdx.x,
-                       xyzz_add(xyzz_load<F>(red + 8 * threadIdx.x), xyzz_load<F>(red + 8 * (threadIdx.x + off))));
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) xyzz_store(out, xyzz_load<F>(red));
-}
-
-}  // namespace halo
-
-static int check_curve(halo_curve_t c) {
-    if (c != HALO_PALLAS && c != HALO_VESTA) return set_error(HALO_EINVAL, "unknown curve id %d", (int)c);
-    return HALO_OK;
-}
-
-extern "C" int halo_msm_window_bits(size_t n) { return msm_window_bits(n); }
-
-extern "C" int halo_srs_window_bits(halo_curve_t curve) {
-    clear_error();
-    if (curve != HALO_PALLAS && curve != HALO_VESTA) return set_error(HALO_EINVAL, "unknown curve id %d", (int)curve);
-    DeviceState* st = current_state();
-    if (!st) return HALO_EDEVICE;
-    std::lock_guard<std::mutex> g(st->mu);
-    const SrsState& srs = st->srs[curve];
-    return srs.shifted_c ? srs.shifted_c : srs.part_c;
-}
-
-extern "C" int halo_point_sum(halo_curve_t curve, const halo_wrapped_point_t* pts, size_t k, halo_wrapped_point_t* out) {
-    clear_error();
-    HALO_CHECK(check_curve(curve));
-    if (!out || (k && !pts)) return set_error(HALO_EINVAL, "halo_point_sum: null buffer");
-    DeviceState* st = current_state();
-    if (!st) return HALO_EDEVICE;
-    std::lock_guard<std::mutex> g(st->mu);
-    hipStream_t s = 0;
-    ScratchUse su(st, s);
-    HALO_CHECK(st->scratch[0].reserve(std::max<size_t>(k, 1) * 64 + 64));
-    char* buf = (char*)st->scratch[0].ptr;
-    HALO_CHECK(copy_h2d(buf + 64, pts, k * 64, s));
-    DISPATCH_CURVE(curve, Cv, {
-        hipLaunchKernelGGL(k_point_sum<Cv>, dim3(1), dim3(256), 0, s, (const uint4*)(buf + 64), k, (uint4*)buf);
-    });
-    HALO_HIP(hipGetLastError());
-    return copy_d2h(out, buf, 64, s);
-}
-
-extern "C" int halo_point_sum_dev(halo_curve_t curve, const void* d_pts, size_t k, size_t stride_bytes, void* d_out,
-                                  void* stream) {
-    clear_error();
-    HALO_CHECK(check_curve(curve));
-    if (!d_out || (k && !d_pts)) return set_error(HALO_EINVAL, "halo_point_sum_dev: null buffer");
-    if (stride_bytes != 64) return set_error(HALO_EINVAL, "halo_point_sum_dev: only contiguous (64-B stride) points");
-    hipStream_t s = (hipStream_t)stream;
-    DISPATCH_CURVE(curve, Cv, {
-        hipLaunchKernelGGL(k_point_sum<Cv>, dim3(1), dim3(256), 0, s, (const uint4*)d_pts, k, (uint4*)d_out);
-    });
-    HALO_HIP(hipGetLastError());
-    return HALO_OK;
-}
-
-extern "C" int halo_point_sum_rows_dev(halo_curve_t curve, const void* d_pts, size_t rows, size_t k, void* d_out,
-                                       void* stream) {
-    clear_error();
-    HALO_CHECK(check_curve(curve));
-    if (!rows) return HALO_OK;
-    if (!d_out || (k && !d_pts)) return set_error(HALO_EINVAL, "halo_point_sum_rows_dev: null buffer");
-    if (rows > 65535) return set_error(HALO_EINVAL, "halo_point_sum_rows_dev: %zu rows (at most 65535)", rows);
-    hipStream_t s = (hipStream_t)stream;
-    DISPATCH_CURVE(curve, Cv, {
-        hipLaunchKernelGGL(k_point_sum<Cv>, dim3((unsigned)rows), dim3(256), 0, s, (const uint4*)d_pts, k, (uint4*)d_out);
-    });
-    HALO_HIP(hipGetLastError());
-    return HALO_OK;
-}
-
-extern "C" int halo_point_sum_xyzz_dev(halo_curve_t curve, const void* d_pts, size_t k, size_t stride_bytes, void* d_out,
-                                       void* stream) {
-    clear_error();
-    HALO_CHECK(check_curve(curve));
-    if (!d_out || (k && !d_pts)) return set_error(HALO_EINVAL, "halo_point_sum_xyzz_dev: null buffer");
-    if (stride_bytes < 128 || stride_bytes % 16)
-        return set_error(HALO_EINVAL, "halo_point_sum_xyzz_dev: stride %zu (a multiple of 16, at least 128)", stride_bytes);
-    hipStream_t s = (hipStream_t)stream;
-    DISPATCH_CURVE(curve, Cv, {
-        hipLaunchKernelGGL(k_point_sum_xyzz<Cv>, dim3(1), dim3(256), 0, s, (const uint4*)d_pts, k, stride_bytes / 16,
-                           (uint4*)d_out);
-    });
-    HALO_HIP(hipGetLastError());
-    return HALO_OK;
-}
-
-extern "C" int halo_xyzz_to_wrapped(halo_curve_t curve, const void* xyzz, size_t k, halo_wrapped_point_t* out) {
-    clear_error();
-    HALO_CHECK(check_curve(curve));
-    if (k && (!xyzz || !out)) return set_error(HALO_EINVAL, "halo_xyzz_to_wrapped: null buffer");
-    for (size_t i = 0; i < k; i++) host_xyzz_to_wrapped(curve, (const char*)xyzz + 128 * i, out + i);
-    return HALO_OK;
-}
-
-extern "C" int halo_srs_read(halo_curve_t curve, size_t offset, size_t n, halo_wrapped_point_t* out) {
-    clear_error();
-    HALO_CHECK(check_curve(curve));
-    if (!out && n) return set_error(HALO_EINVAL, "halo_srs_read: null buffer");
-    DeviceState* st = current_state();
-    if (!st) return HALO_EDEVICE;
-    std::lock_guard<std::mutex> g(st->mu);
-    SrsState& srs = st->srs[curve];
-    if (offset + n > srs.n) return set_error(HALO_ESRSRANGE, "range [%zu, %zu) exceeds the SRS length %zu", offset, offset + n, srs.n);
-    if (!n) return HALO_OK;
-    hipStream_t s = 0;
-    ScratchUse su(st, s);
-    HALO_CHECK(st->scratch[0].reserve(n * 64));
-    HALO_CHECK(convert_internal_to_wrapped(curve, srs.gs.as<const char>() + offset * 64, st->scratch[0].ptr, n, s));
-    return copy_d2h(out, st->scratch[0].ptr, n * 64, s);
-}
-
-extern "C" void halo_synth_scalar(halo_curve_t curve, uint64_t seed, uint64_t j, uint64_t out_canonical[4]) {
-    (void)curve;
-    synth_scalar(seed, j, out_canonical);
-}
-
-namespace halo {
 // ark Projective (Jacobian X, Y, Z, Montgomery, 96 B) -> internal affine; Z = 0 -> (0, 0).  One
 // Fermat inversion per lane (Projective::normalize_batch of point_dot, group.rs:53-56).
 template <class Cv>
@@ -1682,7 +1053,35 @@ __global__ void k_jacobian_to_internal(const uint4* in, uint4* out, size_t n) {
     }
     aff_store(out + 4 * i, a);
 }
+
+// k commitments over the resident SRS prefix (lens[i] scalars at d_scalars[i]) -> d_out + 64 i,
+// asynchronous on s (msm_join before reading)
+int msm_batch_device(DeviceState* st, int curve, const void* const* d_scalars, const size_t* lens, size_t k, void* d_out,
+                     hipStream_t s) {
+    SrsState& srs = st->srs[curve];
+    size_t nmax = 0;
+    for (size_t i = 0; i < k; i++) {
+        if (lens[i] && !d_scalars[i]) return set_error(HALO_EINVAL, "halo_msm_batch_dev: null scalars %zu", i);
+        if (lens[i] > srs.n) return set_error(HALO_ESRSRANGE, "n (%zu) exceeds the resident SRS length (%zu)", lens[i], srs.n);
+        nmax = std::max(nmax, lens[i]);
+    }
+    // (Measured and removed: the fronts on a side stream beside the accumulations -- slower, the
+    // sort kernels starve beside k_acc's gathers, DESIGN.md §4.)
+    if (k > 1 && srs.shifted_c && nmax <= msm_multi_max()) {
+        int rc;
+        DISPATCH_CURVE(curve, Cv, { rc = msm_multi_device_t<Cv>(st, d_scalars, lens, k, (uint4*)d_out, s); });
+        return rc;
+    }
+    for (size_t i = 0; i < k; i++)
+        HALO_CHECK(msm_srs_device(st, curve, d_scalars[i], lens[i], nullptr, (char*)d_out + 64 * i, s, MsmOpts::Async()));
+    return HALO_OK;
+}
+
 }  // namespace halo
+
+using namespace halo;
+
+extern "C" int halo_msm_window_bits(size_t n) { return msm_window_bits(n); }
 
 // group::point_dot(xs, &[Projective]) (crates/group/src/group.rs:53-56): the bases arrive as ark
 // Projective (Jacobian) points, normalised on the device, then the MSM of halo_msm.
@@ -1745,241 +1144,6 @@ extern "C" int halo_msm(halo_curve_t curve, const halo_wrapped_point_t* bases, s
     return d2h_point(curve, st->scratch[3].ptr, out, s);
 }
 
-// SRS management --------------------------------------------------------------------------------
-// Installs n WrappedPoints already in device memory (d_wrapped, may be scratch[0]) as the resident
-// SRS of `curve`, plus (S, H) when given (host WrappedPoints).
-static int srs_install(DeviceState* st, int curve, const void* d_wrapped, size_t n, const halo_wrapped_point_t* S,
-                       const halo_wrapped_point_t* H, hipStream_t s) {
-    SrsState& srs = st->srs[curve];
-    HALO_CHECK(srs.gs.reserve(std::max<size_t>(n, 1) * 64));
-    HALO_CHECK(convert_wrapped_to_internal(curve, d_wrapped, srs.gs.ptr, n, s));
-    srs.n = n;
-    srs.invalidate_derived();
-    if (S && H) {
-        HALO_CHECK(st->scratch[1].reserve(256));
-        char* tmp = (char*)st->scratch[1].ptr;
-        HALO_CHECK(copy_h2d(tmp, S, 64, s));
-        HALO_CHECK(copy_h2d(tmp + 64, H, 64, s));
-        HALO_CHECK(convert_wrapped_to_internal(curve, tmp, tmp + 128, 2, s));
-        HALO_CHECK(copy_d2h(srs.S, tmp + 128, 64, s));
-        HALO_CHECK(copy_d2h(srs.H, tmp + 192, 64, s));
-        srs.H_wrapped = *H;
-        srs.has_sh = true;
-        HALO_CHECK(build_s_table(st, curve, s));
-    }
-    HALO_HIP(hipStreamSynchronize(s));
-    return HALO_OK;
-}
-
-extern "C" int halo_srs_upload(halo_curve_t curve, const halo_wrapped_point_t* gs, size_t n,
-                               const halo_wrapped_point_t* S, const halo_wrapped_point_t* H) {
-    clear_error();
-    HALO_CHECK(check_curve(curve));
-    if ((n && !gs)) return set_error(HALO_EINVAL, "halo_srs_upload: null gs");
-    DeviceState* st = current_state();
-    if (!st) return HALO_EDEVICE;
-    std::lock_guard<std::mutex> g(st->mu);
-    hipStream_t s = 0;
-    ScratchUse su(st, s);
-    HALO_CHECK(st->scratch[0].reserve(std::max<size_t>(n, 2) * 64));
-    HALO_CHECK(copy_h2d(st->scratch[0].ptr, gs, n * 64, s));
-    return srs_install(st, curve, st->scratch[0].ptr, n, S, H, s);
-}
-
-// ---------------------------------------------------------------------------------------------
-// the SRS wire format (bincode-v2 `standard()` Vec<WrappedPoint> per block,
-// pp.rs:36-53; (S, H) tuple in sh.bin) decoded on the device.  A block whose records are all in the
-// fixed 72-byte form (every u64 limb as 0xFD + 8 LE bytes -- what the reference's generator writes
-// for Montgomery limbs >= 2^32) is decoded by k_decode_points, one record per lane; any other
-// record (a small limb gets a shorter varint) sends that block through the sequential host decoder.
-// Every point is then checked on the curve on the device (wrappers.rs:606 `assert!(is_on_curve)`).
-// ---------------------------------------------------------------------------------------------
-__global__ void k_decode_points(const uint8_t* rec0, size_t count, uint4* out, uint32_t* bad) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= count) return;
-    const uint8_t* r = rec0 + 72 * i;
-    uint32_t w[16];
-    bool ok = true;
-#pragma unroll
-    for (int l = 0; l < 8; l++) {
-        const uint8_t* f = r + 9 * l;
-        ok &= (f[0] == 0xFD);
-        w[2 * l] = (uint32_t)f[1] | ((uint32_t)f[2] << 8) | ((uint32_t)f[3] << 16) | ((uint32_t)f[4] << 24);
-        w[2 * l + 1] = (uint32_t)f[5] | ((uint32_t)f[6] << 8) | ((uint32_t)f[7] << 16) | ((uint32_t)f[8] << 24);
-    }
-    if (!ok) atomicOr(bad, 1u);
-    out[4 * i] = make_uint4(w[0], w[1], w[2], w[3]);
-    out[4 * i + 1] = make_uint4(w[4], w[5], w[6], w[7]);
-    out[4 * i + 2] = make_uint4(w[8], w[9], w[10], w[11]);
-    out[4 * i + 3] = make_uint4(w[12], w[13], w[14], w[15]);
-}
-
-template <class Cv>
-__global__ void k_check_on_curve(const uint4* pts_wrapped, size_t n, uint32_t* bad) {
-    using F = typename Cv::Base;
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const Affine<F> a = aff_from_wrapped<F>(pts_wrapped + 4 * i);
-    // y^2 == x^3 + 5 (the identity (0, 0) is not on the curve, as for ark's Affine::new_unchecked)
-    const Fe<F> lhs = fe_sqr(a.y);
-    const Fe<F> rhs = fe_add(fe_mul(fe_sqr(a.x), a.x), fe_from_const<F>(Cv::K::B));
-    if (!fe_eq(lhs, rhs)) atomicAdd(bad, 1u);
-}
-
-// bincode-v2 standard() unsigned varint
-static bool bc_varint(const uint8_t* b, size_t len, size_t& off, uint64_t& v) {
-    if (off >= len) return false;
-    const uint8_t t = b[off];
-    if (t < 251) {
-        v = t;
-        off += 1;
-        return true;
-    }
-    const int width = t == 251 ? 2 : t == 252 ? 4 : t == 253 ? 8 : 0;
-    if (!width || off + 1 + width > len) return false;
-    v = 0;
-    for (int i = 0; i < width; i++) v |= (uint64_t)b[off + 1 + i] << (8 * i);
-    off += 1 + width;
-    return true;
-}
-
-static bool bc_point(const uint8_t* b, size_t len, size_t& off, halo_wrapped_point_t& p) {
-    for (int l = 0; l < 4; l++)
-        if (!bc_varint(b, len, off, p.x[l])) return false;
-    for (int l = 0; l < 4; l++)
-        if (!bc_varint(b, len, off, p.y[l])) return false;
-    return true;
-}
-
-extern "C" int halo_srs_load_bincode(halo_curve_t curve, const uint8_t* const* blocks, const size_t* block_lens,
-                                     size_t nblocks, const uint8_t* sh, size_t sh_len, size_t n) {
-    clear_error();
-    HALO_CHECK(check_curve(curve));
-    if (!is_pow2(n)) return set_error(HALO_ENOTPOW2, "assertion failed: n.is_power_of_two()");
-    if (nblocks && (!blocks || !block_lens)) return set_error(HALO_EINVAL, "halo_srs_load_bincode: null blocks");
-    halo_wrapped_point_t SH[2];
-    if (sh) {
-        size_t off = 0;
-        if (!bc_point(sh, sh_len, off, SH[0]) || !bc_point(sh, sh_len, off, SH[1]))
-            return set_error(HALO_EINVAL, "Failed to get SH data for curve %s", curve == HALO_PALLAS ? "pallas" : "vesta");
-    }
-    DeviceState* st = current_state();
-    if (!st) return HALO_EDEVICE;
-    std::lock_guard<std::mutex> g(st->mu);
-    hipStream_t s = 0;
-    ScratchUse su(st, s);
-    HALO_CHECK(st->scratch[0].reserve(std::max<size_t>(n, 2) * 64));
-    HALO_CHECK(st->scratch[2].reserve(16));
-    uint4* d_pts = st->scratch[0].as<uint4>();
-    uint32_t* d_bad = st->scratch[2].as<uint32_t>();
-    size_t have = 0;
-    std::vector<halo_wrapped_point_t> host_pts;
-    for (size_t bi = 0; bi < nblocks && have < n; bi++) {
-        const uint8_t* b = blocks[bi];
-        const size_t len = block_lens[bi];
-        size_t off = 0;
-        uint64_t count = 0;
-        if (!b || !bc_varint(b, len, off, count)) return set_error(HALO_EINVAL, "Failed to decode G_BLOCKS_NO %zu", bi);
-        const size_t take = std::min<size_t>(count, n - have);
-        bool fast = (len - off) >= 72 * take;
-        if (fast && take) {
-            HALO_CHECK(st->scratch[3].reserve(72 * take));
-            HALO_HIP(hipMemsetAsync(d_bad, 0, 4, s));
-            HALO_CHECK(copy_h2d(st->scratch[3].ptr, b + off, 72 * take, s));
-            hipLaunchKernelGGL(k_decode_points, dim3(grid_for(take, 256)), dim3(256), 0, s,
-                               st->scratch[3].as<const uint8_t>(), take, d_pts + 4 * have, d_bad);
-            HALO_HIP(hipGetLastError());
-            uint32_t bad = 0;
-            HALO_CHECK(copy_d2h(&bad, d_bad, 4, s));
-            fast = (bad == 0);
-        }
-        if (!fast) {  // general varints: sequential host decode of this block
-            host_pts.resize(take);
-            for (size_t i = 0; i < take; i++)
-                if (!bc_point(b, len, off, host_pts[i])) return set_error(HALO_EINVAL, "Failed to decode G_BLOCKS_NO %zu", bi);
-            HALO_CHECK(copy_h2d(d_pts + 4 * have, host_pts.data(), take * 64, s));
-        }
-        have += take;
-    }
-    if (have < n) return set_error(HALO_ESRSRANGE, "assertion failed: n <= N (%zu points available)", have);
-    HALO_HIP(hipMemsetAsync(d_bad, 0, 4, s));
-    DISPATCH_CURVE(curve, Cv, {
-        hipLaunchKernelGGL(k_check_on_curve<Cv>, dim3(grid_for(n, 256)), dim3(256), 0, s, (const uint4*)d_pts, n, d_bad);
-    });
-    HALO_HIP(hipGetLastError());
-    uint32_t bad = 0;
-    HALO_CHECK(copy_d2h(&bad, d_bad, 4, s));
-    if (bad) return set_error(HALO_EINVAL, "assertion failed: affine.is_on_curve() (%u points)", bad);
-    return srs_install(st, curve, d_pts, n, sh ? &SH[0] : nullptr, sh ? &SH[1] : nullptr, s);
-}
-
-// PublicParams' (S, H) (pp.rs:26-61) as ark WrappedPoints
-extern "C" int halo_srs_sh(halo_curve_t curve, halo_wrapped_point_t* S, halo_wrapped_point_t* H) {
-    clear_error();
-    HALO_CHECK(check_curve(curve));
-    if (!S || !H) return set_error(HALO_EINVAL, "halo_srs_sh: null buffer");
-    DeviceState* st = current_state();
-    if (!st) return HALO_EDEVICE;
-    std::lock_guard<std::mutex> g(st->mu);
-    SrsState& srs = st->srs[curve];
-    if (!srs.has_sh) return set_error(HALO_ESRSRANGE, "no (S, H) uploaded");
-    hipStream_t s = 0;
-    ScratchUse su(st, s);
-    HALO_CHECK(st->scratch[0].reserve(256));
-    char* b = st->scratch[0].as<char>();
-    HALO_CHECK(copy_h2d(b, srs.S, 64, s));
-    HALO_CHECK(copy_h2d(b + 64, srs.H, 64, s));
-    HALO_CHECK(convert_internal_to_wrapped(curve, b, b + 128, 2, s));
-    HALO_CHECK(copy_d2h(S, b + 128, 64, s));
-    return copy_d2h(H, b + 192, 64, s);
-}
-
-extern "C" int halo_srs_len(halo_curve_t curve, size_t* n) {
-    clear_error();
-    HALO_CHECK(check_curve(curve));
-    if (!n) return set_error(HALO_EINVAL, "null n");
-    DeviceState* st = current_state();
-    if (!st) return HALO_EDEVICE;
-    *n = st->srs[curve].n;
-    return HALO_OK;
-}
-
-extern "C" int halo_srs_synthesize(halo_curve_t curve, size_t n, uint64_t seed) {
-    clear_error();
-    HALO_CHECK(check_curve(curve));
-    DeviceState* st = current_state();
-    if (!st) return HALO_EDEVICE;
-    std::lock_guard<std::mutex> g(st->mu);
-    hipStream_t s = 0;
-    ScratchUse su(st, s);
-    SrsState& srs = st->srs[curve];
-    HALO_CHECK(srs.gs.reserve(std::max<size_t>(n, 1) * 64));
-    if (n) {
-        DISPATCH_CURVE(curve, Cv, {
-            hipLaunchKernelGGL(k_synth_bases<Cv>, dim3(grid_for(n, 64)), dim3(64), 0, s, srs.gs.as<uint4>(), n, seed);
-        });
-        HALO_HIP(hipGetLastError());
-    }
-    HALO_HIP(hipStreamSynchronize(s));
-    srs.n = n;
-    srs.invalidate_derived();
-    return HALO_OK;
-}
-
-extern "C" int halo_srs_precompute_windows(halo_curve_t curve) {
-    return halo_srs_precompute_window_range(curve, 0, 0, 0);
-}
-
-extern "C" int halo_srs_precompute_window_range(halo_curve_t curve, int c, int w_lo, int w_hi) {
-    clear_error();
-    HALO_CHECK(check_curve(curve));
-    DeviceState* st = current_state();
-    if (!st) return HALO_EDEVICE;
-    std::lock_guard<std::mutex> g(st->mu);
-    ScratchUse su(st, 0);
-    return srs_precompute_windows(st, curve, 0, c, w_lo, w_hi);
-}
-
 extern "C" int halo_msm_srs(halo_curve_t curve, const halo_fe_t* scalars, size_t n, halo_wrapped_point_t* out) {
     clear_error();
     HALO_CHECK(check_curve(curve));
@@ -2037,31 +1201,6 @@ extern "C" int halo_msm_dev_async(halo_curve_t curve, const void* d_bases, const
     HALO_CHECK(convert_wrapped_to_internal(curve, d_bases, conv->ptr, n, s));
     return msm_device(st, curve, conv->ptr, d_scalars, n, nullptr, nullptr, d_out, s, MsmOpts::Async().on_set(set));
 }
-
-namespace halo {
-// k commitments over the resident SRS prefix (lens[i] scalars at d_scalars[i]) -> d_out + 64 i,
-// asynchronous on s (msm_join before reading)
-int msm_batch_device(DeviceState* st, int curve, const void* const* d_scalars, const size_t* lens, size_t k, void* d_out,
-                     hipStream_t s) {
-    SrsState& srs = st->srs[curve];
-    size_t nmax = 0;
-    for (size_t i = 0; i < k; i++) {
-        if (lens[i] && !d_scalars[i]) return set_error(HALO_EINVAL, "halo_msm_batch_dev: null scalars %zu", i);
-        if (lens[i] > srs.n) return set_error(HALO_ESRSRANGE, "n (%zu) exceeds the resident SRS length (%zu)", lens[i], srs.n);
-        nmax = std::max(nmax, lens[i]);
-    }
-    // (Measured and removed: the fronts on a side stream beside the accumulations -- slower, the
-    // sort kernels starve beside k_acc's gathers, DESIGN.md §4.)
-    if (k > 1 && srs.shifted_c && nmax <= msm_multi_max()) {
-        int rc;
-        DISPATCH_CURVE(curve, Cv, { rc = msm_multi_device_t<Cv>(st, d_scalars, lens, k, (uint4*)d_out, s); });
-        return rc;
-    }
-    for (size_t i = 0; i < k; i++)
-        HALO_CHECK(msm_srs_device(st, curve, d_scalars[i], lens[i], nullptr, (char*)d_out + 64 * i, s, MsmOpts::Async()));
-    return HALO_OK;
-}
-}  // namespace halo
 
 extern "C" int halo_msm_batch_dev(halo_curve_t curve, const void* const* d_scalars, const size_t* lens, size_t k,
                                   void* d_out, void* stream) {

@@ -1,6 +1,6 @@
-// Internal interfaces shared between msm.hip, ipa.hip and the multi-GPU glue.
+// The MSM's internal interface: the drivers of msm.hip, the small-table and tiny MSMs of ipa.hip and
+// the reduction tail of msm_tail.hip.
 #pragma once
-#include <vector>
 #include "msm_plan.hpp"
 #include "runtime.hpp"
 
@@ -12,7 +12,7 @@ struct MsmOpts {
     bool async;                       // false: stream s also waits for the reduction tail; true: msm_join does
     uint32_t blk_lg = 32;             // msm_srs_range_device: half-blocks of 2^blk_lg points (32: contiguous)
     bool hide_glv = false;            // the hiding table is {2^i P : i < 128}, the scalar GLV-split (k_hide_term)
-    bool out_xyzz = false;            // the result as 128 B packed XYZZ (host_xyzz_to_wrapped), not a WrappedPoint
+    bool out_xyzz = false;            // the result as 128 B packed XYZZ (points.hpp), not a WrappedPoint
     hipEvent_t hide_ready = nullptr;  // event after which the hiding table is complete (built on another stream)
     int preset = -1;                  // msm_device: the scratch set the caller claimed (msm_claim_set)
     static MsmOpts Sync() { return MsmOpts(false); }
@@ -39,8 +39,6 @@ int msm_claim_set(DeviceState* st, hipStream_t s, int* set, DevBuf** conv);
 // result i (WrappedPoint) at d_out + 64 i; asynchronous on s like msm_device(async) (msm_join).
 int msm_batch_device(DeviceState* st, int curve, const void* const* d_scalars, const size_t* lens, size_t k, void* d_out,
                      hipStream_t s);
-// Destroys the MSM pipeline's streams and events (halo_shutdown).
-void msm_shutdown();
 // Makes stream s wait for the reduction tails of the async MSMs enqueued on s.
 int msm_join(DeviceState* st, hipStream_t s);
 // Restarts the scratch-set slot assignment (no owners, first sets) when no MSM tail is running.
@@ -77,15 +75,16 @@ struct MsmPreHide {
     void (*fn)(hipStream_t ts, void* ctx);
     void* ctx;
 };
-// host_emit (np == 1 only): L and R also go to pinned host memory with flags = seq (MsmTailArgs::pair_host)
+// emit_host (np == 1 only): L and R also go to pinned host memory with flags = seq (MsmTailArgs::pair_host)
 int msm_srs_pairs_device(DeviceState* st, int curve, size_t np, const MsmPairIO* io, size_t half, uint32_t lgm,
                          const void* hide_table, hipStream_t s, hipEvent_t hide_ready, const MsmPreHide* pre_hide = nullptr,
-                         uint32_t* host_emit = nullptr, uint32_t seq = 0);
+                         uint32_t* emit_host = nullptr, uint32_t seq = 0);
 // shift_stride > 0: bases are the resident window-shifted SRS (copy w = 2^(c_s w) G at w shift_stride):
 // every c_s-bit digit of w[u] is split into three unsigned sub-digits, so the final Horner runs
 // over three windows (~2 c_s / 3 doublings) instead of ~255 / c windows (~255 doublings).
 int msm_shared_batch(DeviceState* st, int curve, const void* bases_int, const void* w_ark, size_t T, size_t len,
                      void* out, bool xyzz_out, BatchScratch& S, hipStream_t s, size_t shift_stride = 0, int c_s = 0);
+// The window-shifted copies 2^(c w) G_i, w in [w_lo, w_hi), that the SRS drivers above read (srs.hip).
 int srs_precompute_windows(DeviceState* st, int curve, hipStream_t s, int c = 0, int w_lo = 0, int w_hi = 0);
 // Small MSM over the resident SRS prefix (1 <= n <= srs_small_max(), ipa.hip): every (point, 4-bit GLV
 // window) term is one entry of a per-SRS multiples table, then block trees with the hiding term
@@ -102,44 +101,10 @@ int srs_small_table(DeviceState* st, int curve, hipStream_t s);
 int msm_tiny(int curve, const void* bases_int, const void* scalars_ark, size_t n, void* scratch, void* out_xyzz,
              hipStream_t s);
 size_t msm_tiny_max();
-// out_xyzz: the result as 128 B packed XYZZ (host_xyzz_to_wrapped) instead of a WrappedPoint.
+// out_xyzz: the result as 128 B packed XYZZ (points.hpp) instead of a WrappedPoint.
 // plus_wrapped (device WrappedPoint, or null): added to the result.
 int msm_srs_small(DeviceState* st, int curve, const void* scalars_ark, size_t n, const void* hide_scalar,
                   void* d_out_wrapped, hipStream_t s, bool out_xyzz = false, const void* plus_wrapped = nullptr);
-// ---- not MSM: what ipa.hip, field_ops.hip and the NTT declare here for each other (the pcdl_*
-// steps, the host point / scalar conversions, ntt_device_dispatch) ------------------------------
-// Releases the pooled IPA sessions (halo_shutdown, ipa.hip).
-void ipa_shutdown();
-// The hiding branch of pcdl::open_without_eval on device buffers (field_ops.hip), stream-ordered on s:
-// p_bar = (X - z) q (q: d ark coefficients, z: ark scalar) -> d + 1 ark coefficients;
-// p' = p (len coefficients, zero-padded to n) + alpha p_bar (p' may alias p), w' = w + alpha w_bar,
-// C' = C + alpha C_bar - w' S (C, C_bar, C' WrappedPoints; S internal affine).
-int pcdl_pbar_device(int curve, const void* q, size_t d, const void* z, void* p_bar, hipStream_t s);
-int pcdl_combine_device(int curve, const void* p, size_t len, const void* p_bar, size_t n, const void* alpha,
-                        const void* w, const void* w_bar, const void* C, const void* C_bar, const void* S_int,
-                        void* p_prime, void* C_prime, void* w_prime, hipStream_t s);
-// p[i] += alpha p_bar[i] and p_bar[i] = alpha p_bar[i] in place (i < n); w' = w + alpha w_bar, negw = -w.
-int pcdl_combine_scalars_device(int curve, void* p, void* p_bar, size_t n, const void* alpha, const void* w,
-                                const void* w_bar, void* w_prime, void* negw, hipStream_t s);
-// xyzz (128 B packed XYZZ) = xyzz (or, from_wrapped, the WrappedPoint first_wrapped) + the WrappedPoint
-// at wrapped (one lane).
-int xyzz_add_wrapped_device(int curve, void* xyzz, const void* wrapped, hipStream_t s, bool from_wrapped = false,
-                            const void* first_wrapped = nullptr);
-// Host conversion of a 128-B packed XYZZ point (internal format, each coordinate < 2p) to an ark
-// WrappedPoint: one inversion in 4 x 64-bit Montgomery arithmetic on the CPU (identity -> (0, 0)).
-void host_xyzz_to_wrapped(int curve, const void* xyzz, void* wrapped);
-// x^-1 of an ark (Montgomery) scalar of the curve's scalar field, on the host (binary extended Euclid);
-// false for x = 0
-bool host_scalar_inverse(int curve, const void* x_ark, void* out_ark);
-// k <= 16 points at once with one inversion (Montgomery's trick)
-void host_xyzz_to_wrapped2(int curve, const void* const* xyzz, void* const* wrapped, int k);
-int convert_wrapped_to_internal(int curve, const void* in, void* out, size_t n, hipStream_t s);
-int convert_internal_to_wrapped(int curve, const void* in, void* out, size_t n, hipStream_t s);
-// rad: the pass split to launch (null: ntt_radices(logn)); a caller that sized anything by the split
-// (the zero-tail prune) passes the vector it used
-int ntt_device_dispatch(DeviceState* st, int field, const void* d_in, void* d_out, void* d_tmp, unsigned logn,
-                        size_t batch, int inverse, hipStream_t s, void* d_tmp2 = nullptr, unsigned prune = 0,
-                        const std::vector<unsigned>* rad = nullptr);
 
 // ---- the MSM's reduction tail (msm_tail.hip) ---------------------------------------------------
 // Inputs of the MSM's reduction tail (msm_tail.hip), launched on the tail stream.

@@ -335,8 +335,6 @@ __global__ __launch_bounds__(64) void k_final(const uint4* window_sums, int W, i
         aff_to_wrapped(out_wrapped, xyzz_to_aff(horner));
 }
 
-static unsigned grid_for_t(size_t n, unsigned thr) { return (unsigned)std::max<size_t>(1, (n + thr - 1) / thr); }
-
 template <class Cv>
 static int tail_launch_t(const MsmTailArgs& a, hipStream_t ts) {
     if (a.n > 0) {
@@ -349,7 +347,7 @@ static int tail_launch_t(const MsmTailArgs& a, hipStream_t ts) {
         // two lanes per bucket, each summing half of its chunk partials (measured per bucket: one lane
         // 167 us, two 138 us, four 172 us isolated at 2^20)
         constexpr int lanes = 2;
-        hipLaunchKernelGGL((k_merge<Cv, lanes>), dim3(grid_for_t(a.p.NB * lanes, 256)), dim3(256), 0, ts, (const uint32_t*)a.bstart,
+        hipLaunchKernelGGL((k_merge<Cv, lanes>), dim3(grid_for(a.p.NB * lanes, 256)), dim3(256), 0, ts, (const uint32_t*)a.bstart,
                            a.scount, a.p.K, a.p.NB, (const uint4*)a.first, (const uint4*)a.last,
                            (const uint4*)a.g1, (const uint4*)a.g2, a.bucket_sums);
         if (a.batch_windows) {
@@ -360,7 +358,7 @@ static int tail_launch_t(const MsmTailArgs& a, hipStream_t ts) {
             const uint32_t segs = std::max(BATCH_SEGS, B / 8);
             auto kws = segs == 8 ? k_batch_window_sums<Cv, 8> : segs == 16 ? k_batch_window_sums<Cv, 16>
                      : segs == 32 ? k_batch_window_sums<Cv, 32> : k_batch_window_sums<Cv, 64>;
-            hipLaunchKernelGGL(kws, dim3(grid_for_t((size_t)a.p.SW * segs, 256)), dim3(256), 0, ts,
+            hipLaunchKernelGGL(kws, dim3(grid_for((size_t)a.p.SW * segs, 256)), dim3(256), 0, ts,
                                (const uint4*)a.bucket_sums, (uint32_t)a.p.SW, B, a.window_sums);
             HALO_HIP(hipGetLastError());
             return HALO_OK;

@@ -19,7 +19,7 @@
 #include <cstdlib>
 
 #include "dispatch.hpp"
-#include "msm.hpp"
+#include "ntt.hpp"
 #include "runtime.hpp"
 
 namespace halo {

@@ -1,6 +1,5 @@
 // Runtime: error state, device selection, per-device state, buffers.
 #include "runtime.hpp"
-#include "msm.hpp"
 
 #include <atomic>
 #include <cstdio>

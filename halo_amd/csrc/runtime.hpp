@@ -4,6 +4,7 @@
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstddef>
 #include <cstdint>
@@ -170,11 +171,19 @@ struct ProfScope {
             hipLaunchKernelGGL(kern, grid, block, shmem, stream, __VA_ARGS__);                        \
     } while (0)
 
+// ---- halo_shutdown: what each subsystem releases while the HIP runtime is alive -----------------
+// Destroys the MSM pipeline's streams and events (halo_shutdown).
+void msm_shutdown();
+// Releases the pooled IPA sessions (halo_shutdown, ipa.hip).
+void ipa_shutdown();
+
 inline bool is_pow2(size_t n) { return n && !(n & (n - 1)); }
 inline unsigned ilog2(size_t n) {
     unsigned r = 0;
     while ((size_t(1) << (r + 1)) <= n) r++;
     return r;
 }
+// blocks of `threads` lanes that cover n items (at least one)
+inline unsigned grid_for(size_t n, unsigned threads) { return (unsigned)std::max<size_t>(1, (n + threads - 1) / threads); }
 
 }  // namespace halo

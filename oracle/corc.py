@@ -157,7 +157,7 @@ def msm_window_size(n: int) -> int:
 
 
 def synth_scalars(seed: int, n: int) -> np.ndarray:
-    """numpy restatement of halo_synth_scalar (msm.hip synth_scalar: a splitmix64 stream per index,
+    """numpy restatement of halo_synth_scalar (srs.hip synth_scalar: a splitmix64 stream per index,
     top word masked below 2^253, zero replaced by 1): the known discrete logs k_j of the synthetic
     SRS G_j = k_j G, canonical (not Montgomery)."""
     j = np.arange(n, dtype=np.uint64)

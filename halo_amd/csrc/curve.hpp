@@ -202,8 +202,9 @@ HALO_DEV XYZZ<F> xyzz_madd_acc(const XYZZ<F>& p, const Affine<F>& q, uint32_t ne
 // U2_i - X_i + 4p_i + c <= (2^29 - 1) + (2^30 - 2) + (2^29 - 1) + 3 and X3_i - Q_i + 6p_i + c <=
 // 3 (2^29 - 1) + (2^29 - 1) + 3, both 2^31 - 1 at most (so c <= 3), and >= -2^30 - 2^29 - 3 below.
 // Rn Tn + Yt PPP < 72p^2 + 4p^2 < p 2^261 with all four operands normalized, P^2 < 100p^2.
-// xyzz_run_out settles X and applies s for a store.  tests/test_acc_three_chains.py models the step limb
-// by limb on adversarial operands.
+// xyzz_run_out settles X and applies s: before an interior bucket's store, and in partial_load for the
+// chunk partials, which are stored as they stand.  tests/test_acc_three_chains.py models the step limb
+// by limb on adversarial operands, tests/test_raw_partials.py the partial's store and load.
 template <class F>
 HALO_DEV XYZZ<F> xyzz_madd_run(const XYZZ<F>& p, uint32_t& sneg, bool& fresh, const Affine<F>& q, uint32_t negmask,
                                bool check_q) {
@@ -304,8 +305,8 @@ HALO_DEV XYZZ<F> xyzz_madd_run_aff(const XYZZ<F>& p, uint32_t& sneg, bool& fresh
     return r;
 }
 
-// A running sum of xyzz_madd_run as a plain XYZZ for a store: X + 4p through one carry chain (normalized,
-// in (0, 8p): what partial_load and xyzz_settle take) and Y = Yt, or 2p - Yt in (0, 2p] when s = -1, by one
+// A running sum of xyzz_madd_run as a plain XYZZ: X + 4p through one carry chain (normalized,
+// in (0, 8p): what xyzz_settle takes) and Y = Yt, or 2p - Yt in (0, 2p] when s = -1, by one
 // chain with the sign folded in (as fe_sub_k_sgn; 2p itself only from Yt = 0, which no product gives
 // -- Rn, Tn > 0 -- and no curve point has; it is normalized, below 2^256 and 0 mod p all the same).
 template <class F>
@@ -450,19 +451,28 @@ HALO_DEV void xyzz_store(uint4* p, const XYZZ<F>& a) {
     fe_store(p + 6, a.ZZZ);
 }
 
-// Chunk partials (k_acc -> k_group_sums -> k_merge): XYZZ as 4 x 9 raw limbs, 36 dwords = 9 uint4
-// (144 B), with X as k_acc's running sum leaves it (normalized limbs, < 8p).  k_acc then stores
-// without settling X or packing limbs; its bucket-boundary stores are divergent (at 2^20 about a
-// quarter of its steps have a lane at a boundary), so they cost the whole wave.  The loader settles X.
+// Chunk partials (k_acc -> k_group_sums -> k_merge): 4 x 9 raw limbs, 36 dwords = 9 uint4 (144 B),
+// holding a running sum of xyzz_madd_run as k_acc has it in registers -- the point (X, s Yt, ZZ, ZZZ):
+//   X    signed-lazy: int32 limbs, |limb| < 2^30, value in (-4p, 4p) (xyzz_madd_run's X3), or normalized
+//        and below 2p (a lane's first entry, a doubling, a settled sum);
+//   Yt, ZZ, ZZZ  normalized, below 2p: every limb but the top one is below 2^29;
+//   s    in bit 31 of ZZ's limb 0 (set for s = -1), which that limb's value (< 2^29) never reaches.
+// k_acc's bucket-boundary stores are divergent (at 2^20 about a quarter of its steps have a lane at a
+// boundary), so whatever a store computes costs the whole wave: it computes nothing, and the loader, where
+// every lane loads a partial of its own, runs xyzz_run_out's two carry chains (X + 4p, normalized, in
+// (0, 8p): X_i + 4p_i + c stays within +-(2^30 + 2^29); Y = Yt or 2p - Yt) and settles X below 2p.
+// A settled sum (k_group_sums) is the same format with s = 0: X < 2p comes back as it is.  The identity
+// (ZZ = 0: xyzz_id, or what a cancelled segment left) loads as the identity whatever X, Yt and s hold.
 constexpr int PARTIAL_U4 = 9;
 template <class F>
-HALO_DEV void partial_store(uint4* p, const XYZZ<F>& a) {
+HALO_DEV void partial_store(uint4* p, const XYZZ<F>& a, uint32_t sneg = 0) {
     const Fe<F>* c[4] = {&a.X, &a.Y, &a.ZZ, &a.ZZZ};
     uint32_t w[4 * NLIMB];
 #pragma unroll
     for (int k = 0; k < 4; k++)
 #pragma unroll
         for (int i = 0; i < NLIMB; i++) w[k * NLIMB + i] = c[k]->v[i];
+    w[2 * NLIMB] |= sneg & 0x80000000u;
 #pragma unroll
     for (int q = 0; q < PARTIAL_U4; q++) p[q] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
 }
@@ -483,6 +493,9 @@ HALO_DEV XYZZ<F> partial_load(const uint4* p) {
     for (int k = 0; k < 4; k++)
 #pragma unroll
         for (int i = 0; i < NLIMB; i++) c[k]->v[i] = w[k * NLIMB + i];
+    const uint32_t sneg = (uint32_t)((int32_t)a.ZZ.v[0] >> 31);
+    a.ZZ.v[0] &= 0x7fffffffu;
+    a = xyzz_run_out(a, sneg);
     a.X = fe_reduce_8p(a.X);
     return a;
 }

@@ -6,6 +6,28 @@
 
 namespace halo {
 
+// Step one of the recoding: the ark scalar as its folded canonical integer min(s, p - s) < 2^254 with
+// the fold's sign in bit 255 (digits_core.hpp digits_fold) -- the one Montgomery multiplication, the
+// comparison with p / 2 and the subtraction from p that a scalar's recoding costs before any window is cut.
+template <class S>
+HALO_DEV void scalar_fold(const uint4* scalar, uint32_t (&f8)[8]) {
+    fe_ark_to_canonical_words<S>(scalar, f8);
+    uint32_t p8[8];
+#pragma unroll
+    for (int q = 0; q < 8; q++) p8[q] = (uint32_t)(S::MODULUS64[q >> 1] >> (32 * (q & 1)));
+    digits_fold(f8, p8);
+}
+
+// Step two: the windows of a folded scalar (scalar_fold's 8 words), f(w, digit) as below.
+template <int WMAX = 0, int C = 0, class Fn>
+HALO_DEV void folded_signed_digits(const uint32_t (&f8)[8], int c, int W, Fn&& f) {
+    uint32_t w8[8];
+#pragma unroll
+    for (int q = 0; q < 8; q++) w8[q] = f8[q];
+    const uint32_t flip = digits_unfold(w8);
+    signed_digit_entries<C, WMAX>(w8, flip, c, W, f);
+}
+
 // The W signed c-bit digits of an ark scalar, as sort entries: DIGIT_NONE for a zero digit, else
 // (|d| - 1) with bit 31 = sign.  s > p / 2 is replaced by p - s and every digit's sign flipped
 // (s P = -(p - s) P), so W = ceil(255 / c) windows suffice.  f(w, digit) is called for w < W in order.
@@ -16,22 +38,9 @@ namespace halo {
 // mask, and the loop is unrolled whatever WMAX.
 template <class S, int WMAX = 0, int C = 0, class Fn>
 HALO_DEV void scalar_signed_digits(const uint4* scalar, int c, int W, Fn&& f) {
-    uint32_t w8[8];
-    fe_ark_to_canonical_words<S>(scalar, w8);
-    // t = p - s, and the borrow of t - s: set when p - s < s
-    uint32_t t8[8];
-    int64_t br = 0, lt = 0;
-#pragma unroll
-    for (int q = 0; q < 8; q++) {
-        const int64_t d = (int64_t)(uint32_t)(S::MODULUS64[q >> 1] >> (32 * (q & 1))) - (int64_t)w8[q] + br;
-        t8[q] = (uint32_t)d;
-        br = d >> 32;
-        lt = ((int64_t)t8[q] - (int64_t)w8[q] + lt) >> 32;
-    }
-    const bool neg = lt != 0;
-#pragma unroll
-    for (int q = 0; q < 8; q++) w8[q] = neg ? t8[q] : w8[q];
-    signed_digit_entries<C, WMAX>(w8, neg ? 0x80000000u : 0u, c, W, f);
+    uint32_t f8[8];
+    scalar_fold<S>(scalar, f8);
+    folded_signed_digits<WMAX, C>(f8, c, W, f);
 }
 
 }  // namespace halo

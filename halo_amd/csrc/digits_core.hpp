@@ -1,6 +1,6 @@
 // Signed-window recoding of a 256-bit integer into the MSM's sort entries: the arithmetic core of
 // digits.hpp.  Free of HIP types and of the field code, so a plain C++17 compiler builds it
-// (tests/test_digits_core.py); hipcc compiles the same text for the device.
+// (tests/test_digits_core.py, tests/test_digits_two_step.py); hipcc compiles the same text for the device.
 #pragma once
 #include <cstdint>
 
@@ -34,6 +34,36 @@ HALO_DIGITS_FN uint32_t digits_entry(uint32_t raw, uint32_t& carry, uint32_t hal
     const uint32_t m = 0u - carry;
     const uint32_t mag = (v ^ m) + ((full + 1u) & m);
     return (mag - 1u) | ((carry << 31) ^ flip);
+}
+
+// The recoding in two steps, so that a scalar's conversion and fold are done once and its windows cut
+// wherever they are needed (the fused first sort pass: the histogram kernel folds and stores, the
+// scatter loads and cuts).
+// Step one, digits_fold: the canonical integer s < p in w8 (p8: the modulus' words) becomes
+// min(s, p - s) <= (p - 1) / 2 < 2^254, with the fold's sign in the spare bit 255: set when p - s < s, i.e. when
+// p - s was taken and every digit's sign is to be inverted (s P = -(p - s) P).  32 B, as the scalar.
+// Step two, digits_unfold: the folded integer back in w8 and the flip (0 or 0x80000000) as
+// signed_digit_entries takes them.
+HALO_DIGITS_FN void digits_fold(uint32_t (&w8)[8], const uint32_t (&p8)[8]) {
+    // t = p - s, and the borrow of t - s: set when p - s < s
+    uint32_t t8[8];
+    int64_t br = 0, lt = 0;
+    HALO_DIGITS_UNROLL
+    for (int q = 0; q < 8; q++) {
+        const int64_t d = (int64_t)p8[q] - (int64_t)w8[q] + br;
+        t8[q] = (uint32_t)d;
+        br = d >> 32;
+        lt = ((int64_t)t8[q] - (int64_t)w8[q] + lt) >> 32;
+    }
+    const bool neg = lt != 0;
+    HALO_DIGITS_UNROLL
+    for (int q = 0; q < 8; q++) w8[q] = neg ? t8[q] : w8[q];
+    w8[7] |= neg ? 0x80000000u : 0u;
+}
+HALO_DIGITS_FN uint32_t digits_unfold(uint32_t (&w8)[8]) {
+    const uint32_t flip = w8[7] & 0x80000000u;
+    w8[7] &= 0x7fffffffu;
+    return flip;
 }
 
 // The W signed c-bit digits of the integer in w8 (8 words of 32 bits, least significant first; the

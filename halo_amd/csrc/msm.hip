@@ -164,7 +164,7 @@ __device__ __forceinline__ void acc_chunk(size_t t, uint32_t cnt, const uint32_t
         if (POS != 0 && k != cur) {  // bucket boundary inside the chunk
             for (uint32_t b = cur + 1; b <= k; b++) bstart[b] = e;
             if (!first_done) {
-                partial_store(first + PARTIAL_U4 * t, xyzz_run_out(acc, sneg));
+                partial_store(first + PARTIAL_U4 * t, acc, sneg);  // as it stands (curve.hpp, chunk partials)
                 first_done = true;
             } else {
                 xyzz_store(bucket_sums + 8 * (size_t)cur, xyzz_settle(xyzz_run_out(acc, sneg)));
@@ -211,7 +211,7 @@ __device__ __forceinline__ void acc_chunk(size_t t, uint32_t cnt, const uint32_t
     step(e++, std::integral_constant<int, 0>{});
     if (e < end) step(e++, std::integral_constant<int, 1>{});
     for (; e < end; e++) step(e, std::integral_constant<int, 2>{});
-    partial_store((first_done ? last : first) + PARTIAL_U4 * t, xyzz_run_out(acc, sneg));
+    partial_store((first_done ? last : first) + PARTIAL_U4 * t, acc, sneg);
     if (end == cnt)
         for (uint32_t b = cur + 1; b <= NB; b++) bstart[b] = cnt;
 }

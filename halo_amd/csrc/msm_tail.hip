@@ -69,12 +69,12 @@ __global__ __launch_bounds__(256) void k_merge(const uint32_t* bstart, const uin
     }
     XYZZ<F> acc = xyzz_id<F>();
     if (active) {
-        // this lane's sources: chunks (t0, t1] split in LN contiguous parts [t, tb]
-        // (measured and left out: counting chunk t0's partial as lane 0's first source, so that 16 sources
-        // split 7 + 7 additions instead of 8 + 6 -- inside the noise of the step, DESIGN_HISTORY.md)
-        const uint32_t total = t1 - t0, per = (total + LN - 1) / LN;
-        uint32_t t = t0 + 1 + j * per;
-        const uint32_t tb = min(t1, t0 + (j + 1) * per);
+        // this lane's sources: chunks [t0, t1] split in LN contiguous parts [t, tb].  Chunk t0's partial
+        // counts as lane 0's first source (it starts that lane's sum below), so 16 sources split into
+        // 7 + 7 additions, not 8 + 6: the wave executes the longest lane's chain
+        const uint32_t total = t1 - t0 + 1, per = (total + LN - 1) / LN;
+        uint32_t t = t0 + j * per + (j == 0 ? 1u : 0u);
+        const uint32_t tb = min(t1, t0 + (j + 1) * per - 1);
         constexpr uint32_t G2 = MSM_GROUP * MSM_GROUP;
         auto next_src = [&]() -> const uint4* {
             const uint4* src;

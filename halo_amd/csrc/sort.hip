@@ -48,8 +48,11 @@ constexpr size_t RS_STAGE_BYTES = 2 * 4 * RS_THREADS * 16;  // k_rs_scatter's ke
 constexpr uint32_t RS_NONE = 0xffffffffu;
 
 // The scalars of a fused first pass: P outputs of n scalars each (output p at s[p], keys offset by p B)
+// folded: the scalars after the recoding's first step (digits.hpp scalar_fold), 32 B each at 2 (p n + i):
+// written by k_rs_hist_sc, read by the fused k_rs_scatter, so a scalar is converted and folded once
 struct RsScalars {
     const uint4* s[8] = {};
+    uint4* folded = nullptr;
     uint32_t n = 0, P = 1, B = 0;
 };
 // (output p of the global scalar g and its scalar's address: a select chain, not a dynamic index into
@@ -248,6 +251,8 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_hist(RsIn in, uint32_t ntiles
 // from the scalars here instead of being written by k_digits and read back (32 B of scalar per
 // W = 15 entries instead of 2 x 4 B per entry).  Thread = one scalar, round = window: a tile is
 // RS_THREADS scalars x W windows.  Entry key = |d| - 1, value = (w n + i) | sign, as k_digits + pass 0.
+// The recoding's first step (to canonical words, the fold to min(s, p - s)) runs here only: the folded
+// scalar goes to sc.folded (32 B, as much as the scalar read), and the scatter cuts its windows from that.
 // (P > 1 outputs: key p B + |d| - 1 has the same low byte as |d| - 1 only when B is a multiple of 256,
 // which msm_radix_sort's check of the fused arguments requires)
 // C: the window width when it is one of the widths the resident SRS copies use (16, 17: the
@@ -262,8 +267,11 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_hist_sc(const RsScalars sc, i
     __syncthreads();
     const uint32_t g = blockIdx.x * RS_THREADS + threadIdx.x;
     if (g < sc.P * sc.n) {
-        uint32_t p, i;
-        scalar_signed_digits<S, 0, C>(rs_scalar(sc, g, p, i), c, W, [&](int, uint32_t d) {
+        uint32_t p, i, f8[8];
+        scalar_fold<S>(rs_scalar(sc, g, p, i), f8);
+        sc.folded[2 * (size_t)g] = make_uint4(f8[0], f8[1], f8[2], f8[3]);
+        sc.folded[2 * (size_t)g + 1] = make_uint4(f8[4], f8[5], f8[6], f8[7]);
+        folded_signed_digits<0, C>(f8, c, W, [&](int, uint32_t d) {
             if (d != DIGIT_NONE) atomicAdd(&h[d & 255u], 1u);
         });
     }
@@ -274,8 +282,8 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_hist_sc(const RsScalars sc, i
 // Each wave owns a contiguous eighth of the tile (1024 entries, 16 rounds of 64), so ranking is
 // wave-local (ballots + a wave-private LDS run counter per digit) and the workgroup needs only
 // three barriers: after the per-wave histograms, after the prefix, after staging.
-// SF: void, or the scalar field of a fused first pass (k_rs_hist_sc's entries, in.sc != null), with
-// its window width C as in k_rs_hist_sc
+// SF: void, or the scalar field of a fused first pass (the scalars k_rs_hist_sc folded, in.sc.folded),
+// with its window width C as in k_rs_hist_sc
 template <int BITS, class SF = void, bool PASS0 = false, int C = 0>
 __global__ __launch_bounds__(RS_THREADS) void k_rs_scatter(RsIn in, const uint32_t* tile_off, const uint32_t* chunk_off,
                                                            uint32_t* keys_out, uint32_t* vals_out) {
@@ -314,10 +322,12 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_scatter(RsIn in, const uint32
         }
         const uint32_t g = blockIdx.x * RS_THREADS + tid;
         if (g < in.sc.P * in.sc.n) {
-            uint32_t p, i;
-            const uint4* src = rs_scalar(in.sc, g, p, i);
+            // (g = p n + i: output p's scalar i, folded by k_rs_hist_sc)
+            const uint32_t p = in.sc.P == 1 ? 0u : g / in.sc.n, i = g - p * in.sc.n;
+            const uint4 lo = in.sc.folded[2 * (size_t)g], hi = in.sc.folded[2 * (size_t)g + 1];
+            const uint32_t f8[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
             const uint32_t koff = p * in.sc.B;
-            scalar_signed_digits<SF, R, C>(src, in.c, in.W, [&](int w, uint32_t d) {
+            folded_signed_digits<R, C>(f8, in.c, in.W, [&](int w, uint32_t d) {
                 // (no branch: K and V of a zero digit are never read, validmask guards every use)
                 K[w] = koff + (d & 0x7fffffffu);
                 V[w] = ((uint32_t)w * in.sc.n + i) | (d & 0x80000000u);
@@ -609,6 +619,7 @@ int msm_radix_sort(const uint32_t* digits, size_t E, size_t npw, uint32_t B, uin
     const size_t nchmax = (ntmax + RS_CH - 1) / RS_CH;
     HALO_CHECK(S.offs.reserve(nchmax * RS_BINS_MAX * 4));
     HALO_CHECK(S.count.reserve(16));
+    if (fused) HALO_CHECK(S.folded.reserve(std::max<size_t>(nsc, 1) * 32));
     // the last-arriver counters start at zero and are reset by their last arrivers
     // (a reallocation may return the freed address: the capacity, not the pointer, tells)
     const size_t ctr_had = S.ctr.bytes;
@@ -634,6 +645,7 @@ int msm_radix_sort(const uint32_t* digits, size_t E, size_t npw, uint32_t B, uin
         if (fp) {
             for (int q = 0; q < 8; q++)
                 in.sc.s[q] = (const uint4*)(fused->P == 1 ? (q == 0 ? fused->scalars : nullptr) : fused->srcs[q]);
+            in.sc.folded = S.folded.as<uint4>();
             in.sc.n = (uint32_t)fused->n;
             in.sc.P = (uint32_t)fused->P;
             in.sc.B = B;

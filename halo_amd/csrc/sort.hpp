@@ -6,6 +6,7 @@ namespace halo {
 
 struct SortScratch {
     DevBuf keys[2], vals[2], hist, offs, count, scan_tmp, ctr;
+    DevBuf folded;  // fused first pass: 32 B per scalar, the recoding's first step (grow-only like the rest)
 };
 
 // Exclusive scan of n u32 values: out[0..n) exclusive prefix, out[n] = total.
@@ -19,7 +20,8 @@ int device_exclusive_scan(const uint32_t* in, size_t n, uint32_t* out, DevBuf& t
 // key.  Fills bstart[0..NB] when bstart is not null (bucket b's entries are [bstart[b], bstart[b+1])
 // of the sorted arrays).
 // Fused first pass (window-shifted MSM, one bucket set, W <= 16): the entries come from the scalars
-// (digits.hpp recoding) instead of a digit array; `digits` is then unused.  P > 1 outputs (the IPA's
+// (digits.hpp recoding: converted and folded once, by the histogram kernel, into SortScratch::folded, from
+// which the scatter cuts the windows) instead of a digit array; `digits` is then unused.  P > 1 outputs (the IPA's
 // L / R pair MSM, msm_srs_pairs): output p's n scalars at srcs[p], its keys offset by p 2^(c-1) and its
 // values w n + i as for one output -- the layout k_digits_multi + a plain first pass produce.
 struct RsFused {

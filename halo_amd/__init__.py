@@ -8,7 +8,9 @@ reference's names, argument meaning and assertion messages:
                          crates/group/src/pp.rs     (PublicParams: resident SRS)
     halo_amd.poly     -- crates/group/src/poly.rs   (Domain, Evals: NTT / iNTT wrappers)
     halo_amd.pedersen -- crates/accumulation/src/pedersen.rs (commit)
-    halo_amd.pcdl     -- crates/accumulation/src/pcdl.rs     (commit, open_without_eval round loop)
+    halo_amd.pcdl     -- crates/accumulation/src/pcdl.rs     (commit, open_without_eval round loop,
+                         succinct_check and check: the verifier's scalar multiplications as one batch)
+    halo_amd.acc      -- crates/accumulation/src/acc.rs      (common_subroutine, prover, verifier, decider)
     halo_amd.schnorr  -- crates/schnorr/src/lib.rs (hash_message, PublicKey::verify) and the inner
                          Poseidon sponge of crates/poseidon, as batches of independent items
 
@@ -18,4 +20,4 @@ without the HIP library or a GPU every call raises.
 """
 from . import _lib  # noqa: F401
 
-__all__ = ["_lib", "group", "poly", "pedersen", "pcdl", "schnorr"]
+__all__ = ["_lib", "group", "poly", "pedersen", "pcdl", "acc", "schnorr"]

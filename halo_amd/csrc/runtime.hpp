@@ -123,6 +123,7 @@ struct DeviceState {
     uint64_t poseidon_ver[2] = {0, 0};
     DevBuf schnorr_gtab[2];  // per curve: d G and phi(d G), 1 <= d <= 8, XYZZ (the fixed-base table of s G)
     DevBuf schnorr_e;        // the challenges of a verification batch (canonical words)
+    DevBuf lincomb_terms;    // the terms of a batch of linear combinations (lincomb.hip): packed XYZZ, then a byte each
     // ScratchUse state: completion event of the last scratch user and its stream
     hipEvent_t scratch_ev = nullptr;
     hipStream_t scratch_last = nullptr;

@@ -1,4 +1,5 @@
-"""Mirror of crates/accumulation/src/pcdl.rs (commit + the IPA round loop) on the MI355X backend.
+"""Mirror of crates/accumulation/src/pcdl.rs (commit, the IPA round loop, succinct_check and check) on the
+MI355X backend.
 
 The Fiat-Shamir transcript (Poseidon sponge, crates/poseidon) stays with the caller: the round loop
 of ``open_without_eval`` (pcdl.rs:404-438) asks a ``challenge(xi_prev, L, R) -> xi`` callable for
@@ -7,7 +8,7 @@ each round's challenge, exactly where the reference calls ``transcript.challenge
 from __future__ import annotations
 
 import ctypes
-from typing import Callable
+from typing import Callable, NamedTuple
 
 import numpy as np
 
@@ -314,6 +315,19 @@ class HPoly:
         H.check(H.load().halo_hpoly_coeffs(self.field, H.ptr(self.xis), len(self.xis), H.ptr(out)))
         return out
 
+    def eval(self, z) -> np.ndarray:  # noqa: A003
+        """HPoly::eval (pcdl.rs:222-235): lg n products on the host."""
+        r = _SCALAR[self.curve]
+        r_inv = pow(1 << 256, -1, r)
+        x = [_ark_int(v) * r_inv % r for v in self.xis]
+        zi = _ark_int(z) * r_inv % r
+        lg_n = len(x) - 1
+        v = (1 + x[lg_n] * zi) % r
+        for i in range(1, lg_n):
+            zi = zi * zi % r
+            v = v * (1 + x[lg_n - i] * zi) % r
+        return _ark_limbs(v * (1 << 256) % r)
+
     @staticmethod
     def combine(hs: list["HPoly"], alphas) -> np.ndarray:
         """sum_i alphas[i] * h_i(X) (acc.rs:89), trimmed like DensePolynomial."""
@@ -336,6 +350,162 @@ def decider_commit(xis, d: int, curve="pallas") -> np.ndarray:
     out = np.zeros(8, dtype=np.uint64)
     H.check(H.load().halo_pcdl_decider_commit(_curve(curve), H.ptr(x), len(x), d, H.ptr(out)))
     return out
+
+
+class CheckFailed(Exception):
+    """A verifier's ``ensure!`` failed (pcdl.rs:494,547,580; acc.rs:154,207-210): the message is the
+    reference's.  ``index``: the failing instance of a batch (None for a single check)."""
+
+    def __init__(self, msg: str, index: int | None = None):
+        super().__init__(msg if index is None else f"{msg} (instance {index})")
+        self.msg = msg
+        self.index = index
+
+
+class Instance(NamedTuple):
+    """pcdl.rs Instance: ((C, d, z, v), pi), pi the EvalProof dict of ``open`` (Ls, Rs, U, c, C_bar, w_prime)."""
+    C: np.ndarray
+    d: int
+    z: np.ndarray
+    v: np.ndarray
+    pi: dict
+
+
+SUCCINCT_MSG = "C_(log_n) \u2260 CM.Commit_\u03a3(c || v')"
+DECIDER_MSG = "U \u2260 CM.Commit(ck, h_vec)"
+
+
+def _ark_int(x) -> int:
+    x = np.asarray(x, dtype=np.uint64).reshape(4)
+    return int(x[0]) | int(x[1]) << 64 | int(x[2]) << 128 | int(x[3]) << 192
+
+
+def _ark_limbs(v: int) -> np.ndarray:
+    return np.array([(v >> (64 * i)) & (2**64 - 1) for i in range(4)], dtype=np.uint64)
+
+
+def _ark_neg(x, cid: int) -> np.ndarray:
+    """-x for an ark Montgomery scalar (the Montgomery form is linear)."""
+    return _ark_limbs((_SCALAR[cid] - _ark_int(x)) % _SCALAR[cid])
+
+
+def point_lincomb(pts, scalars, add=None, curve="pallas") -> np.ndarray:
+    """out[i] = add[i] + sum_j scalars[i, j] pts[i, j] for k items of t terms (halo_point_lincomb_batch):
+    pts (k, t, 8) WrappedPoints, scalars (k, t, 4) ark scalars, add (k, 8) or None.  Returns (k, 8)."""
+    H.ensure_device()
+    p = np.ascontiguousarray(np.asarray(pts, dtype=np.uint64))
+    k, t = p.shape[0], p.shape[1]
+    sc = np.ascontiguousarray(np.asarray(scalars, dtype=np.uint64).reshape(k, t, 4))
+    a = np.ascontiguousarray(np.asarray(add, dtype=np.uint64).reshape(k, 8)) if add is not None else None
+    out = np.zeros((k, 8), dtype=np.uint64)
+    H.check(H.load().halo_point_lincomb_batch(_curve(curve), H.ptr(a), H.ptr(p) if t else None, H.ptr(sc) if t else None,
+                                              k, t, H.ptr(out)))
+    return out
+
+
+def succinct_check_verdicts(C_primes, d: int, zs, vs, xis, Ls, Rs, Us, cs, curve="pallas") -> np.ndarray:
+    """halo_pcdl_succinct_check_batch: steps 5-10 of succinct_check for k instances of degree bound d given
+    their challenges xis (k, lg n + 1).  Returns k bytes, 1 where C_(lg n) == c U + v' H'."""
+    H.ensure_device()
+    Cp = H.point_array(C_primes)
+    k = len(Cp)
+    lg = (d + 1).bit_length() - 1
+    ok = np.zeros(k, dtype=np.uint8)
+    H.check(H.load().halo_pcdl_succinct_check_batch(
+        _curve(curve), d, k, H.ptr(Cp), H.ptr(H.fe_array(zs, k)), H.ptr(H.fe_array(vs, k)),
+        H.ptr(H.fe_array(xis, k * (lg + 1))), H.ptr(H.point_array(Ls)) if lg else None,
+        H.ptr(H.point_array(Rs)) if lg else None, H.ptr(H.point_array(Us)), H.ptr(H.fe_array(cs, k)), H.ptr(ok)))
+    return ok
+
+
+def succinct_check_many(instances, transcripts, curve="pallas"):
+    """pcdl::succinct_check (pcdl.rs:483-554) for many instances at once.  instances: (C, d, z, v, pi) each
+    (``Instance``); transcripts: one fresh PCDL sponge per instance (pcdl.rs:496), with the reference's
+    interface.  Every challenge is derived on the host in the reference's absorb order; the hiding
+    instances' C' = C + alpha C_bar - w' S come from one halo_point_lincomb_batch call and all verdicts
+    from one halo_pcdl_succinct_check_batch call per distinct d.  Returns [(HPoly, U)]; raises CheckFailed
+    naming the first failing instance."""
+    from .group import PublicParams
+    H.ensure_device()
+    cid = _curve(curve)
+    insts = [Instance(*q) for q in instances]
+    ts = list(transcripts)
+    if len(ts) != len(insts):
+        raise ValueError("succinct_check_many needs one PCDL transcript per instance")
+    D = PublicParams.len(cid) - 1
+    for i, q in enumerate(insts):
+        n = q.d + 1
+        if n & (n - 1) or n == 0:
+            raise H.HaloAssertion(4, f"n ({n}) is not a power of two")
+        if q.d > D:
+            raise CheckFailed("d was larger than D!", i)
+    zs = [H.fe_array(q.z, 1)[0] for q in insts]
+    vs = [H.fe_array(q.v, 1)[0] for q in insts]
+    Cs = [H.point_array(q.C).reshape(8) for q in insts]
+    # 3-4. alpha and C' of the hiding instances (pcdl.rs:506-515)
+    C_primes = list(Cs)
+    hid = [i for i, q in enumerate(insts) if q.pi.get("C_bar") is not None]
+    if hid:
+        S, _ = PublicParams.sh(cid)
+        pts, sc = [], []
+        for i in hid:
+            pi = insts[i].pi
+            C_bar = H.point_array(pi["C_bar"]).reshape(8)
+            ts[i].absorb_g([Cs[i], C_bar])
+            ts[i].absorb_fr([zs[i], vs[i]])
+            alpha = np.ascontiguousarray(ts[i].challenge(), dtype=np.uint64)
+            pts.append([C_bar, S])
+            sc.append([alpha, _ark_neg(pi["w_prime"], cid)])
+        out = point_lincomb(np.array(pts), np.array(sc), add=np.array([Cs[i] for i in hid]), curve=cid)
+        for i, cp in zip(hid, out):
+            C_primes[i] = cp
+    # 5, 7.a the challenges xi_0 .. xi_lg_n (pcdl.rs:518-534)
+    xis = []
+    for i, q in enumerate(insts):
+        t = ts[i]
+        lg = (q.d + 1).bit_length() - 1
+        Ls, Rs = H.point_array(q.pi["Ls"]), H.point_array(q.pi["Rs"])
+        if len(Ls) != lg or len(Rs) != lg:
+            raise ValueError(f"instance {i}: the proof has {len(Ls)} rounds, d = {q.d} needs {lg}")
+        t.absorb_g([C_primes[i]])
+        t.absorb_fr([zs[i], vs[i]])
+        x = [np.ascontiguousarray(t.challenge(), dtype=np.uint64)]
+        for j in range(lg):
+            t.absorb_fr([x[j]])
+            t.absorb_g([Ls[j], Rs[j]])
+            x.append(np.ascontiguousarray(t.challenge(), dtype=np.uint64))
+        xis.append(np.stack(x))
+    # 6, 7.b, 9, 10 on the device, one call per degree bound
+    ok = np.zeros(len(insts), dtype=np.uint8)
+    for d in sorted({q.d for q in insts}):
+        idx = [i for i, q in enumerate(insts) if q.d == d]
+        ok[idx] = succinct_check_verdicts(
+            np.stack([C_primes[i] for i in idx]), d, np.stack([zs[i] for i in idx]), np.stack([vs[i] for i in idx]),
+            np.concatenate([xis[i] for i in idx]),
+            np.concatenate([H.point_array(insts[i].pi["Ls"]) for i in idx]) if d else None,
+            np.concatenate([H.point_array(insts[i].pi["Rs"]) for i in idx]) if d else None,
+            np.stack([H.point_array(insts[i].pi["U"]).reshape(8) for i in idx]),
+            np.stack([H.fe_array(insts[i].pi["c"], 1)[0] for i in idx]), curve=cid)
+    for i in range(len(insts)):
+        if not ok[i]:
+            raise CheckFailed(SUCCINCT_MSG, i)
+    return [(HPoly(xis[i], cid), H.point_array(q.pi["U"]).reshape(8).copy()) for i, q in enumerate(insts)]
+
+
+def succinct_check(C, d: int, z, v, pi: dict, transcript, curve="pallas"):
+    """pcdl::succinct_check (pcdl.rs:483-554) under the caller's fresh PCDL sponge.  Returns (HPoly, U);
+    raises CheckFailed("C_(log_n) != CM.Commit_Sigma(c || v')", in the reference's spelling)."""
+    try:
+        return succinct_check_many([Instance(C, d, z, v, pi)], [transcript], curve)[0]
+    except CheckFailed as e:
+        raise CheckFailed(e.msg) from None
+
+
+def check(C, d: int, z, v, pi: dict, transcript, curve="pallas") -> None:
+    """pcdl::check (pcdl.rs:563-583): succinct_check, then U == CM.Commit(ck, h_vec) over Gs[0..d]."""
+    h, U = succinct_check(C, d, z, v, pi, transcript, curve)
+    if not np.array_equal(decider_commit(h.xis, d, curve), U):
+        raise CheckFailed(DECIDER_MSG)
 
 
 def trace_commit_batch(evals, d: int, curve="pallas", want_coeffs: bool = False):

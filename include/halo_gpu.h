@@ -447,6 +447,37 @@ int halo_schnorr_verify_batch(halo_curve_t curve, const halo_wrapped_point_t* pk
 int halo_schnorr_verify_batch_dev(halo_curve_t curve, const void* d_pk, const void* d_R, const void* d_s,
                                   const void* d_msgs, size_t msg_len, size_t k, void* d_ok, void* stream);
 
+/* ------------------------------------------------------------------ the PCDL verifier
+ * k linear combinations of t terms each, out[i] = add[i] + sum_{j < t} scalars[i t + j] pts[i t + j]
+ * (row-major k x t; add NULL: no addend): one variable-base ladder per term over its GLV halves, then one
+ * sum per item (equal, opposite and identity partial sums included).  Scalars of `curve` (ark), below the
+ * modulus, else HALO_EINVAL.  A term point or an addend that is neither the identity (0, 0) nor on the
+ * curve makes its item invalid, and the item's result is (0, 0): the reference's Affine type cannot hold
+ * such a point (the rule of halo_schnorr_verify_batch).  t = 0 returns the addends.  The hiding pre-step
+ * of the succinct check, C' = C + alpha C_bar - w' S (pcdl.rs:506-515), is one call with t = 2 whose
+ * affine result goes back to the caller's transcript. */
+int halo_point_lincomb_batch(halo_curve_t curve, const halo_wrapped_point_t* add, const halo_wrapped_point_t* pts,
+                             const halo_fe_t* scalars, size_t k, size_t t, halo_wrapped_point_t* out);
+/* The same over device pointers, asynchronous on `stream`: d_out_xyzz receives k packed XYZZ points (128 B
+ * each, halo_ipa_round_lr_dev's format; convert with halo_xyzz_to_wrapped), d_is_identity (k bytes, may be
+ * NULL) 1 where item i is valid and its sum is the identity.  An invalid item -- here also one with a
+ * scalar that is not below the modulus -- gives the identity and byte 0. */
+int halo_point_lincomb_batch_dev(halo_curve_t curve, const void* d_add, const void* d_pts, const void* d_scalars,
+                                 size_t k, size_t t, void* d_out_xyzz, void* d_is_identity, void* stream);
+/* Steps 5-10 of pcdl::succinct_check (pcdl.rs:517-550) for k instances of one degree bound d, given the
+ * challenges the caller's transcript derived: C_prime[i] (C, or C + alpha C_bar - w' S when hiding), z[i],
+ * v[i], xis[i (lg n + 1) + j] = xi_j, Ls / Rs[i lg n + j], U[i], c[i].  The host forms xi_(j+1)^-1, h(z)
+ * (HPoly::eval, pcdl.rs:222-235) and e = xi_0 (v - c h(z)); the device sums, per instance,
+ * C' + sum_j (xi_(j+1)^-1 L_j + xi_(j+1) R_j) + e H - c U over the resident SRS's H in one lincomb launch
+ * of t = 2 lg n + 2 terms.  ok_out[i] = 1 iff every point of instance i is valid and that sum is the
+ * identity, i.e. C_(lg n) == c U + v' H' (pcdl.rs:547-550).  Before any device work: HALO_ENOTPOW2
+ * "n ({n}) is not a power of two", HALO_ESRSRANGE "d was larger than D!", HALO_EINVAL for a null pointer,
+ * a scalar not below the modulus or a zero xi_(j+1) (the reference unwraps its inverse).  k = 0: HALO_OK. */
+int halo_pcdl_succinct_check_batch(halo_curve_t curve, size_t d, size_t k, const halo_wrapped_point_t* C_prime,
+                                   const halo_fe_t* z, const halo_fe_t* v, const halo_fe_t* xis,
+                                   const halo_wrapped_point_t* Ls, const halo_wrapped_point_t* Rs,
+                                   const halo_wrapped_point_t* U, const halo_fe_t* c, uint8_t* ok_out);
+
 /* ------------------------------------------------------------------ measurement hooks
  * When enabled, the library brackets its dominant kernels (MSM bucket accumulation, NTT passes)
  * with hipEvents on the stream they run on; halo_profile_read returns the number of launches and

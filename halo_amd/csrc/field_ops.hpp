@@ -1,4 +1,4 @@
-// What field_ops.hip offers the IPA sessions (ipa.hip): the pcdl_* steps on device buffers.
+// What field_ops.hip offers the hiding open (pcdl_open.hip): the pcdl_* steps on device buffers.
 #pragma once
 #include "runtime.hpp"
 

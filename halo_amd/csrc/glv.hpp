@@ -2,8 +2,8 @@
 //
 // phi(x, y) = (beta x, y) = lambda (x, y); a scalar k splits as k = k1 + lambda k2 (mod r) with
 // |k1|, |k2| < 2^128 using the short lattice basis (a_i, b_i) (consts.hpp, gen_consts.py), so k P
-// needs ~128 doublings instead of 255.  Used by the IPA fold (shared challenge, ipa.hip) and by the
-// MSM's digit recoding when bases are not window-shifted (msm.hip).
+// needs ~128 doublings instead of 255.  Used by the IPA fold (shared challenge, ipa.hip), the
+// multiples-table sums (tail.hip) and by the MSM's digit recoding when bases are not window-shifted (msm.hip).
 #pragma once
 #include "fields.hpp"
 

@@ -1,4 +1,4 @@
-// The MSM's internal interface: the drivers of msm.hip, the small-table and tiny MSMs of ipa.hip and
+// The MSM's internal interface: the drivers of msm.hip, the small-table and tiny MSMs of tail.hip and
 // the reduction tail of msm_tail.hip.
 #pragma once
 #include "msm_plan.hpp"
@@ -86,7 +86,7 @@ int msm_shared_batch(DeviceState* st, int curve, const void* bases_int, const vo
                      void* out, bool xyzz_out, BatchScratch& S, hipStream_t s, size_t shift_stride = 0, int c_s = 0);
 // The window-shifted copies 2^(c w) G_i, w in [w_lo, w_hi), that the SRS drivers above read (srs.hip).
 int srs_precompute_windows(DeviceState* st, int curve, hipStream_t s, int c = 0, int w_lo = 0, int w_hi = 0);
-// Small MSM over the resident SRS prefix (1 <= n <= srs_small_max(), ipa.hip): every (point, 4-bit GLV
+// Small MSM over the resident SRS prefix (1 <= n <= srs_small_max(), tail.hip): every (point, 4-bit GLV
 // window) term is one entry of a per-SRS multiples table, then block trees with the hiding term
 // hide_scalar * S from the 2^i S table -- no sort, buckets or bucket reduction.  Stream-ordered on s;
 // writes one ark WrappedPoint to d_out_wrapped.
@@ -96,7 +96,7 @@ size_t srs_small_max();  // largest MSM on the table path (HALO_SRS_SMALL_N, def
 // min(srs_tab_n(), srs.n) points); stream s waits for its completion.  Shared by the small MSMs and
 // by IPA sessions whose tail rounds start on the unfolded SRS prefix.
 int srs_small_table(DeviceState* st, int curve, hipStream_t s);
-// MSM of n <= msm_tiny_max() caller points (internal affine) by GLV windows and one Horner (ipa.hip):
+// MSM of n <= msm_tiny_max() caller points (internal affine) by GLV windows and one Horner (tail.hip):
 // packed XYZZ to out_xyzz (device); scratch >= 4 KiB of device memory.  Stream-ordered on s.
 int msm_tiny(int curve, const void* bases_int, const void* scalars_ark, size_t n, void* scratch, void* out_xyzz,
              hipStream_t s);

@@ -20,6 +20,7 @@
 
 #include "dispatch.hpp"
 #include "ntt.hpp"
+#include "points.hpp"
 #include "runtime.hpp"
 
 namespace halo {
@@ -827,11 +828,6 @@ int fold_device_dispatch(int field, const void* d_in, size_t len, void* d_out, s
 }  // namespace halo
 
 using namespace halo;
-
-static int check_field(halo_field_t f) {
-    if (f != HALO_FP && f != HALO_FQ) return set_error(HALO_EINVAL, "unknown field id %d", (int)f);
-    return HALO_OK;
-}
 
 // host -> device NTT helper: in/out host arrays of N elements (in may be longer: folded)
 static int ntt_host(halo_field_t field, const halo_fe_t* in, size_t len, unsigned logn, int inverse, halo_fe_t* out) {

@@ -1,4 +1,4 @@
-// What ntt.hip offers the other translation units (the IPA's polynomial products, ipa.hip).
+// What ntt.hip offers the other translation units (the polynomial products and trace commitments, poly.hip).
 #pragma once
 #include <vector>
 

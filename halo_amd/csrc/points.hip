@@ -80,6 +80,11 @@ int check_curve(halo_curve_t c) {
     return HALO_OK;
 }
 
+int check_field(halo_field_t f) {
+    if (f != HALO_FP && f != HALO_FQ) return set_error(HALO_EINVAL, "unknown field id %d", (int)f);
+    return HALO_OK;
+}
+
 int d2h_point(int curve, const void* d_xyzz, halo_wrapped_point_t* out, hipStream_t s) {
     alignas(16) uint64_t buf[16];
     HALO_CHECK(copy_d2h(buf, d_xyzz, 128, s));

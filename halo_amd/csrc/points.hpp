@@ -8,6 +8,8 @@ namespace halo {
 
 // HALO_EINVAL (with the error set) unless c is HALO_PALLAS or HALO_VESTA
 int check_curve(halo_curve_t c);
+// HALO_EINVAL (with the error set) unless f is HALO_FP or HALO_FQ
+int check_field(halo_field_t f);
 
 // Host conversion of a 128-B packed XYZZ point (internal format, each coordinate < 2p) to an ark
 // WrappedPoint: one inversion in 4 x 64-bit Montgomery arithmetic on the CPU (identity -> (0, 0)).

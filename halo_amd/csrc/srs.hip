@@ -1,7 +1,7 @@
 // The resident SRS (the PublicParams provider, crates/group/src/pp.rs:26-94): everything that writes
 // or describes it.  Synthetic bases, the upload and the bincode decoder, the tables derived from the
 // points (the window-shifted copies 2^(c w) G_i and the hiding table 2^i S) and the halo_srs_* queries.
-// The MSMs that read it are in msm.hip, the multiples table of its prefix in ipa.hip.
+// The MSMs that read it are in msm.hip, the multiples table of its prefix in tail.hip.
 #include <algorithm>
 #include <vector>
 

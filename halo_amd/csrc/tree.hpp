@@ -1,5 +1,5 @@
 // Tree sums of XYZZ points across the lanes of a block (the MSM reduction tail, msm_tail.hip, and
-// the IPA's tail rounds, ipa.hip), in the arithmetic namespace of the including unit (fields.hpp).
+// the multiples-table sums, tail.hip), in the arithmetic namespace of the including unit (fields.hpp).
 #pragma once
 #include "curve.hpp"
 

@@ -162,7 +162,7 @@ def test_ntt_signed_products(field):
 
 
 # ---------------------------------------------------------------------------------------------
-# GLV halves for the IPA tail's signed 4-bit windows (ipa.hip tail_bias / tail_digit): a half k is
+# GLV halves for the IPA tail's signed 4-bit windows (tail.hpp tail_bias / tail_digit): a half k is
 # stored as |k| + 0x8888...8 in 128 bits, so |k| must stay below 2^128 - 0x8888...8 (~0.467 x 2^128).
 # ---------------------------------------------------------------------------------------------
 def _glv_consts():

@@ -5,7 +5,8 @@ The Fiat-Shamir sponges stay with the caller: ``new_transcript(label)`` returns 
 reference's interface (absorb_g, absorb_fr, challenge over WrappedPoints / ark scalars) for the label
 "ASDL" (one per common_subroutine, acc.rs:135) or "PCDL" (one per succinct check and per opening,
 pcdl.rs:336,496).  The m succinct checks of common_subroutine run as one batch on the device
-(pcdl.succinct_check_many).  An accumulator is the ``pcdl.Instance`` acc.q of the reference.
+(pcdl.succinct_check_many; with ``device_transcripts=True`` their PCDL sponges run there too,
+pcdl.succinct_check_device).  An accumulator is the ``pcdl.Instance`` acc.q of the reference.
 """
 from __future__ import annotations
 
@@ -24,9 +25,10 @@ def _alphas_dot_h(hs, alphas, z, cid: int) -> np.ndarray:
     return pcdl._ark_limbs(v * pow(1 << 256, -1, r) % r)  # the product of two Montgomery forms carries R twice
 
 
-def common_subroutine(qs, new_transcript, curve="pallas"):
+def common_subroutine(qs, new_transcript, curve="pallas", device_transcripts=False):
     """acc.rs:128-176.  Returns (C_bar, d, z, hs, alphas): hs the HPolys h_i and alphas the powers of alpha
-    (AccumulatedHPolys)."""
+    (AccumulatedHPolys).  device_transcripts: the PCDL sponges of the succinct checks run on the device
+    (pcdl.succinct_check_device); the ASDL sponge stays new_transcript's."""
     cid = _curve(curve)
     qs = [Instance(*q) for q in qs]
     m = len(qs)
@@ -38,7 +40,10 @@ def common_subroutine(qs, new_transcript, curve="pallas"):
     # instance of another degree bound ends the batch: a failing check before it is reported first.
     bad = next((i for i, q in enumerate(qs) if q.d != d), None)
     upto = m if bad is None else bad + 1
-    res = pcdl.succinct_check_many(qs[:upto], [new_transcript("PCDL") for _ in range(upto)], cid)
+    if device_transcripts:
+        res = pcdl.succinct_check_device(qs[:upto], cid)
+    else:
+        res = pcdl.succinct_check_many(qs[:upto], [new_transcript("PCDL") for _ in range(upto)], cid)
     if bad is not None:
         raise CheckFailed("d_i ≠ d", bad)
     hs = [h for h, _ in res]
@@ -64,11 +69,11 @@ def prover(qs, new_transcript, curve="pallas") -> Instance:
     return Instance(C_bar, d, z, v, pi)
 
 
-def verifier(qs, acc, new_transcript, curve="pallas") -> None:
+def verifier(qs, acc, new_transcript, curve="pallas", device_transcripts=False) -> None:
     """acc.rs:200-213."""
     cid = _curve(curve)
     acc = Instance(*acc)
-    C_bar_prime, d_prime, z_prime, hs, alphas = common_subroutine(qs, new_transcript, cid)
+    C_bar_prime, d_prime, z_prime, hs, alphas = common_subroutine(qs, new_transcript, cid, device_transcripts)
     if not np.array_equal(C_bar_prime, H.point_array(acc.C).reshape(8)):
         raise CheckFailed("C_bar' ≠ C_bar")
     if not np.array_equal(z_prime, H.fe_array(acc.z, 1)[0]):

@@ -13,6 +13,7 @@
 #include "dispatch.hpp"
 #include "glv.hpp"
 #include "host_mont.hpp"
+#include "lincomb.hpp"
 #include "points.hpp"
 #include "quad_ladder.hpp"
 #include "runtime.hpp"
@@ -27,23 +28,6 @@ constexpr int LINCOMB_TAB_U4 = 8 * 8;  // d P at d - 1 (1 <= d <= 8) per quad: X
 // Waves per SIMD the term kernel is compiled for: at 206 VGPRs it spills nothing; compiled for three it
 // spills 116 VGPRs and the 16 KB tables admit only 2.5, and it measured 16 % slower.
 constexpr int LINCOMB_TERM_WAVES = 2;
-
-// The ark limbs at p are below the modulus of S.
-template <class S>
-HALO_DEV bool ark_is_canonical(const uint4* p) {
-    const uint4 lo = p[0], hi = p[1];
-    const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-    bool below = false, decided = false;
-#pragma unroll
-    for (int i = 7; i >= 0; i--) {
-        const uint32_t m = (uint32_t)(S::MODULUS64[i >> 1] >> (32 * (i & 1)));
-        if (!decided && w[i] != m) {
-            below = w[i] < m;
-            decided = true;
-        }
-    }
-    return below;
-}
 
 // Term i = s_i P_i as packed XYZZ, ok[i] = 1; a P_i that is neither (0, 0) nor on the curve, or an s_i
 // that is not below the modulus, gives the identity and ok[i] = 0.  One aligned quad of lanes per term,
@@ -159,7 +143,6 @@ __global__ __launch_bounds__(LINCOMB_THREADS) void k_lincomb_sum(const uint4* __
 // host side
 // ---------------------------------------------------------------------------------------------
 static bool valid_curve(int c) { return c == HALO_PALLAS || c == HALO_VESTA; }
-constexpr size_t LINCOMB_MAX_ITEMS = 0x7fffffffu;  // one block per item
 
 // Scalar arithmetic of one curve on ark Montgomery limbs (host_mont.hpp), for the succinct check's
 // h(z) and e.  Inputs below the modulus.
@@ -222,8 +205,8 @@ static bool host_on_curve_or_id(int curve, const halo_wrapped_point_t& P) {
 
 // The two launches.  st->mu and a ScratchUse of `s` held by the caller (st->lincomb_terms is shared by the
 // calls on every stream).  k >= 1.
-static int lincomb_device(DeviceState* st, int curve, const void* d_add, const void* d_pts, const void* d_scalars, size_t k,
-                          size_t t, void* d_out, void* d_is_id, hipStream_t s) {
+int lincomb_device(DeviceState* st, int curve, const void* d_add, const void* d_pts, const void* d_scalars, size_t k,
+                   size_t t, void* d_out, void* d_is_id, hipStream_t s) {
     const size_t n = k * t;
     HALO_CHECK(st->lincomb_terms.reserve(std::max<size_t>(n, 1) * 129));
     uint4* terms = st->lincomb_terms.as<uint4>();

@@ -14,6 +14,7 @@
 #include "poseidon.hpp"
 #include "quad_ladder.hpp"
 #include "runtime.hpp"
+#include "sponge_launch.hpp"
 #include "tree.hpp"
 
 #include <cstring>
@@ -23,19 +24,6 @@ namespace halo {
 // ---------------------------------------------------------------------------------------------
 // hashing
 // ---------------------------------------------------------------------------------------------
-// Index of this lane's sponge and whether this lane reports its result.
-template <int LANES>
-HALO_DEV size_t sponge_index(bool& writer) {
-    if (LANES == 1) {
-        writer = true;
-        return (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    }
-    const size_t wave = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const unsigned lane = threadIdx.x & 63u;
-    writer = lane % 3u == 0 && lane != 63u;
-    return wave * poseidon::SPONGES_PER_WAVE_3 + (lane == 63u ? 20u : lane / 3u);
-}
-
 // k inner sponges: absorb row i of `in` (len ark elements), squeeze once.
 template <class F, int LANES>
 __global__ __launch_bounds__(256) void k_poseidon_hash(const uint32_t* __restrict__ params, const uint4* __restrict__ in,
@@ -232,7 +220,6 @@ static uint64_t g_poseidon_next = 1;
 
 static bool valid_field(int f) { return f == HALO_FP || f == HALO_FQ; }
 static bool valid_curve(int c) { return c == HALO_PALLAS || c == HALO_VESTA; }
-static int base_field(int curve) { return curve == HALO_PALLAS ? HALO_FQ : HALO_FP; }
 
 // ark Montgomery limbs (a 2^256 mod p, canonical) -> the kernels' form (a 2^261 mod p as nine 29-bit
 // limbs): five modular doublings on the host.  False when the input is not below p.
@@ -265,13 +252,13 @@ static bool ark_to_limbs(const uint64_t (&p)[4], const halo_fe_t& in, uint32_t* 
     return true;
 }
 
-static bool poseidon_params_set(int field) {
+bool poseidon_params_set(int field) {
     std::lock_guard<std::mutex> g(g_poseidon.mu);
     return g_poseidon.ver[field] != 0;
 }
 
 // This device's copy of the parameters of `field` (st->mu held).
-static int poseidon_device_params(DeviceState* st, int field, const uint32_t** out) {
+int poseidon_device_params(DeviceState* st, int field, const uint32_t** out) {
     std::lock_guard<std::mutex> g(g_poseidon.mu);
     if (st->poseidon_ver[field] != g_poseidon.ver[field]) {
         HALO_CHECK(st->poseidon[field].reserve(sizeof(g_poseidon.tab[field])));
@@ -290,20 +277,11 @@ static int poseidon_device_params(DeviceState* st, int field, const uint32_t** o
 // take 3.46 ms on 3121 three-lane waves against 2.72 ms on 1024 one-lane waves, and from there on the
 // one-lane layout stays 5-20 % ahead (its lanes are all busy and it has no crossbar traffic).  So: three
 // lanes while their waves number at most two per SIMD.  The poseidon_lanes tuning key pins either.
-static int poseidon_lanes(const DeviceState* st, size_t k) {
+int poseidon_lanes(const DeviceState* st, size_t k) {
     const long long t = tuning(TUNE_POSEIDON_LANES);
     if (t == 1 || t == 3) return (int)t;
     const size_t waves3 = (k + poseidon::SPONGES_PER_WAVE_3 - 1) / poseidon::SPONGES_PER_WAVE_3;
     return waves3 <= (size_t)8 * st->num_cu ? 3 : 1;
-}
-
-struct HashGrid {
-    unsigned blocks, threads;
-};
-static HashGrid hash_grid(size_t k, int lanes) {
-    const size_t waves = lanes == 1 ? (k + 63) / 64 : (k + poseidon::SPONGES_PER_WAVE_3 - 1) / poseidon::SPONGES_PER_WAVE_3;
-    const unsigned wpb = waves > 4096 ? 4 : 1;  // small batches spread one wave per block over the CUs
-    return {(unsigned)((waves + wpb - 1) / wpb), 64 * wpb};
 }
 
 static int poseidon_hash_device(DeviceState* st, int field, const void* d_in, size_t len, size_t k, void* d_out,

@@ -3,7 +3,9 @@ MI355X backend.
 
 The Fiat-Shamir transcript (Poseidon sponge, crates/poseidon) stays with the caller: the round loop
 of ``open_without_eval`` (pcdl.rs:404-438) asks a ``challenge(xi_prev, L, R) -> xi`` callable for
-each round's challenge, exactly where the reference calls ``transcript.challenge()``.
+each round's challenge, exactly where the reference calls ``transcript.challenge()``.  The verifier alone
+also exists without a caller's transcript: ``succinct_check_device`` / ``check_device`` derive the PCDL
+challenges of a batch of instances on the device (halo_pcdl_succinct_check_fs_batch).
 """
 from __future__ import annotations
 
@@ -504,6 +506,86 @@ def succinct_check(C, d: int, z, v, pi: dict, transcript, curve="pallas"):
 def check(C, d: int, z, v, pi: dict, transcript, curve="pallas") -> None:
     """pcdl::check (pcdl.rs:563-583): succinct_check, then U == CM.Commit(ck, h_vec) over Gs[0..d]."""
     h, U = succinct_check(C, d, z, v, pi, transcript, curve)
+    if not np.array_equal(decider_commit(h.xis, d, curve), U):
+        raise CheckFailed(DECIDER_MSG)
+
+
+def succinct_check_fs_verdicts(Cs, d: int, zs, vs, Ls, Rs, Us, cs, hiding=None, C_bars=None, w_primes=None,
+                               curve="pallas"):
+    """halo_pcdl_succinct_check_fs_batch: succinct_check of k raw instances of degree bound d, their transcripts
+    on the device.  hiding: k flags (None: no instance hides); C_bars (k, 8) and w_primes (k, 4) are read
+    where the flag is set.  Returns (ok, xis, alphas): k bytes, (k, lg n + 1, 4) challenges, (k, 4) alphas
+    (zero where the instance does not hide).  halo_poseidon_set_params must have installed the parameters
+    of the curve's base field."""
+    H.ensure_device()
+    C = H.point_array(Cs)
+    k = len(C)
+    lg = (d + 1).bit_length() - 1
+    ok = np.zeros(k, dtype=np.uint8)
+    xis = np.zeros((k, lg + 1, 4), dtype=np.uint64)
+    alphas = np.zeros((k, 4), dtype=np.uint64)
+    hid = cb = wp = None
+    if hiding is not None:
+        hid = np.ascontiguousarray(np.asarray(hiding, dtype=np.uint8).reshape(k))
+        cb, wp = H.point_array(C_bars), H.fe_array(w_primes, k)
+        assert len(cb) == k
+    H.check(H.load().halo_pcdl_succinct_check_fs_batch(
+        _curve(curve), d, k, H.ptr(C), H.ptr(H.fe_array(zs, k)), H.ptr(H.fe_array(vs, k)),
+        H.ptr(H.point_array(Ls)) if lg else None, H.ptr(H.point_array(Rs)) if lg else None, H.ptr(H.point_array(Us)),
+        H.ptr(H.fe_array(cs, k)), H.ptr(hid), H.ptr(cb), H.ptr(wp), H.ptr(xis), H.ptr(alphas), H.ptr(ok)))
+    return ok, xis, alphas
+
+
+def succinct_check_device(instances, curve="pallas"):
+    """succinct_check_many without transcripts: the device derives every challenge itself
+    (halo_pcdl_succinct_check_fs_batch, one call per distinct d).  Returns [(HPoly, U)]; raises CheckFailed
+    naming the first failing instance."""
+    from .group import PublicParams
+    H.ensure_device()
+    cid = _curve(curve)
+    insts = [Instance(*q) for q in instances]
+    D = PublicParams.len(cid) - 1
+    for i, q in enumerate(insts):
+        n = q.d + 1
+        if n & (n - 1) or n == 0:
+            raise H.HaloAssertion(4, f"n ({n}) is not a power of two")
+        if q.d > D:
+            raise CheckFailed("d was larger than D!", i)
+        lg = n.bit_length() - 1
+        if len(H.point_array(q.pi["Ls"])) != lg or len(H.point_array(q.pi["Rs"])) != lg:
+            raise ValueError(f"instance {i}: the proof has {len(q.pi['Ls'])} rounds, d = {q.d} needs {lg}")
+    ok = np.zeros(len(insts), dtype=np.uint8)
+    xis = [None] * len(insts)
+    zero_pt, zero_fe = np.zeros(8, dtype=np.uint64), np.zeros(4, dtype=np.uint64)
+    for d in sorted({q.d for q in insts}):
+        idx = [i for i, q in enumerate(insts) if q.d == d]
+        qs = [insts[i] for i in idx]
+        hid = [q.pi.get("C_bar") is not None for q in qs]
+        ok_d, xis_d, _ = succinct_check_fs_verdicts(
+            np.stack([H.point_array(q.C).reshape(8) for q in qs]), d, np.stack([H.fe_array(q.z, 1)[0] for q in qs]),
+            np.stack([H.fe_array(q.v, 1)[0] for q in qs]),
+            np.concatenate([H.point_array(q.pi["Ls"]) for q in qs]) if d else None,
+            np.concatenate([H.point_array(q.pi["Rs"]) for q in qs]) if d else None,
+            np.stack([H.point_array(q.pi["U"]).reshape(8) for q in qs]),
+            np.stack([H.fe_array(q.pi["c"], 1)[0] for q in qs]),
+            hiding=hid if any(hid) else None,
+            C_bars=np.stack([H.point_array(q.pi["C_bar"]).reshape(8) if h else zero_pt for q, h in zip(qs, hid)]),
+            w_primes=np.stack([H.fe_array(q.pi["w_prime"], 1)[0] if h else zero_fe for q, h in zip(qs, hid)]), curve=cid)
+        for j, i in enumerate(idx):
+            ok[i], xis[i] = ok_d[j], xis_d[j]
+    for i in range(len(insts)):
+        if not ok[i]:
+            raise CheckFailed(SUCCINCT_MSG, i)
+    return [(HPoly(xis[i], cid), H.point_array(q.pi["U"]).reshape(8).copy()) for i, q in enumerate(insts)]
+
+
+def check_device(C, d: int, z, v, pi: dict, curve="pallas") -> None:
+    """pcdl::check (pcdl.rs:563-583) with the transcript on the device: succinct_check_device, then
+    U == CM.Commit(ck, h_vec) over Gs[0..d]."""
+    try:
+        h, U = succinct_check_device([Instance(C, d, z, v, pi)], curve)[0]
+    except CheckFailed as e:
+        raise CheckFailed(e.msg) from None
     if not np.array_equal(decider_commit(h.xis, d, curve), U):
         raise CheckFailed(DECIDER_MSG)
 

@@ -477,6 +477,29 @@ int halo_pcdl_succinct_check_batch(halo_curve_t curve, size_t d, size_t k, const
                                    const halo_fe_t* z, const halo_fe_t* v, const halo_fe_t* xis,
                                    const halo_wrapped_point_t* Ls, const halo_wrapped_point_t* Rs,
                                    const halo_wrapped_point_t* U, const halo_fe_t* c, uint8_t* ok_out);
+/* pcdl::succinct_check (pcdl.rs:483-554) for k raw instances of one degree bound d: each instance's transcript
+ * (Sponge::new(Protocols::PCDL), outer_sponge.rs) runs on the device.  Per instance i: C[i], z[i], v[i],
+ * Ls/Rs[i lg n + j], U[i], c[i]; hiding (may be NULL: no instance hides) hiding[i] != 0 => C_bar[i], w_prime[i]
+ * are read (pcdl.rs:503-515), else ignored.  Optional outputs: xis_out[i (lg n + 1) + j] = xi_j (ark),
+ * alpha_out[i] (zero for a non-hiding instance).  ok_out[i] = 1 iff C_(lg n) == c U + v' H'.
+ * Needs the resident SRS with (S, H) and halo_poseidon_set_params for the curve's base field.  Before any
+ * device work: HALO_ENOTPOW2 "n ({n}) is not a power of two", HALO_EINVAL for a null required pointer, for
+ * hiding without C_bar and w_prime, for unset Poseidon parameters and for a z, v, c or read w' that is not
+ * below the modulus; then HALO_ESRSRANGE "d was larger than D!" or for a missing (S, H).  k = 0: HALO_OK.
+ * A point that is neither (0, 0) nor on the curve gives verdict 0 for its instance alone (that instance's
+ * xis_out row is then unspecified).  One deviation from the reference: a derived xi_(j+1) = 0 (probability
+ * about 2^-254), whose inverse the reference unwraps, gives verdict 0 here. */
+int halo_pcdl_succinct_check_fs_batch(halo_curve_t curve, size_t d, size_t k,
+        const halo_wrapped_point_t* C, const halo_fe_t* z, const halo_fe_t* v,
+        const halo_wrapped_point_t* Ls, const halo_wrapped_point_t* Rs,
+        const halo_wrapped_point_t* U, const halo_fe_t* c,
+        const uint8_t* hiding, const halo_wrapped_point_t* C_bar, const halo_fe_t* w_prime,
+        halo_fe_t* xis_out, halo_fe_t* alpha_out, uint8_t* ok_out);
+/* The same over device pointers, asynchronous on `stream`; no host wait, no host arithmetic.  Here a
+ * scalar that is not below the modulus also gives verdict 0 for its instance. */
+int halo_pcdl_succinct_check_fs_batch_dev(halo_curve_t curve, size_t d, size_t k, const void* d_C, const void* d_z,
+        const void* d_v, const void* d_Ls, const void* d_Rs, const void* d_U, const void* d_c, const void* d_hiding,
+        const void* d_C_bar, const void* d_w_prime, void* d_xis_out, void* d_alpha_out, void* d_ok, void* stream);
 
 /* ------------------------------------------------------------------ measurement hooks
  * When enabled, the library brackets its dominant kernels (MSM bucket accumulation, NTT passes)

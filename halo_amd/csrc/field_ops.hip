@@ -152,12 +152,8 @@ __global__ __launch_bounds__(64) void k_curve_op(int op, const uint4* a, const u
     XYZZ<F> r;
     if (op == 0) {
         r = xyzz_madd(xyzz_from_aff(p), aff_from_wrapped<F>(b + 4 * i));
-    } else if (op == 1) {
+    } else {  // op 1 (halo_curve_op admits 0..2, and 2 returned above)
         r = xyzz_dbl(xyzz_from_aff(p));
-    } else {
-        uint32_t w[8];
-        fe_ark_to_canonical_words<S>(k + 2 * i, w);
-        r = scalar_mul_glv<Cv>(p, w, smul_tab + 16 * 8 * threadIdx.x);
     }
     aff_to_wrapped(out + 4 * i, xyzz_to_aff(r));
 }

@@ -29,6 +29,33 @@ def commit(p, d: int, w=None, curve="pallas") -> np.ndarray:
     return out
 
 
+def hiding_blind(q, d: int, z, w_bar, curve="pallas", want_p_bar: bool = True):
+    """pcdl.rs:344-355 as one host call (halo_pcdl_hiding_blind): p_bar = (X - z) q for the d
+    coefficients q, C_bar = commit(p_bar, d, w_bar) over the resident SRS.  Returns (p_bar, C_bar);
+    p_bar is None when it is not asked for."""
+    H.ensure_device()
+    p_bar = np.zeros((d + 1, 4), dtype=np.uint64) if want_p_bar else None
+    C_bar = np.zeros(8, dtype=np.uint64)
+    H.check(H.load().halo_pcdl_hiding_blind(_curve(curve), H.ptr(H.fe_array(q, d)), d, H.ptr(H.fe_array(z, 1)),
+                                            H.ptr(H.fe_array(w_bar, 1)), H.ptr(p_bar), H.ptr(C_bar)))
+    return p_bar, C_bar
+
+
+def hiding_combine(p, p_bar, d: int, alpha, C, C_bar, w, w_bar, curve="pallas"):
+    """pcdl.rs:366-371 as one host call (halo_pcdl_hiding_combine): p' = p + alpha p_bar (p padded to
+    d + 1), w' = w + alpha w_bar, C' = C + alpha C_bar - w' S.  Returns (p', w', C')."""
+    H.ensure_device()
+    pa = H.fe_array(p) if p is not None and len(p) else None
+    p_prime = np.zeros((d + 1, 4), dtype=np.uint64)
+    w_prime = np.zeros(4, dtype=np.uint64)
+    C_prime = np.zeros(8, dtype=np.uint64)
+    H.check(H.load().halo_pcdl_hiding_combine(
+        _curve(curve), H.ptr(pa), 0 if pa is None else len(pa), H.ptr(H.fe_array(p_bar, d + 1)), d,
+        H.ptr(H.fe_array(alpha, 1)), H.ptr(H.point_array(C)), H.ptr(H.point_array(C_bar)), H.ptr(H.fe_array(w, 1)),
+        H.ptr(H.fe_array(w_bar, 1)), H.ptr(p_prime), H.ptr(w_prime), H.ptr(C_prime)))
+    return p_prime, w_prime, C_prime
+
+
 class IpaSession:
     """Device-resident (G, c, z) of one opening; mirrors the loop state of pcdl.rs:392-438."""
 

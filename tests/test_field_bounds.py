@@ -182,6 +182,21 @@ def _glv_consts():
     return out
 
 
+def glv_decompose(c, k):
+    """glv.hpp decompose on Python integers (round_shift384 included): the signed halves (k1, k2) of
+    k = k1 + lambda k2 (mod r); c = _glv_consts()[curve]."""
+    c1 = (k * abs(c["G1"]) + (1 << 383)) >> 384
+    c2 = (k * abs(c["G2"]) + (1 << 383)) >> 384
+    c1 = -c1 if c["G1"] < 0 else c1
+    c2 = -c2 if c["G2"] < 0 else c2
+    return k - c1 * c["A1"] - c2 * c["A2"], -c1 * c["B1"] - c2 * c["B2"]
+
+
+def glv_lambda(c, r):
+    """lambda = -a1 / b1 (mod r): (a1, b1) is a lattice vector, a1 + lambda b1 = 0 (mod r)."""
+    return -c["A1"] * pow(c["B1"], -1, r) % r
+
+
 @pytest.mark.parametrize("curve,r", [("PallasCurveCfg", PRIMES["fq"]), ("VestaCurveCfg", PRIMES["fp"])])
 def test_glv_halves_fit_signed_windows(curve, r):
     c = _glv_consts()[curve]
@@ -190,12 +205,8 @@ def test_glv_halves_fit_signed_windows(curve, r):
     assert (abs(c["A1"]) + abs(c["A2"])) // 2 + 1 < limit
     assert (abs(c["B1"]) + abs(c["B2"])) // 2 + 1 < limit
 
-    def decompose(k):  # glv.hpp decompose on Python integers (round_shift384 included)
-        c1 = (k * abs(c["G1"]) + (1 << 383)) >> 384
-        c2 = (k * abs(c["G2"]) + (1 << 383)) >> 384
-        c1 = -c1 if c["G1"] < 0 else c1
-        c2 = -c2 if c["G2"] < 0 else c2
-        return k - c1 * c["A1"] - c2 * c["A2"], -c1 * c["B1"] - c2 * c["B2"]
+    def decompose(k):
+        return glv_decompose(c, k)
 
     rng = random.Random(5)
     ks = [0, 1, r - 1, r // 2, r // 2 + 1, r // 3, 2 * r // 3] + [rng.randrange(r) for _ in range(20000)]

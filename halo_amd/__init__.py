@@ -13,6 +13,8 @@ reference's names, argument meaning and assertion messages:
     halo_amd.acc      -- crates/accumulation/src/acc.rs      (common_subroutine, prover, verifier, decider)
     halo_amd.schnorr  -- crates/schnorr/src/lib.rs (hash_message, PublicKey::verify) and the inner
                          Poseidon sponge of crates/poseidon, as batches of independent items
+    halo_amd.plonk    -- crates/plonk/src/plonk/protocol.rs (PlonkProof, verify_succinct, verify: batches
+                         of raw proofs of one circuit, every transcript on the device)
 
 Field elements are numpy uint64 arrays of shape (n, 4) in arkworks Montgomery form; points are
 (n, 8) WrappedPoint arrays (x, y Montgomery limbs; (0, 0) = identity).  There is no CPU fallback:
@@ -20,4 +22,4 @@ without the HIP library or a GPU every call raises.
 """
 from . import _lib  # noqa: F401
 
-__all__ = ["_lib", "group", "poly", "pedersen", "pcdl", "acc", "schnorr"]
+__all__ = ["_lib", "group", "poly", "pedersen", "pcdl", "acc", "schnorr", "plonk"]

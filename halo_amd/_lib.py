@@ -140,6 +140,8 @@ SIGNATURES = {
     "halo_pcdl_succinct_check_batch": [ctypes.c_int, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "halo_pcdl_succinct_check_fs_batch": [ctypes.c_int, _sz, _sz] + [_vp] * 13,
     "halo_pcdl_succinct_check_fs_batch_dev": [ctypes.c_int, _sz, _sz] + [_vp] * 14,
+    "halo_plonk_verify_succinct_batch": [ctypes.c_int, _sz, _sz, _vp, _vp, _sz] + [_vp] * 19,
+    "halo_plonk_verify_succinct_batch_dev": [ctypes.c_int, _sz, _sz, _vp, _vp, _sz] + [_vp] * 20,
     "halo_field_op": [ctypes.c_int, ctypes.c_int, _vp, _vp, _sz, _vp],
     "halo_curve_op": [ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _sz, _vp],
 }

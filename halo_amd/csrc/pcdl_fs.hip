@@ -23,6 +23,7 @@
 #include "dispatch.hpp"
 #include "lincomb.hpp"
 #include "outer_sponge.hpp"
+#include "pcdl_fs.hpp"
 #include "quad_ladder.hpp"
 #include "runtime.hpp"
 #include "sponge_launch.hpp"
@@ -231,13 +232,6 @@ __global__ __launch_bounds__(FS_THREADS) void k_pcdl_terms(const uint4* __restri
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-struct FsCall {  // the arguments of either entry point
-    int curve;
-    size_t d, k;
-    const void *C, *z, *v, *Ls, *Rs, *U, *c, *hiding, *C_bar, *w_prime;
-    void *xis_out, *alpha_out, *ok;
-};
-
 // Everything that needs no device; done: an empty batch.
 static int check_fs_args(const char* call, const FsCall& a, bool& done) {
     done = false;
@@ -262,7 +256,7 @@ static int check_fs_args(const char* call, const FsCall& a, bool& done) {
 static size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 
 // The launches of one call over device pointers, all on `s`.  st->mu and a ScratchUse of `s` held; a.k >= 1.
-static int fs_device(const char* call, DeviceState* st, const FsCall& a, hipStream_t s) {
+int fs_device(const char* call, DeviceState* st, const FsCall& a, hipStream_t s) {
     const SrsState& srs = st->srs[a.curve];
     if (!srs.n || a.d > srs.n - 1) return set_error(HALO_ESRSRANGE, "d was larger than D!");
     if (!srs.has_sh) return set_error(HALO_ESRSRANGE, "%s: no (S, H) uploaded", call);

@@ -1,0 +1,18 @@
+// The device-level succinct check of pcdl_fs.hip for the units that build on it (plonk_verify.hip).
+#pragma once
+#include "runtime.hpp"
+
+namespace halo {
+
+struct FsCall {  // the arguments of either entry point of halo_pcdl_succinct_check_fs_batch
+    int curve;
+    size_t d, k;
+    const void *C, *z, *v, *Ls, *Rs, *U, *c, *hiding, *C_bar, *w_prime;
+    void *xis_out, *alpha_out, *ok;
+};
+
+// The launches of one call over device pointers, all on `s`: st->mu and a ScratchUse of `s` held, a.k >= 1,
+// the arguments checked.  Works in st->scratch[7] and st->lincomb_terms.
+int fs_device(const char* call, DeviceState* st, const FsCall& a, hipStream_t s);
+
+}  // namespace halo

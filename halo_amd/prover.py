@@ -20,8 +20,9 @@ backend ``B``; with ``DeviceBackend`` every data-parallel step runs in libhalo_g
   polynomial evaluations of the proof (protocol.rs:273-323).
 
 Out of scope (SURVEY §8 "out of scope"): circuit construction and witness generation (the witness
-polynomials here are synthetic), the Poseidon Fiat-Shamir transcript (challenges come from a seeded
-stand-in, ``Challenges``), the succinct checks of acc::prover (verifier arithmetic over lg n
+polynomials here are synthetic), the Poseidon Fiat-Shamir transcript on the benchmarked path (challenges
+come from a seeded stand-in, ``Challenges``; ``naive_prover(..., transcript=new_transcript)`` runs the
+reference's sponges instead, so that halo_amd.plonk can verify the proof), the succinct checks of acc::prover (verifier arithmetic over lg n
 elements) and the hiding terms (``naive_prover`` opens with w = None).  The generic pipeline also
 runs on the CPU restatement backend (oracle/prover_ref.py) at small n: tests/test_gpu_prover.py
 checks every commitment, evaluation and opening bit-exact against it.
@@ -193,13 +194,42 @@ def geometric_polys(B, zeta: int, polys):
     return result
 
 
-def naive_prover(B, wit, n: int, chal: Challenges, acc_prev=None, keep=None):
+class _TranscriptChallenges:
+    """The reference's PLONK sponge (protocol.rs:70) behind the call interface of ``Challenges``: the
+    prover absorbs its commitments through ``absorb_g`` and draws canonical integers."""
+
+    def __init__(self, sponge, modulus: int):
+        self.sponge, self.m = sponge, modulus
+        self.r_inv = pow(1 << 256, -1, modulus)
+
+    def absorb_g(self, points):
+        self.sponge.absorb_g(points)
+
+    def __call__(self) -> int:
+        x = np.asarray(self.sponge.challenge(), dtype=np.uint64).reshape(4)
+        return (int(x[0]) | int(x[1]) << 64 | int(x[2]) << 128 | int(x[3]) << 192) * self.r_inv % self.m
+
+
+def naive_prover(B, wit, n: int, chal: Challenges, acc_prev=None, keep=None, transcript=None):
     """protocol.rs:64-330 on backend B.  Returns the proof's commitments, evaluations, the three IPA
     openings and per-round wall times (seconds; B.sync() before each stamp).  ``keep``: an optional
     dict that receives the intermediate polynomials and challenges (z, f, t's pieces, beta, gamma,
-    alpha, zeta, xi, ...) so a test can check them at full size against the oracle."""
+    alpha, zeta, xi, ...) so a test can check them at full size against the oracle.
+
+    ``transcript``: None draws every challenge from the stand-in ``chal`` (the benchmarked path).  A
+    factory ``new_transcript(label)`` in the convention of halo_amd/acc.py (fresh sponges over
+    WrappedPoints / ark scalars for "PLONK", "PCDL", "ASDL") makes the proof the reference's: the PLONK
+    sponge absorbs C_ws, C_z and C_ts where protocol.rs:116,163,265 do, and round 5 goes through the
+    backend's ``instance_open`` / ``acc_prove`` hooks (Instance::open and acc::prover under their own
+    sponges).  ``acc_prev`` is then required, as the dict such a hook returns (C, z, v, Ls, Rs, U, c),
+    and ``chal`` is not read."""
     import time
 
+    if transcript is not None:
+        if acc_prev is None:
+            raise ValueError("naive_prover under a transcript needs acc_prev (an accumulator of acc_prove)")
+        chal = _TranscriptChallenges(transcript("PLONK"), B.m)
+    real = transcript is not None
     m = B.m
     d = n - 1
     N8 = n * CONSTRAINT_DEGREE_MULTIPLIER
@@ -223,6 +253,8 @@ def naive_prover(B, wit, n: int, chal: Challenges, acc_prev=None, keep=None):
     # ---- round 1 (protocol.rs:114)
     t1 = time.perf_counter()
     C_ws = B.commit_many(wit["ws"])
+    if real:
+        chal.absorb_g(C_ws)
     B.sync()
     times["round1"] = time.perf_counter() - t1
 
@@ -248,6 +280,8 @@ def naive_prover(B, wit, n: int, chal: Challenges, acc_prev=None, keep=None):
     z_omega = B.intt(B.shift_left(z_evals, 1))
     z = B.intt(z_evals)
     C_z = B.commit_many([z])[0]
+    if real:
+        chal.absorb_g([C_z])
     B.sync()
     times["round3"] = time.perf_counter() - t3
 
@@ -283,6 +317,8 @@ def naive_prover(B, wit, n: int, chal: Challenges, acc_prev=None, keep=None):
     assert B.length(t) <= T_POLYS * n, f"{B.length(t)} < {T_POLYS * n}"
     ts = B.split(B.resize(t, T_POLYS * n), n)                  # t_split (protocol.rs:509-517)
     C_ts = B.commit_many(ts)
+    if real:
+        chal.absorb_g(C_ts)
     B.sync()
     times["round4"] = time.perf_counter() - t4
 
@@ -299,10 +335,17 @@ def naive_prover(B, wit, n: int, chal: Challenges, acc_prev=None, keep=None):
         acc_prev = synthetic_accumulator(B, n, chal)
     B.sync()
     t5a = time.perf_counter()
-    q_r, q_r_omega = instances_open(B, [(r, xi), (r_omega, xi * omega % m)], d)
+    if real:
+        q_r = B.instance_open(r, d, xi, transcript)
+        q_r_omega = B.instance_open(r_omega, d, xi * omega % m, transcript)
+    else:
+        q_r, q_r_omega = instances_open(B, [(r, xi), (r_omega, xi * omega % m)], d)
     B.sync()
     t5b = time.perf_counter()
-    acc_next = acc_prover(B, [acc_prev, q_r, q_r_omega], d, chal)
+    if real:
+        acc_next = B.acc_prove([acc_prev, q_r, q_r_omega], d, transcript)
+    else:
+        acc_next = acc_prover(B, [acc_prev, q_r, q_r_omega], d, chal)
     B.sync()
     t5c = time.perf_counter()
     at_xi = wit["ws"] + wit["rs"] + wit["qs"] + ts + wit["ids"] + wit["sigmas"] + [z] + w_omegas
@@ -714,6 +757,30 @@ class DeviceBackend:
 
     def ipa(self, p, n: int, z: int, h_prime, chal):
         return self.ipa_many([(p, n, z, h_prime)], [chal])[0]
+
+    # -- round 5 under the reference's transcripts (naive_prover(..., transcript=new_transcript)): the
+    # host-array entry points of halo_amd.pcdl / halo_amd.acc; this mode is for correctness, not the benchmark
+    def instance_open(self, p, d: int, z: int, new_transcript):
+        """Instance::open (pcdl.rs:41-51) with w = None: C = commit(p), v = p(z), pi = open under a fresh
+        PCDL sponge.  Returns dict(C, z, v, Ls, Rs, U, c); z, v, c canonical integers."""
+        from . import pcdl
+
+        ph = np.ascontiguousarray(p.cpu().numpy().view(np.uint64))
+        C = pcdl.commit(ph, d, curve=self.curve)
+        pi = pcdl.open(ph, C, d, self.fe(z), transcript=new_transcript("PCDL"), curve=self.curve)
+        return {"C": C, "z": z, "v": self.to_int(pi["v"]), "Ls": pi["Ls"], "Rs": pi["Rs"], "U": pi["U"],
+                "c": self.to_int(pi["c"])}
+
+    def acc_prove(self, qs, d: int, new_transcript):
+        """acc::prover (acc.rs:178-198) over instances in instance_open's form; the accumulator in the same form."""
+        from . import acc, pcdl
+
+        insts = [pcdl.Instance(np.asarray(q["C"], dtype=np.uint64), d, self.fe(q["z"]), self.fe(q["v"]),
+                               {"Ls": np.stack(q["Ls"]), "Rs": np.stack(q["Rs"]), "U": np.asarray(q["U"], dtype=np.uint64),
+                                "c": self.fe(q["c"]), "C_bar": None, "w_prime": None}) for q in qs]
+        a = acc.prover(insts, new_transcript, self.curve)
+        return {"C": a.C, "z": self.to_int(a.z), "v": self.to_int(a.v), "Ls": a.pi["Ls"], "Rs": a.pi["Rs"],
+                "U": a.pi["U"], "c": self.to_int(a.pi["c"])}
 
 
 class DevEvals:

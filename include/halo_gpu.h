@@ -501,6 +501,62 @@ int halo_pcdl_succinct_check_fs_batch_dev(halo_curve_t curve, size_t d, size_t k
         const void* d_v, const void* d_Ls, const void* d_Rs, const void* d_U, const void* d_c, const void* d_hiding,
         const void* d_C_bar, const void* d_w_prime, void* d_xis_out, void* d_alpha_out, void* d_ok, void* stream);
 
+/* ------------------------------------------------------------------ the Plonk verifier
+ * PlonkProof::verify_succinct (crates/plonk/src/plonk/protocol.rs:357-491) for k raw proofs of one circuit:
+ * rows = n (a power of two >= 4, d = n - 1, omega = 5^((r - 1) / n)), the circuit's selector commitments
+ * C_qs[10], the scalar Poseidon MDS matrix mds[9] (P::SCALAR_POSEIDON_MDS, row-major) and npi public inputs
+ * per proof (public_inputs[i npi + j]; npi may be 0, public_inputs then NULL).  The proofs do not hide
+ * (naive_prover and acc::prover open with w = None), so no C_bar / w_prime is carried.  Per proof i:
+ *   C_ws[16 i + j], C_z[i], C_ts[16 i + j]         PlonkProofCommitments
+ *   vs[78 i + j]                                   PlonkProofEvals in struct order (protocol.rs:36-46): ws 16,
+ *                                                  rs 15, qs 10, ts 16, ids 8, sigmas 8, z, z_omega, w_omegas 3
+ *   Ls / Rs[(3 i + q) lg n + j], U[3 i + q], c[3 i + q]   the EvalProofs of qs = [acc_prev, instance_1 (r),
+ *                                                  instance_2 (r_omega)] (protocol.rs:487), q = 0, 1, 2
+ *   acc_prev_{C, z, v}[i], acc_next_{C, z, v}[i]   acc_next.pi is not read (acc.rs:201)
+ * Every transcript runs on the device: the PLONK sponge (beta, gamma, alpha, zeta, xi), the PCDL sponge of each
+ * of the 3 k instances (halo_pcdl_succinct_check_fs_batch) and the ASDL sponge of acc::verifier.
+ * verdict[i] is HALO_PLONK_ACCEPT or the first failing check in the reference's order (halo_plonk_verdict_t).
+ * HALO_PLONK_MALFORMED stands for a proof the reference has no verdict for and comes before every check: a
+ * point that is neither (0, 0) nor on the curve (the reference's Affine type cannot hold one), or a derived
+ * xi with n (xi - omega^j) = 0 for some 1 <= j <= max(npi, 1) (probability about npi 2^-254), where the
+ * reference divides by zero in l1 or public_input_eval_generic and panics.  A malformed proof never
+ * disturbs its neighbours; its optional outputs are unspecified.
+ * Optional outputs (may be NULL): challenges_out[5 i ..] = beta, gamma, alpha, zeta, xi; sides_out[2 i ..] =
+ * f(xi) and t(xi) z_H(xi), the two sides of protocol.rs:441-444; asdl_out[2 i ..] = the accumulation's
+ * alpha and z' (acc.rs:160,169).
+ * Needs the resident SRS with (S, H) and halo_poseidon_set_params for the curve's base field.  Before any
+ * device work: HALO_ENOTPOW2 "n ({n}) is not a power of two", HALO_EINVAL for rows < 4, a null required
+ * pointer, unset Poseidon parameters or a scalar that is not below the modulus; then HALO_ESRSRANGE
+ * "d was larger than D!" or for a missing (S, H).  k = 0: HALO_OK. */
+#define HALO_PLONK_EVALS 78
+typedef enum {
+    HALO_PLONK_ACCEPT = 0,
+    HALO_PLONK_IDENTITY = 1,   /* "T(z) != (F_GC(z) + a F_CC1(z) + a^2 F_CC2(z) + ...) / Z_H(z)" (protocol.rs:441-444) */
+    HALO_PLONK_INSTANCE_0 = 2, /* succinct check of acc_prev (acc.rs:149) */
+    HALO_PLONK_INSTANCE_1 = 3, /* ... of (C_r, d, xi, v_r, pi_r) */
+    HALO_PLONK_INSTANCE_2 = 4, /* ... of (C_r_omega, d, xi omega, v_r_omega, pi_r_omega) */
+    HALO_PLONK_C_BAR = 5,      /* "C_bar' != C_bar" (acc.rs:207) */
+    HALO_PLONK_Z = 6,          /* "z' = z" (acc.rs:208) */
+    HALO_PLONK_V = 7,          /* "h(z) = v" (acc.rs:210) */
+    HALO_PLONK_MALFORMED = 8
+} halo_plonk_verdict_t;
+int halo_plonk_verify_succinct_batch(halo_curve_t curve, size_t rows, size_t k,
+        const halo_wrapped_point_t* C_qs, const halo_fe_t* public_inputs, size_t npi,
+        const halo_wrapped_point_t* C_ws, const halo_wrapped_point_t* C_z, const halo_wrapped_point_t* C_ts,
+        const halo_fe_t* vs, const halo_wrapped_point_t* Ls, const halo_wrapped_point_t* Rs,
+        const halo_wrapped_point_t* U, const halo_fe_t* c,
+        const halo_wrapped_point_t* acc_prev_C, const halo_fe_t* acc_prev_z, const halo_fe_t* acc_prev_v,
+        const halo_wrapped_point_t* acc_next_C, const halo_fe_t* acc_next_z, const halo_fe_t* acc_next_v,
+        const halo_fe_t* mds, uint8_t* verdict, halo_fe_t* challenges_out, halo_fe_t* sides_out, halo_fe_t* asdl_out);
+/* The same over device pointers, asynchronous on `stream`; no host wait, no host arithmetic.  Here a
+ * scalar that is not below the modulus gives HALO_PLONK_MALFORMED for its proof (an MDS entry: for all). */
+int halo_plonk_verify_succinct_batch_dev(halo_curve_t curve, size_t rows, size_t k,
+        const void* d_C_qs, const void* d_public_inputs, size_t npi, const void* d_C_ws, const void* d_C_z,
+        const void* d_C_ts, const void* d_vs, const void* d_Ls, const void* d_Rs, const void* d_U, const void* d_c,
+        const void* d_acc_prev_C, const void* d_acc_prev_z, const void* d_acc_prev_v,
+        const void* d_acc_next_C, const void* d_acc_next_z, const void* d_acc_next_v, const void* d_mds,
+        void* d_verdict, void* d_challenges_out, void* d_sides_out, void* d_asdl_out, void* stream);
+
 /* ------------------------------------------------------------------ measurement hooks
  * When enabled, the library brackets its dominant kernels (MSM bucket accumulation, NTT passes)
  * with hipEvents on the stream they run on; halo_profile_read returns the number of launches and

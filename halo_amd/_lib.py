@@ -140,8 +140,14 @@ SIGNATURES = {
     "halo_pcdl_succinct_check_batch": [ctypes.c_int, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "halo_pcdl_succinct_check_fs_batch": [ctypes.c_int, _sz, _sz] + [_vp] * 13,
     "halo_pcdl_succinct_check_fs_batch_dev": [ctypes.c_int, _sz, _sz] + [_vp] * 14,
+    "halo_pcdl_decide_batch": [ctypes.c_int, _sz, _sz] + [_vp] * 5,
+    "halo_pcdl_decide_batch_dev": [ctypes.c_int, _sz, _sz] + [_vp] * 7,
+    "halo_pcdl_check_fs_batch": [ctypes.c_int, _sz, _sz] + [_vp] * 12,
+    "halo_pcdl_check_fs_batch_dev": [ctypes.c_int, _sz, _sz] + [_vp] * 14,
     "halo_plonk_verify_succinct_batch": [ctypes.c_int, _sz, _sz, _vp, _vp, _sz] + [_vp] * 19,
     "halo_plonk_verify_succinct_batch_dev": [ctypes.c_int, _sz, _sz, _vp, _vp, _sz] + [_vp] * 20,
+    "halo_plonk_verify_batch": [ctypes.c_int, _sz, _sz, _vp, _vp, _sz] + [_vp] * 21,
+    "halo_plonk_verify_batch_dev": [ctypes.c_int, _sz, _sz, _vp, _vp, _sz] + [_vp] * 23,
     "halo_field_op": [ctypes.c_int, ctypes.c_int, _vp, _vp, _sz, _vp],
     "halo_curve_op": [ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _sz, _vp],
 }

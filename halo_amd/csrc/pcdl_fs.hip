@@ -233,7 +233,7 @@ __global__ __launch_bounds__(FS_THREADS) void k_pcdl_terms(const uint4* __restri
 // host side
 // ---------------------------------------------------------------------------------------------
 // Everything that needs no device; done: an empty batch.
-static int check_fs_args(const char* call, const FsCall& a, bool& done) {
+int check_fs_args(const char* call, const FsCall& a, bool& done) {
     done = false;
     if (a.curve != HALO_PALLAS && a.curve != HALO_VESTA) return set_error(HALO_EINVAL, "%s: unknown curve", call);
     if (a.k == 0) {
@@ -332,6 +332,49 @@ int fs_device(const char* call, DeviceState* st, const FsCall& a, hipStream_t s)
     return lincomb_device(st, a.curve, Cp, pts, sc, k, t, sum, a.ok, s);
 }
 
+// The host form's scalars: z, v, c and every w' that is read are below the modulus.
+int fs_host_scalars(const char* call, const FsCall& host) {
+    const uint64_t(&p)[4] = host.curve == HALO_PALLAS ? FpCfg::MODULUS64 : FqCfg::MODULUS64;  // the scalar field
+    auto below = [&](const halo_fe_t& x) {
+        for (int q = 3; q >= 0; q--)
+            if (x.l[q] != p[q]) return x.l[q] < p[q];
+        return false;
+    };
+    const halo_fe_t *z = (const halo_fe_t*)host.z, *v = (const halo_fe_t*)host.v, *c = (const halo_fe_t*)host.c,
+                    *w_prime = (const halo_fe_t*)host.w_prime;
+    const uint8_t* hiding = (const uint8_t*)host.hiding;
+    for (size_t i = 0; i < host.k; i++)
+        if (!below(z[i]) || !below(v[i]) || !below(c[i]) || (hiding && hiding[i] && !below(w_prime[i])))
+            return set_error(HALO_EINVAL, "%s: a scalar of instance %zu is not below the modulus", call, i);
+    return HALO_OK;
+}
+
+// The inputs of a host call as one buffer (st->scratch[0]) on stream s; dev: the same call over device
+// pointers, its outputs null.
+int fs_upload(DeviceState* st, const FsCall& host, FsCall& dev, hipStream_t s) {
+    const size_t k = host.k, lg = ilog2(host.d + 1);
+    const bool hid = host.hiding != nullptr;
+    struct Part {
+        const void* src;
+        size_t bytes, off;
+    } in[10] = {{host.C, k * 64, 0},       {host.z, k * 32, 0},       {host.v, k * 32, 0},
+                {host.Ls, k * lg * 64, 0}, {host.Rs, k * lg * 64, 0}, {host.U, k * 64, 0},
+                {host.c, k * 32, 0},       {host.hiding, hid ? k : 0, 0}, {host.C_bar, hid ? k * 64 : 0, 0},
+                {host.w_prime, hid ? k * 32 : 0, 0}};
+    size_t n_in = 0;
+    for (Part& q : in) {
+        q.off = n_in;
+        n_in += align256(q.bytes);
+    }
+    HALO_CHECK(st->scratch[0].reserve(n_in));
+    uint8_t* di = st->scratch[0].as<uint8_t>();
+    for (const Part& q : in) HALO_CHECK(copy_h2d(di + q.off, q.src, q.bytes, s));
+    auto at = [&](int j) -> const void* { return in[j].bytes ? di + in[j].off : nullptr; };
+    dev = FsCall{host.curve, host.d, k, at(0), at(1), at(2), at(3), at(4), at(5), at(6), at(7), at(8), at(9),
+                 nullptr, nullptr, nullptr};
+    return HALO_OK;
+}
+
 }  // namespace halo
 
 using namespace halo;
@@ -367,43 +410,22 @@ extern "C" int halo_pcdl_succinct_check_fs_batch(halo_curve_t curve, size_t d, s
     bool done;
     HALO_CHECK(check_fs_args(call, host, done));
     if (done) return HALO_OK;
-    const uint64_t(&p)[4] = curve == HALO_PALLAS ? FpCfg::MODULUS64 : FqCfg::MODULUS64;  // the scalar field
-    auto below = [&](const halo_fe_t& x) {
-        for (int q = 3; q >= 0; q--)
-            if (x.l[q] != p[q]) return x.l[q] < p[q];
-        return false;
-    };
-    for (size_t i = 0; i < k; i++)
-        if (!below(z[i]) || !below(v[i]) || !below(c[i]) || (hiding && hiding[i] && !below(w_prime[i])))
-            return set_error(HALO_EINVAL, "%s: a scalar of instance %zu is not below the modulus", call, i);
+    HALO_CHECK(fs_host_scalars(call, host));
     DeviceState* st = current_state();
     if (!st) return HALO_EDEVICE;
     std::lock_guard<std::mutex> g(st->mu);
     hipStream_t s = 0;
     ScratchUse su(st, s);
-    // one buffer of inputs and one of outputs
     const size_t lg = ilog2(d + 1);
-    struct Part {
-        const void* src;
-        size_t bytes, off;
-    } in[10] = {{C, k * 64, 0},       {z, k * 32, 0},      {v, k * 32, 0},
-                {Ls, k * lg * 64, 0}, {Rs, k * lg * 64, 0}, {U, k * 64, 0},
-                {c, k * 32, 0},       {hiding, hiding ? k : 0, 0}, {C_bar, hiding ? k * 64 : 0, 0},
-                {w_prime, hiding ? k * 32 : 0, 0}};
-    size_t n_in = 0;
-    for (Part& q : in) {
-        q.off = n_in;
-        n_in += align256(q.bytes);
-    }
+    FsCall a;
+    HALO_CHECK(fs_upload(st, host, a, s));
     const size_t o_xis = 0, o_alpha = o_xis + align256(xis_out ? k * (lg + 1) * 32 : 0),
                  o_ok = o_alpha + align256(alpha_out ? k * 32 : 0);
-    HALO_CHECK(st->scratch[0].reserve(n_in));
     HALO_CHECK(st->scratch[1].reserve(o_ok + k));
-    uint8_t *di = st->scratch[0].as<uint8_t>(), *dout = st->scratch[1].as<uint8_t>();
-    for (const Part& q : in) HALO_CHECK(copy_h2d(di + q.off, q.src, q.bytes, s));
-    auto dev = [&](int j) -> const void* { return in[j].bytes ? di + in[j].off : nullptr; };
-    const FsCall a{(int)curve, d,      k,      dev(0), dev(1), dev(2), dev(3), dev(4), dev(5), dev(6), dev(7), dev(8), dev(9),
-                   xis_out ? dout + o_xis : nullptr, alpha_out ? dout + o_alpha : nullptr, dout + o_ok};
+    uint8_t* dout = st->scratch[1].as<uint8_t>();
+    a.xis_out = xis_out ? dout + o_xis : nullptr;
+    a.alpha_out = alpha_out ? dout + o_alpha : nullptr;
+    a.ok = dout + o_ok;
     HALO_CHECK(fs_device(call, st, a, s));
     if (xis_out) HALO_CHECK(copy_d2h(xis_out, dout + o_xis, k * (lg + 1) * 32, s));
     if (alpha_out) HALO_CHECK(copy_d2h(alpha_out, dout + o_alpha, k * 32, s));

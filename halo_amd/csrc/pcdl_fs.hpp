@@ -15,4 +15,11 @@ struct FsCall {  // the arguments of either entry point of halo_pcdl_succinct_ch
 // the arguments checked.  Works in st->scratch[7] and st->lincomb_terms.
 int fs_device(const char* call, DeviceState* st, const FsCall& a, hipStream_t s);
 
+// What the host entry points share (halo_pcdl_check_fs_batch, decider.hip): the checks that need no device
+// (done: an empty batch), the scalars of a host call below the modulus, and the inputs of a host call as one
+// buffer in st->scratch[0] (dev: the call over device pointers, its outputs null).
+int check_fs_args(const char* call, const FsCall& a, bool& done);
+int fs_host_scalars(const char* call, const FsCall& host);
+int fs_upload(DeviceState* st, const FsCall& host, FsCall& dev, hipStream_t s);
+
 }  // namespace halo

@@ -21,9 +21,18 @@
 //   (lincomb_device)    C_bar' - C_bar is the identity
 //   k_plonk_verdict     the stage bits folded into one byte per proof, in the reference's order
 //
+// PlonkProof::verify (protocol.rs:493-502, halo_plonk_verify_batch) is the same chain with four PCDL instances
+// per proof, the fourth acc_next itself, and acc::decider after it (decider.hip):
+//   k_plonk_next        before fs_device: the instance 4 i + 3 and the evaluation proofs of all 4 k instances in
+//                       fs_device's layout
+//   k_plonk_split_xis   after it: the challenges of the first three instances three per proof (what the ASDL
+//                       kernels read, unchanged) and those of acc_next as decide_device's rows
+//   (decide_device)     the deciders of the proofs whose verdict is still ACCEPT; k_plonk_decided folds them in
+//
 // As in pcdl_fs.hip no sponge state passes between kernels, and lanes past the batch repeat its last
 // proof because they take part in the shuffles.
 #include "curve.hpp"
+#include "decider.hpp"
 #include "dispatch.hpp"
 #include "lincomb.hpp"
 #include "outer_sponge.hpp"
@@ -149,7 +158,7 @@ HALO_DEV Fe<S> gate_add_core(const Fe<S>& xp, const Fe<S>& yp, const Fe<S>& xq, 
 
 // One lane per proof.  den: m = max(npi, 1) elements per proof for the prefix products of the shared
 // inversion.  Writes sides[2 i ..] = f, t z_H; bits[i] = BIT_IDENTITY when they differ; the scalars z, v of the
-// instances 3 i + 0 .. 2; the term rows of C_r and C_r_omega.  mal[i] = 1 for a scalar that is not below the
+// instances ipp i + 0 .. 2 (ipp instances per proof); the term rows of C_r and C_r_omega.  mal[i] = 1 for a scalar that is not below the
 // modulus or a zero denominator n (xi - omega^j), 1 <= j <= m.
 template <class Cv>
 __global__ __launch_bounds__(PV_THREADS) void k_plonk_identity(
@@ -157,7 +166,7 @@ __global__ __launch_bounds__(PV_THREADS) void k_plonk_identity(
     const uint4* __restrict__ mds, const uint4* __restrict__ C_qs, const uint4* __restrict__ C_ws,
     const uint4* __restrict__ C_z, const uint4* __restrict__ C_ts, const uint4* __restrict__ prev_z,
     const uint4* __restrict__ prev_v, const uint4* __restrict__ next_z, const uint4* __restrict__ next_v,
-    const uint4* __restrict__ c, unsigned lg, size_t k, uint4* __restrict__ den, uint4* __restrict__ r_pts,
+    const uint4* __restrict__ c, unsigned lg, size_t k, size_t ipp, uint4* __restrict__ den, uint4* __restrict__ r_pts,
     uint4* __restrict__ r_sc, uint4* __restrict__ ro_pts, uint4* __restrict__ ro_sc, uint4* __restrict__ inst_z,
     uint4* __restrict__ inst_v, uint4* __restrict__ sides, uint8_t* __restrict__ bits, uint8_t* __restrict__ mal) {
     using S = typename Cv::Scalar;
@@ -347,8 +356,8 @@ __global__ __launch_bounds__(PV_THREADS) void k_plonk_identity(
         }
         zp = fe_mul(zp, zeta);
     }
-    inst_z += 2 * 3 * i;
-    inst_v += 2 * 3 * i;
+    inst_z += 2 * ipp * i;  // the proof's instances 0 .. 2 of ipp
+    inst_v += 2 * ipp * i;
     for (int q = 0; q < 2; q++) {
         inst_z[q] = prev_z[2 * i + q];
         inst_v[q] = prev_v[2 * i + q];
@@ -359,20 +368,20 @@ __global__ __launch_bounds__(PV_THREADS) void k_plonk_identity(
     fe_to_ark(inst_v + 4, v_ro);
 }
 
-// C of the instances 3 i + 0 .. 2: acc_prev.C, C_r, C_r_omega (the sums made affine; the identity becomes (0, 0)).
+// C of the instances ipp i + 0 .. 2: acc_prev.C, C_r, C_r_omega (the sums made affine; the identity becomes (0, 0)).
 template <class Cv>
 __global__ __launch_bounds__(PV_THREADS) void k_plonk_instances(const uint4* __restrict__ prev_C,
                                                                 const uint4* __restrict__ sum_r,
-                                                                const uint4* __restrict__ sum_ro, size_t k,
+                                                                const uint4* __restrict__ sum_ro, size_t k, size_t ipp,
                                                                 uint4* __restrict__ inst_C) {
     using F = typename Cv::Base;
     const size_t g = (size_t)blockIdx.x * PV_THREADS + threadIdx.x;
     if (g >= 3 * k) return;
-    const size_t i = g / 3, j = g % 3;
+    const size_t i = g / 3, j = g % 3, o = ipp * i + j;
     if (j == 0)
-        for (int q = 0; q < 4; q++) inst_C[4 * g + q] = prev_C[4 * i + q];
+        for (int q = 0; q < 4; q++) inst_C[4 * o + q] = prev_C[4 * i + q];
     else
-        aff_to_wrapped(inst_C + 4 * g, xyzz_to_aff(xyzz_load<F>((j == 1 ? sum_r : sum_ro) + 8 * i)));
+        aff_to_wrapped(inst_C + 4 * o, xyzz_to_aff(xyzz_load<F>((j == 1 ? sum_r : sum_ro) + 8 * i)));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -461,8 +470,8 @@ __global__ __launch_bounds__(PV_THREADS) void k_asdl_terms(const uint4* __restri
 // checks in its order.
 __global__ __launch_bounds__(PV_THREADS) void k_plonk_verdict(const uint8_t* __restrict__ mal, const uint8_t* __restrict__ bits,
                                                               const uint8_t* __restrict__ ok3,
-                                                              const uint8_t* __restrict__ c_is_id, size_t k,
-                                                              uint8_t* __restrict__ verdict) {
+                                                              const uint8_t* __restrict__ c_is_id, size_t k, size_t ipp,
+                                                              uint8_t* __restrict__ verdict, uint8_t* __restrict__ live) {
     const size_t i = (size_t)blockIdx.x * PV_THREADS + threadIdx.x;
     if (i >= k) return;
     uint8_t v = HALO_PLONK_ACCEPT;
@@ -470,11 +479,11 @@ __global__ __launch_bounds__(PV_THREADS) void k_plonk_verdict(const uint8_t* __r
         v = HALO_PLONK_MALFORMED;
     else if (bits[i] & BIT_IDENTITY)
         v = HALO_PLONK_IDENTITY;
-    else if (!ok3[3 * i])
+    else if (!ok3[ipp * i])
         v = HALO_PLONK_INSTANCE_0;
-    else if (!ok3[3 * i + 1])
+    else if (!ok3[ipp * i + 1])
         v = HALO_PLONK_INSTANCE_1;
-    else if (!ok3[3 * i + 2])
+    else if (!ok3[ipp * i + 2])
         v = HALO_PLONK_INSTANCE_2;
     else if (!c_is_id[i])
         v = HALO_PLONK_C_BAR;
@@ -482,7 +491,68 @@ __global__ __launch_bounds__(PV_THREADS) void k_plonk_verdict(const uint8_t* __r
         v = HALO_PLONK_Z;
     else if (bits[i] & BIT_V)
         v = HALO_PLONK_V;
+    else if (ipp > 3 && !ok3[ipp * i + 3])
+        v = HALO_PLONK_DECIDER_SUCCINCT;
     verdict[i] = v;
+    if (live) live[i] = v == HALO_PLONK_ACCEPT ? 1 : 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// PlonkProof::verify: acc_next as a fourth instance per proof, then its decider
+// ---------------------------------------------------------------------------------------------
+// One lane per proof: the instance 4 i + 3 = (acc_next.C, d, acc_next.z, acc_next.v) and the evaluation proofs of
+// the proof's four instances as fs_device reads them (row 4 i + q).
+__global__ __launch_bounds__(PV_THREADS) void k_plonk_next(
+    const uint4* __restrict__ Ls, const uint4* __restrict__ Rs, const uint4* __restrict__ U, const uint4* __restrict__ c,
+    const uint4* __restrict__ next_Ls, const uint4* __restrict__ next_Rs, const uint4* __restrict__ next_U,
+    const uint4* __restrict__ next_c, const uint4* __restrict__ next_C, const uint4* __restrict__ next_z,
+    const uint4* __restrict__ next_v, size_t lg, size_t k, uint4* __restrict__ Ls4, uint4* __restrict__ Rs4,
+    uint4* __restrict__ U4, uint4* __restrict__ c4, uint4* __restrict__ inst_C, uint4* __restrict__ inst_z,
+    uint4* __restrict__ inst_v) {
+    const size_t i = (size_t)blockIdx.x * PV_THREADS + threadIdx.x;
+    if (i >= k) return;
+#pragma unroll 1
+    for (size_t q = 0; q < 4; q++) {
+        const size_t o = 4 * i + q;
+        const uint4 *sl = q < 3 ? Ls + 4 * (3 * i + q) * lg : next_Ls + 4 * i * lg,
+                    *sr = q < 3 ? Rs + 4 * (3 * i + q) * lg : next_Rs + 4 * i * lg,
+                    *su = q < 3 ? U + 4 * (3 * i + q) : next_U + 4 * i, *sc = q < 3 ? c + 2 * (3 * i + q) : next_c + 2 * i;
+#pragma unroll 1
+        for (size_t j = 0; j < 4 * lg; j++) {
+            Ls4[4 * o * lg + j] = sl[j];
+            Rs4[4 * o * lg + j] = sr[j];
+        }
+        for (int w = 0; w < 4; w++) U4[4 * o + w] = su[w];
+        for (int w = 0; w < 2; w++) c4[2 * o + w] = sc[w];
+    }
+    const size_t o = 4 * i + 3;
+    for (int w = 0; w < 4; w++) inst_C[4 * o + w] = next_C[4 * i + w];
+    for (int w = 0; w < 2; w++) {
+        inst_z[2 * o + w] = next_z[2 * i + w];
+        inst_v[2 * o + w] = next_v[2 * i + w];
+    }
+}
+
+// The xi rows of a full call, four per proof, split for their readers: those of the instances 4 i + 0 .. 2 three
+// per proof (the ASDL kernels' layout, which verify_succinct's chain writes directly) and those of the instances
+// 4 i + 3 one after the other (decide_device's layout).  One lane per scalar.
+__global__ __launch_bounds__(PV_THREADS) void k_plonk_split_xis(const uint4* __restrict__ xis, size_t lg, size_t k,
+                                                                uint4* __restrict__ three, uint4* __restrict__ next) {
+    const size_t g = (size_t)blockIdx.x * PV_THREADS + threadIdx.x;
+    if (g >= 4 * k * (lg + 1)) return;
+    const size_t inst = g / (lg + 1), j = g % (lg + 1), i = inst / 4, q = inst % 4;
+    uint4* dst = q < 3 ? three + 2 * ((3 * i + q) * (lg + 1) + j) : next + 2 * (i * (lg + 1) + j);
+    dst[0] = xis[2 * g];
+    dst[1] = xis[2 * g + 1];
+}
+
+// A proof that was still accepted takes the decider's verdict.
+__global__ __launch_bounds__(PV_THREADS) void k_plonk_decided(const uint8_t* __restrict__ live,
+                                                              const uint8_t* __restrict__ decided, size_t k,
+                                                              uint8_t* __restrict__ verdict) {
+    const size_t i = (size_t)blockIdx.x * PV_THREADS + threadIdx.x;
+    if (i >= k) return;
+    if (live[i]) verdict[i] = decided[i] ? HALO_PLONK_ACCEPT : HALO_PLONK_DECIDER;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -493,6 +563,17 @@ struct PlonkCall {  // the arguments of either entry point
     size_t rows, k, npi;
     const void *C_qs, *pub, *C_ws, *C_z, *C_ts, *vs, *Ls, *Rs, *U, *c, *prev_C, *prev_z, *prev_v, *next_C, *next_z, *next_v, *mds;
     void *verdict, *chal_out, *sides_out, *asdl_out;
+    // PlonkProof::verify only (full): acc_next.pi, the decider's weights (or null) and its `combined` byte (or null)
+    bool full = false;
+    const void *next_Ls = nullptr, *next_Rs = nullptr, *next_U = nullptr, *next_c = nullptr, *rho = nullptr;
+    void* combined = nullptr;
+};
+
+// What the decider of a full call reads, left in scratch by plonk_device (plonk_decide runs it, and runs it again
+// in exact mode when the host form's combined check failed).
+struct PlonkDecide {
+    const void *xis, *live;
+    void *decided, *combined;
 };
 
 static size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
@@ -510,8 +591,9 @@ static int check_plonk_args(const char* call, const PlonkCall& a, bool& done) {
     if (!a.C_qs || !a.C_ws || !a.C_z || !a.C_ts || !a.vs || !a.Ls || !a.Rs || !a.U || !a.c || !a.prev_C || !a.prev_z ||
         !a.prev_v || !a.next_C || !a.next_z || !a.next_v || !a.mds || !a.verdict || (a.npi && !a.pub))
         return set_error(HALO_EINVAL, "%s: null pointer", call);
-    const size_t lg = ilog2(a.rows);
-    if (a.k > LINCOMB_MAX_ITEMS / (3 * (2 * lg + 2)) || a.k > LINCOMB_MAX_ITEMS / R_TERMS || a.npi > (SIZE_MAX / 64) / a.k)
+    if (a.full && (!a.next_Ls || !a.next_Rs || !a.next_U || !a.next_c)) return set_error(HALO_EINVAL, "%s: null pointer", call);
+    const size_t lg = ilog2(a.rows), ipp = a.full ? 4 : 3;
+    if (a.k > LINCOMB_MAX_ITEMS / (ipp * (2 * lg + 2)) || a.k > LINCOMB_MAX_ITEMS / R_TERMS || a.npi > (SIZE_MAX / 64) / a.k)
         return set_error(HALO_EINVAL, "%s: %zu proofs in one call", call, a.k);
     if (!poseidon_params_set(base_field(a.curve)))
         return set_error(HALO_EINVAL, "%s: no Poseidon parameters for the curve's base field (halo_poseidon_set_params)",
@@ -527,10 +609,23 @@ static int check_plonk_srs(const char* call, const DeviceState* st, const PlonkC
     return HALO_OK;
 }
 
+// acc::decider of the proofs that are still accepted (rho null: exact mode), then their verdicts.
+static int plonk_decide(DeviceState* st, const PlonkCall& a, const PlonkDecide& pd, const void* rho, hipStream_t s) {
+    const DecideCall dc{a.curve, a.rows - 1, a.k, pd.xis, a.next_U, pd.live, rho, pd.decided, pd.combined};
+    HALO_CHECK(decide_device(st, dc, s));
+    hipLaunchKernelGGL(k_plonk_decided, dim3(grid_for(a.k, PV_THREADS)), dim3(PV_THREADS), 0, s, (const uint8_t*)pd.live,
+                       (const uint8_t*)pd.decided, a.k, (uint8_t*)a.verdict);
+    HALO_HIP(hipGetLastError());
+    return HALO_OK;
+}
+
 // The launches of one call over device pointers, all on `s`.  st->mu and a ScratchUse of `s` held; a.k >= 1,
-// check_plonk_srs passed.
-static int plonk_device(const char* call, DeviceState* st, const PlonkCall& a, hipStream_t s) {
-    const size_t k = a.k, lg = ilog2(a.rows), d = a.rows - 1, m = a.npi ? a.npi : 1;
+// check_plonk_srs passed.  ipp = 3 instances per proof (verify_succinct), or 4 with acc_next (a.full), whose PCDL
+// transcript then runs inside the same fs_device chain and whose decider follows (pd, when given, receives what
+// a second decider pass needs).
+static int plonk_device(const char* call, DeviceState* st, const PlonkCall& a, hipStream_t s, PlonkDecide* pd = nullptr) {
+    const size_t k = a.k, lg = ilog2(a.rows), d = a.rows - 1, m = a.npi ? a.npi : 1, ipp = a.full ? 4 : 3;
+    const size_t nx = a.full ? k : 0;  // proofs with a fourth instance
     const uint32_t* params;
     HALO_CHECK(poseidon_device_params(st, base_field(a.curve), &params));
     // one scratch buffer; the succinct checks work in scratch[7]
@@ -541,15 +636,17 @@ static int plonk_device(const char* call, DeviceState* st, const PlonkCall& a, h
         return o;
     };
     const size_t o_rp = take(k * R_TERMS * 64), o_rs = take(k * R_TERMS * 32), o_op = take(k * RO_TERMS * 64),
-                 o_os = take(k * RO_TERMS * 32), o_sr = take(k * 128), o_so = take(k * 128), o_ic = take(3 * k * 64),
-                 o_iz = take(3 * k * 32), o_iv = take(3 * k * 32), o_xis = take(3 * k * (lg + 1) * 32), o_den = take(k * m * 32),
-                 o_ap = take(3 * k * 64), o_as = take(3 * k * 32), o_neg = take(k * 64), o_sum = take(k * 128),
-                 o_chal = take(a.chal_out ? 0 : k * 5 * 32), o_sides = take(a.sides_out ? 0 : k * 2 * 32),
-                 o_asdl = take(a.asdl_out ? 0 : k * 2 * 32), o_mal = take(k), o_bits = take(k), o_ok3 = take(3 * k),
-                 o_cid = take(k);
+                 o_os = take(k * RO_TERMS * 32), o_sr = take(k * 128), o_so = take(k * 128), o_ic = take(ipp * k * 64),
+                 o_iz = take(ipp * k * 32), o_iv = take(ipp * k * 32), o_xis = take(ipp * k * (lg + 1) * 32),
+                 o_den = take(k * m * 32), o_ap = take(3 * k * 64), o_as = take(3 * k * 32), o_neg = take(k * 64),
+                 o_sum = take(k * 128), o_chal = take(a.chal_out ? 0 : k * 5 * 32),
+                 o_sides = take(a.sides_out ? 0 : k * 2 * 32), o_asdl = take(a.asdl_out ? 0 : k * 2 * 32), o_mal = take(k),
+                 o_bits = take(k), o_ok3 = take(ipp * k), o_cid = take(k), o_l4 = take(4 * nx * lg * 64),
+                 o_r4 = take(4 * nx * lg * 64), o_u4 = take(4 * nx * 64), o_c4 = take(4 * nx * 32),
+                 o_nxis = take(nx * (lg + 1) * 32), o_xis3 = take(3 * nx * (lg + 1) * 32), o_live = take(nx), o_dec = take(nx), o_comb = take(a.full ? 1 : 0);
     HALO_CHECK(st->scratch[6].reserve(off));
     // every linear combination of the chain, before anything is in flight
-    HALO_CHECK(st->lincomb_terms.reserve(k * std::max<size_t>(R_TERMS, 3 * (2 * lg + 2)) * 129));
+    HALO_CHECK(st->lincomb_terms.reserve(k * std::max<size_t>(R_TERMS, ipp * (2 * lg + 2)) * 129));
     uint8_t* base = st->scratch[6].as<uint8_t>();
     auto u4 = [&](size_t o) { return (uint4*)(base + o); };
     uint4* chal = a.chal_out ? (uint4*)a.chal_out : u4(o_chal);
@@ -588,8 +685,8 @@ static int plonk_device(const char* call, DeviceState* st, const PlonkCall& a, h
         DISPATCH_CURVE(a.curve, Cv, {
             HALO_LAUNCH(prof, k_plonk_identity<Cv>, per_proof, blk, 0, s, cp(a.vs), cp(a.pub), a.npi, (const uint4*)chal,
                         cp(a.mds), cp(a.C_qs), cp(a.C_ws), cp(a.C_z), cp(a.C_ts), cp(a.prev_z), cp(a.prev_v), cp(a.next_z),
-                        cp(a.next_v), cp(a.c), (unsigned)lg, k, u4(o_den), u4(o_rp), u4(o_rs), u4(o_op), u4(o_os), u4(o_iz),
-                        u4(o_iv), sides, bits, mal);
+                        cp(a.next_v), cp(a.c), (unsigned)lg, k, ipp, u4(o_den), u4(o_rp), u4(o_rs), u4(o_op), u4(o_os),
+                        u4(o_iz), u4(o_iv), sides, bits, mal);
         });
         HALO_HIP(hipGetLastError());
     }
@@ -597,37 +694,152 @@ static int plonk_device(const char* call, DeviceState* st, const PlonkCall& a, h
     HALO_CHECK(lincomb_device(st, a.curve, nullptr, u4(o_op), u4(o_os), k, RO_TERMS, u4(o_so), nullptr, s));
     DISPATCH_CURVE(a.curve, Cv, {
         hipLaunchKernelGGL(k_plonk_instances<Cv>, dim3(grid_for(3 * k, PV_THREADS)), blk, 0, s, cp(a.prev_C),
-                           (const uint4*)u4(o_sr), (const uint4*)u4(o_so), k, u4(o_ic));
+                           (const uint4*)u4(o_sr), (const uint4*)u4(o_so), k, ipp, u4(o_ic));
     });
     HALO_HIP(hipGetLastError());
-    const FsCall fs{a.curve, d, 3 * k, u4(o_ic), u4(o_iz), u4(o_iv), a.Ls, a.Rs, a.U, a.c, nullptr, nullptr, nullptr,
+    const void *fs_Ls = a.Ls, *fs_Rs = a.Rs, *fs_U = a.U, *fs_c = a.c;
+    if (a.full) {
+        hipLaunchKernelGGL(k_plonk_next, per_proof, blk, 0, s, cp(a.Ls), cp(a.Rs), cp(a.U), cp(a.c), cp(a.next_Ls),
+                           cp(a.next_Rs), cp(a.next_U), cp(a.next_c), cp(a.next_C), cp(a.next_z), cp(a.next_v), lg, k, u4(o_l4),
+                           u4(o_r4), u4(o_u4), u4(o_c4), u4(o_ic), u4(o_iz), u4(o_iv));
+        HALO_HIP(hipGetLastError());
+        fs_Ls = u4(o_l4), fs_Rs = u4(o_r4), fs_U = u4(o_u4), fs_c = u4(o_c4);
+    }
+    const FsCall fs{a.curve, d, ipp * k, u4(o_ic), u4(o_iz), u4(o_iv), fs_Ls, fs_Rs, fs_U, fs_c, nullptr, nullptr, nullptr,
                     u4(o_xis), nullptr, ok3};
     HALO_CHECK(fs_device(call, st, fs, s));
+    const uint4* xis3 = u4(o_xis);  // the challenges of the instances 3 i + 0 .. 2
+    if (a.full) {
+        hipLaunchKernelGGL(k_plonk_split_xis, dim3(grid_for(4 * k * (lg + 1), PV_THREADS)), blk, 0, s, (const uint4*)u4(o_xis),
+                           lg, k, u4(o_xis3), u4(o_nxis));
+        HALO_HIP(hipGetLastError());
+        xis3 = u4(o_xis3);
+    }
     {
         ProfScope prof("asdl_challenges", s);
         DISPATCH_CURVE(a.curve, Cv, {
             if (lanes == 1)
-                HALO_LAUNCH(prof, (k_asdl_challenges<Cv, 1>), dim3(g.blocks), dim3(g.threads), 0, s, params,
-                            (const uint4*)u4(o_xis), cp(a.U), lg, k, asdl);
+                HALO_LAUNCH(prof, (k_asdl_challenges<Cv, 1>), dim3(g.blocks), dim3(g.threads), 0, s, params, xis3,
+                            cp(a.U), lg, k, asdl);
             else
-                HALO_LAUNCH(prof, (k_asdl_challenges<Cv, 3>), dim3(g.blocks), dim3(g.threads), 0, s, params,
-                            (const uint4*)u4(o_xis), cp(a.U), lg, k, asdl);
+                HALO_LAUNCH(prof, (k_asdl_challenges<Cv, 3>), dim3(g.blocks), dim3(g.threads), 0, s, params, xis3,
+                            cp(a.U), lg, k, asdl);
         });
         HALO_HIP(hipGetLastError());
     }
     {
         ProfScope prof("asdl_terms", s);
         DISPATCH_CURVE(a.curve, Cv, {
-            HALO_LAUNCH(prof, k_asdl_terms<Cv>, per_proof, blk, 0, s, (const uint4*)asdl, (const uint4*)u4(o_xis), cp(a.U),
+            HALO_LAUNCH(prof, k_asdl_terms<Cv>, per_proof, blk, 0, s, (const uint4*)asdl, xis3, cp(a.U),
                         cp(a.next_C), cp(a.next_z), cp(a.next_v), lg, k, u4(o_ap), u4(o_as), u4(o_neg), bits);
         });
         HALO_HIP(hipGetLastError());
     }
     HALO_CHECK(lincomb_device(st, a.curve, u4(o_neg), u4(o_ap), u4(o_as), k, 3, u4(o_sum), cid, s));
     hipLaunchKernelGGL(k_plonk_verdict, per_proof, blk, 0, s, (const uint8_t*)mal, (const uint8_t*)bits, (const uint8_t*)ok3,
-                       (const uint8_t*)cid, k, (uint8_t*)a.verdict);
+                       (const uint8_t*)cid, k, ipp, (uint8_t*)a.verdict, a.full ? base + o_live : (uint8_t*)nullptr);
     HALO_HIP(hipGetLastError());
-    return HALO_OK;
+    if (!a.full) return HALO_OK;
+    const PlonkDecide dec{base + o_nxis, base + o_live, base + o_dec, a.combined ? a.combined : (void*)(base + o_comb)};
+    if (pd) *pd = dec;
+    return plonk_decide(st, a, dec, a.rho, s);
+}
+
+static bool fe_all_below(int curve, const halo_fe_t* x, size_t n) {
+    const uint64_t(&p)[4] = curve == HALO_PALLAS ? FpCfg::MODULUS64 : FqCfg::MODULUS64;  // the scalar field
+    for (size_t j = 0; j < n; j++) {
+        bool below = false;
+        for (int q = 3; q >= 0; q--)
+            if (x[j].l[q] != p[q]) {
+                below = x[j].l[q] < p[q];
+                break;
+            }
+        if (!below) return false;
+    }
+    return true;
+}
+
+// Either host entry point: the scalar checks, one buffer of inputs and one of outputs, the chain, and for a full
+// call the exact rerun of the deciders when the combined check failed.
+static int plonk_host(const char* call, const PlonkCall& host) {
+    bool done;
+    HALO_CHECK(check_plonk_args(call, host, done));
+    if (done) return HALO_OK;
+    const size_t k = host.k, npi = host.npi, lg = ilog2(host.rows);
+    auto fes = [](const void* p) { return (const halo_fe_t*)p; };
+    if (!fe_all_below(host.curve, fes(host.mds), 9)) return set_error(HALO_EINVAL, "%s: an MDS entry is not below the modulus", call);
+    for (size_t i = 0; i < k; i++)
+        if (!fe_all_below(host.curve, fes(host.vs) + N_VS * i, N_VS) || !fe_all_below(host.curve, fes(host.pub) + npi * i, npi) ||
+            !fe_all_below(host.curve, fes(host.c) + 3 * i, 3) || !fe_all_below(host.curve, fes(host.prev_z) + i, 1) ||
+            !fe_all_below(host.curve, fes(host.prev_v) + i, 1) || !fe_all_below(host.curve, fes(host.next_z) + i, 1) ||
+            !fe_all_below(host.curve, fes(host.next_v) + i, 1) || (host.full && !fe_all_below(host.curve, fes(host.next_c) + i, 1)))
+            return set_error(HALO_EINVAL, "%s: a scalar of proof %zu is not below the modulus", call, i);
+    for (size_t i = 0; host.rho && i < k; i++) {
+        const halo_fe_t& r = fes(host.rho)[i];
+        if (!(r.l[0] | r.l[1] | r.l[2] | r.l[3])) return set_error(HALO_EINVAL, "%s: rho[%zu] is zero", call, i);
+        if (!fe_all_below(host.curve, &r, 1)) return set_error(HALO_EINVAL, "%s: rho[%zu] is not below the modulus", call, i);
+    }
+    DeviceState* st = current_state();
+    if (!st) return HALO_EDEVICE;
+    std::lock_guard<std::mutex> g(st->mu);
+    HALO_CHECK(check_plonk_srs(call, st, host));
+    hipStream_t s = 0;
+    ScratchUse su(st, s);
+    const size_t nx = host.full ? k : 0;
+    struct Part {
+        const void* src;
+        size_t bytes, off;
+    } in[22] = {{host.C_qs, N_Q * 64, 0},     {host.pub, k * npi * 32, 0},   {host.C_ws, k * N_W * 64, 0},
+                {host.C_z, k * 64, 0},        {host.C_ts, k * N_T * 64, 0},  {host.vs, k * N_VS * 32, 0},
+                {host.Ls, k * 3 * lg * 64, 0}, {host.Rs, k * 3 * lg * 64, 0}, {host.U, k * 3 * 64, 0},
+                {host.c, k * 3 * 32, 0},      {host.prev_C, k * 64, 0},      {host.prev_z, k * 32, 0},
+                {host.prev_v, k * 32, 0},     {host.next_C, k * 64, 0},      {host.next_z, k * 32, 0},
+                {host.next_v, k * 32, 0},     {host.mds, 9 * 32, 0},         {host.next_Ls, nx * lg * 64, 0},
+                {host.next_Rs, nx * lg * 64, 0}, {host.next_U, nx * 64, 0},  {host.next_c, nx * 32, 0},
+                {host.rho, host.rho ? nx * 32 : 0, 0}};
+    size_t n_in = 0;
+    for (Part& q : in) {
+        q.off = n_in;
+        n_in += align256(q.bytes);
+    }
+    const size_t o_chal = 0, o_sides = o_chal + align256(host.chal_out ? k * 5 * 32 : 0),
+                 o_asdl = o_sides + align256(host.sides_out ? k * 2 * 32 : 0),
+                 o_v = o_asdl + align256(host.asdl_out ? k * 2 * 32 : 0);
+    HALO_CHECK(st->scratch[0].reserve(n_in));
+    HALO_CHECK(st->scratch[1].reserve(o_v + k));
+    uint8_t *di = st->scratch[0].as<uint8_t>(), *dout = st->scratch[1].as<uint8_t>();
+    for (const Part& q : in) HALO_CHECK(copy_h2d(di + q.off, q.src, q.bytes, s));
+    auto dev = [&](int j) -> const void* { return in[j].bytes ? di + in[j].off : nullptr; };
+    PlonkCall a{host.curve, host.rows, k,       npi,     dev(0),  dev(1),  dev(2),  dev(3),  dev(4),
+                dev(5),     dev(6),    dev(7),  dev(8),  dev(9),  dev(10), dev(11), dev(12), dev(13),
+                dev(14),    dev(15),   dev(16), dout + o_v, host.chal_out ? dout + o_chal : nullptr,
+                host.sides_out ? dout + o_sides : nullptr, host.asdl_out ? dout + o_asdl : nullptr};
+    a.full = host.full;
+    a.next_Ls = dev(17), a.next_Rs = dev(18), a.next_U = dev(19), a.next_c = dev(20), a.rho = dev(21);
+    PlonkDecide pd{};
+    HALO_CHECK(plonk_device(call, st, a, s, &pd));
+    if (a.full && a.rho && k > 1) {
+        uint8_t combined = 0;
+        HALO_CHECK(copy_d2h(&combined, pd.combined, 1, s));
+        if (!combined) HALO_CHECK(plonk_decide(st, a, pd, nullptr, s));  // some decider fails: the exact verdicts
+    }
+    if (host.chal_out) HALO_CHECK(copy_d2h(host.chal_out, dout + o_chal, k * 5 * 32, s));
+    if (host.sides_out) HALO_CHECK(copy_d2h(host.sides_out, dout + o_sides, k * 2 * 32, s));
+    if (host.asdl_out) HALO_CHECK(copy_d2h(host.asdl_out, dout + o_asdl, k * 2 * 32, s));
+    return copy_d2h(host.verdict, dout + o_v, k, s);
+}
+
+static int plonk_dev(const char* call, const PlonkCall& a, void* stream) {
+    bool done;
+    HALO_CHECK(check_plonk_args(call, a, done));
+    if (done) return HALO_OK;
+    DeviceState* st = current_state();
+    if (!st) return HALO_EDEVICE;
+    std::lock_guard<std::mutex> g(st->mu);
+    HALO_CHECK(check_plonk_srs(call, st, a));
+    hipStream_t s = (hipStream_t)stream;
+    ScratchUse su(st, s);
+    return plonk_device(call, st, a, s);
 }
 
 }  // namespace halo
@@ -641,20 +853,10 @@ extern "C" int halo_plonk_verify_succinct_batch_dev(
     const void* d_acc_next_z, const void* d_acc_next_v, const void* d_mds, void* d_verdict, void* d_challenges_out,
     void* d_sides_out, void* d_asdl_out, void* stream) {
     clear_error();
-    const char* call = "halo_plonk_verify_succinct_batch_dev";
     const PlonkCall a{(int)curve, rows, k, npi, d_C_qs, d_public_inputs, d_C_ws, d_C_z, d_C_ts, d_vs, d_Ls, d_Rs, d_U, d_c,
                       d_acc_prev_C, d_acc_prev_z, d_acc_prev_v, d_acc_next_C, d_acc_next_z, d_acc_next_v, d_mds,
                       d_verdict, d_challenges_out, d_sides_out, d_asdl_out};
-    bool done;
-    HALO_CHECK(check_plonk_args(call, a, done));
-    if (done) return HALO_OK;
-    DeviceState* st = current_state();
-    if (!st) return HALO_EDEVICE;
-    std::lock_guard<std::mutex> g(st->mu);
-    HALO_CHECK(check_plonk_srs(call, st, a));
-    hipStream_t s = (hipStream_t)stream;
-    ScratchUse su(st, s);
-    return plonk_device(call, st, a, s);
+    return plonk_dev("halo_plonk_verify_succinct_batch_dev", a, stream);
 }
 
 extern "C" int halo_plonk_verify_succinct_batch(
@@ -665,67 +867,42 @@ extern "C" int halo_plonk_verify_succinct_batch(
     const halo_wrapped_point_t* acc_next_C, const halo_fe_t* acc_next_z, const halo_fe_t* acc_next_v, const halo_fe_t* mds,
     uint8_t* verdict, halo_fe_t* challenges_out, halo_fe_t* sides_out, halo_fe_t* asdl_out) {
     clear_error();
-    const char* call = "halo_plonk_verify_succinct_batch";
     const PlonkCall host{(int)curve, rows, k, npi, C_qs, public_inputs, C_ws, C_z, C_ts, vs, Ls, Rs, U, c, acc_prev_C,
                          acc_prev_z, acc_prev_v, acc_next_C, acc_next_z, acc_next_v, mds, verdict, challenges_out, sides_out,
                          asdl_out};
-    bool done;
-    HALO_CHECK(check_plonk_args(call, host, done));
-    if (done) return HALO_OK;
-    const size_t lg = ilog2(rows);
-    const uint64_t(&p)[4] = curve == HALO_PALLAS ? FpCfg::MODULUS64 : FqCfg::MODULUS64;  // the scalar field
-    auto all_below = [&](const halo_fe_t* x, size_t n) {
-        for (size_t j = 0; j < n; j++) {
-            bool below = false;
-            for (int q = 3; q >= 0; q--)
-                if (x[j].l[q] != p[q]) {
-                    below = x[j].l[q] < p[q];
-                    break;
-                }
-            if (!below) return false;
-        }
-        return true;
-    };
-    if (!all_below(mds, 9)) return set_error(HALO_EINVAL, "%s: an MDS entry is not below the modulus", call);
-    for (size_t i = 0; i < k; i++)
-        if (!all_below(vs + N_VS * i, N_VS) || !all_below(public_inputs + npi * i, npi) || !all_below(c + 3 * i, 3) ||
-            !all_below(acc_prev_z + i, 1) || !all_below(acc_prev_v + i, 1) || !all_below(acc_next_z + i, 1) ||
-            !all_below(acc_next_v + i, 1))
-            return set_error(HALO_EINVAL, "%s: a scalar of proof %zu is not below the modulus", call, i);
-    DeviceState* st = current_state();
-    if (!st) return HALO_EDEVICE;
-    std::lock_guard<std::mutex> g(st->mu);
-    HALO_CHECK(check_plonk_srs(call, st, host));
-    hipStream_t s = 0;
-    ScratchUse su(st, s);
-    // one buffer of inputs and one of outputs
-    struct Part {
-        const void* src;
-        size_t bytes, off;
-    } in[17] = {{C_qs, N_Q * 64, 0},      {public_inputs, k * npi * 32, 0}, {C_ws, k * N_W * 64, 0}, {C_z, k * 64, 0},
-                {C_ts, k * N_T * 64, 0},  {vs, k * N_VS * 32, 0},           {Ls, k * 3 * lg * 64, 0}, {Rs, k * 3 * lg * 64, 0},
-                {U, k * 3 * 64, 0},       {c, k * 3 * 32, 0},               {acc_prev_C, k * 64, 0},  {acc_prev_z, k * 32, 0},
-                {acc_prev_v, k * 32, 0},  {acc_next_C, k * 64, 0},          {acc_next_z, k * 32, 0},  {acc_next_v, k * 32, 0},
-                {mds, 9 * 32, 0}};
-    size_t n_in = 0;
-    for (Part& q : in) {
-        q.off = n_in;
-        n_in += align256(q.bytes);
-    }
-    const size_t o_chal = 0, o_sides = o_chal + align256(challenges_out ? k * 5 * 32 : 0),
-                 o_asdl = o_sides + align256(sides_out ? k * 2 * 32 : 0), o_v = o_asdl + align256(asdl_out ? k * 2 * 32 : 0);
-    HALO_CHECK(st->scratch[0].reserve(n_in));
-    HALO_CHECK(st->scratch[1].reserve(o_v + k));
-    uint8_t *di = st->scratch[0].as<uint8_t>(), *dout = st->scratch[1].as<uint8_t>();
-    for (const Part& q : in) HALO_CHECK(copy_h2d(di + q.off, q.src, q.bytes, s));
-    auto dev = [&](int j) -> const void* { return in[j].bytes ? di + in[j].off : nullptr; };
-    const PlonkCall a{(int)curve, rows,    k,       npi,     dev(0),  dev(1),  dev(2),  dev(3),  dev(4),
-                      dev(5),     dev(6),  dev(7),  dev(8),  dev(9),  dev(10), dev(11), dev(12), dev(13),
-                      dev(14),    dev(15), dev(16), dout + o_v, challenges_out ? dout + o_chal : nullptr,
-                      sides_out ? dout + o_sides : nullptr, asdl_out ? dout + o_asdl : nullptr};
-    HALO_CHECK(plonk_device(call, st, a, s));
-    if (challenges_out) HALO_CHECK(copy_d2h(challenges_out, dout + o_chal, k * 5 * 32, s));
-    if (sides_out) HALO_CHECK(copy_d2h(sides_out, dout + o_sides, k * 2 * 32, s));
-    if (asdl_out) HALO_CHECK(copy_d2h(asdl_out, dout + o_asdl, k * 2 * 32, s));
-    return copy_d2h(verdict, dout + o_v, k, s);
+    return plonk_host("halo_plonk_verify_succinct_batch", host);
+}
+
+extern "C" int halo_plonk_verify_batch_dev(
+    halo_curve_t curve, size_t rows, size_t k, const void* d_C_qs, const void* d_public_inputs, size_t npi, const void* d_C_ws,
+    const void* d_C_z, const void* d_C_ts, const void* d_vs, const void* d_Ls, const void* d_Rs, const void* d_U, const void* d_c,
+    const void* d_acc_prev_C, const void* d_acc_prev_z, const void* d_acc_prev_v, const void* d_acc_next_C,
+    const void* d_acc_next_z, const void* d_acc_next_v, const void* d_acc_next_Ls, const void* d_acc_next_Rs,
+    const void* d_acc_next_U, const void* d_acc_next_c, const void* d_mds, const void* d_rho, void* d_verdict,
+    void* d_combined, void* stream) {
+    clear_error();
+    PlonkCall a{(int)curve, rows, k, npi, d_C_qs, d_public_inputs, d_C_ws, d_C_z, d_C_ts, d_vs, d_Ls, d_Rs, d_U, d_c,
+                d_acc_prev_C, d_acc_prev_z, d_acc_prev_v, d_acc_next_C, d_acc_next_z, d_acc_next_v, d_mds,
+                d_verdict, nullptr, nullptr, nullptr};
+    a.full = true;
+    a.next_Ls = d_acc_next_Ls, a.next_Rs = d_acc_next_Rs, a.next_U = d_acc_next_U, a.next_c = d_acc_next_c;
+    a.rho = d_rho, a.combined = d_combined;
+    return plonk_dev("halo_plonk_verify_batch_dev", a, stream);
+}
+
+extern "C" int halo_plonk_verify_batch(
+    halo_curve_t curve, size_t rows, size_t k, const halo_wrapped_point_t* C_qs, const halo_fe_t* public_inputs, size_t npi,
+    const halo_wrapped_point_t* C_ws, const halo_wrapped_point_t* C_z, const halo_wrapped_point_t* C_ts, const halo_fe_t* vs,
+    const halo_wrapped_point_t* Ls, const halo_wrapped_point_t* Rs, const halo_wrapped_point_t* U, const halo_fe_t* c,
+    const halo_wrapped_point_t* acc_prev_C, const halo_fe_t* acc_prev_z, const halo_fe_t* acc_prev_v,
+    const halo_wrapped_point_t* acc_next_C, const halo_fe_t* acc_next_z, const halo_fe_t* acc_next_v,
+    const halo_wrapped_point_t* acc_next_Ls, const halo_wrapped_point_t* acc_next_Rs, const halo_wrapped_point_t* acc_next_U,
+    const halo_fe_t* acc_next_c, const halo_fe_t* mds, const halo_fe_t* rho, uint8_t* verdict) {
+    clear_error();
+    PlonkCall host{(int)curve, rows, k, npi, C_qs, public_inputs, C_ws, C_z, C_ts, vs, Ls, Rs, U, c, acc_prev_C,
+                   acc_prev_z, acc_prev_v, acc_next_C, acc_next_z, acc_next_v, mds, verdict, nullptr, nullptr, nullptr};
+    host.full = true;
+    host.next_Ls = acc_next_Ls, host.next_Rs = acc_next_Rs, host.next_U = acc_next_U, host.next_c = acc_next_c;
+    host.rho = rho;
+    return plonk_host("halo_plonk_verify_batch", host);
 }

@@ -390,34 +390,92 @@ __global__ void k_hpoly_coeffs(const uint4* t_lo, const uint4* t_hi, size_t k, u
     const size_t nlo = (size_t)1 << lb, nhi = (size_t)1 << (lg_n - lb);
     const size_t lo = j & (nlo - 1), hi = j >> lb;
     Fe<F> acc = fe_zero<F>();
-    for (size_t i = 0; i < k; i++)
-        acc = fe_add(acc, fe_mul(fe_load<F>(t_lo + 2 * (i * nlo + lo)), fe_load<F>(t_hi + 2 * (i * nhi + hi))));
+    size_t i = 0;
+    // two polynomials per step as one double product with one reduction (entries are < 2p: the sum is far below
+    // fe_mul2's bound of ~127 p^2)
+    for (; i + 1 < k; i += 2)
+        acc = fe_add(acc, fe_mul2(fe_load<F>(t_lo + 2 * (i * nlo + lo)), fe_load<F>(t_hi + 2 * (i * nhi + hi)),
+                                  fe_load<F>(t_lo + 2 * ((i + 1) * nlo + lo)), fe_load<F>(t_hi + 2 * ((i + 1) * nhi + hi))));
+    if (i < k) acc = fe_add(acc, fe_mul(fe_load<F>(t_lo + 2 * (i * nlo + lo)), fe_load<F>(t_hi + 2 * (i * nhi + hi))));
     fe_to_ark(out_ark + 2 * j, acc);
 }
 
-// k h-polynomials (xis: k rows of n_xis ark elements) -> sum_i alpha_i h_i coefficients (ark) at d_out
+// One coefficient row per polynomial instead of their sum: rows[i n + j] = coefficient j of h_i (ark, the form
+// k_digits reads), one multiplication per coefficient from the same two half-tables (built without weights).
+template <class F>
+__global__ __launch_bounds__(256) void k_hpoly_rows(const uint4* __restrict__ t_lo, const uint4* __restrict__ t_hi, size_t g,
+                                                    uint32_t lg_n, uint32_t lb, uint4* __restrict__ rows_ark) {
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if ((idx >> lg_n) >= g) return;
+    const size_t nlo = (size_t)1 << lb, nhi = (size_t)1 << (lg_n - lb);
+    const size_t i = idx >> lg_n, j = idx & (((size_t)1 << lg_n) - 1);
+    const size_t lo = j & (nlo - 1), hi = j >> lb;
+    fe_to_ark(rows_ark + 2 * idx, fe_mul(fe_load<F>(t_lo + 2 * (i * nlo + lo)), fe_load<F>(t_hi + 2 * (i * nhi + hi))));
+}
+
+namespace halo {
+
+size_t hpoly_table_elems(size_t k, uint32_t lg_n) {
+    const uint32_t lb = lg_n / 2;
+    return k * (((size_t)1 << lb) + ((size_t)1 << (lg_n - lb)));
+}
+
+static void hpoly_tables_launch(int field, const void* d_xis, size_t k, uint32_t lg_n, const void* d_alphas, uint4* t_lo,
+                                uint4* t_hi, hipStream_t s) {
+    const uint32_t lb = lg_n / 2;
+    const size_t nlo = (size_t)1 << lb, nhi = (size_t)1 << (lg_n - lb);
+    DISPATCH_FIELD(field, F, {
+        hipLaunchKernelGGL(k_hpoly_tables<F>, dim3(grid_for(k * (nlo + nhi), 128)), dim3(128), 0, s, (const uint4*)d_xis, k,
+                           lg_n, lb, (const uint4*)d_alphas, t_lo, t_hi);
+    });
+}
+
+// sum_i alpha_i h_i coefficients (ark, 2^lg_n entries) at d_out from k xi rows (lg_n + 1 ark elements each) and
+// k weights (or null) that are device pointers; d_tables: hpoly_table_elems(k, lg_n) elements.  On stream s.
+int hpoly_combine_device(int field, const void* d_xis, size_t k, uint32_t lg_n, const void* d_alphas, void* d_tables,
+                         void* d_out, hipStream_t s, const char* prof_name) {
+    const uint32_t lb = lg_n / 2;
+    uint4* t_lo = (uint4*)d_tables;
+    uint4* t_hi = t_lo + 2 * k * ((size_t)1 << lb);
+    hpoly_tables_launch(field, d_xis, k, lg_n, d_alphas, t_lo, t_hi, s);
+    ProfScope prof(prof_name, s);
+    DISPATCH_FIELD(field, F, {
+        HALO_LAUNCH(prof, k_hpoly_coeffs<F>, dim3(grid_for((size_t)1 << lg_n, 256)), dim3(256), 0, s, (const uint4*)t_lo,
+                    (const uint4*)t_hi, k, lg_n, lb, (uint4*)d_out);
+    });
+    HALO_HIP(hipGetLastError());
+    return HALO_OK;
+}
+
+// The g coefficient rows of h_0 .. h_(g-1) (ark, g 2^lg_n entries) at d_rows; g 2^lg_n < 2^32.  On stream s.
+int hpoly_rows_device(int field, const void* d_xis, size_t g, uint32_t lg_n, void* d_tables, void* d_rows, hipStream_t s) {
+    const uint32_t lb = lg_n / 2;
+    uint4* t_lo = (uint4*)d_tables;
+    uint4* t_hi = t_lo + 2 * g * ((size_t)1 << lb);
+    hpoly_tables_launch(field, d_xis, g, lg_n, nullptr, t_lo, t_hi, s);
+    ProfScope prof("hpoly_rows", s);
+    DISPATCH_FIELD(field, F, {
+        HALO_LAUNCH(prof, k_hpoly_rows<F>, dim3(grid_for(g << lg_n, 256)), dim3(256), 0, s, (const uint4*)t_lo,
+                    (const uint4*)t_hi, g, lg_n, lb, (uint4*)d_rows);
+    });
+    HALO_HIP(hipGetLastError());
+    return HALO_OK;
+}
+
+}  // namespace halo
+
+// k h-polynomials (xis: k rows of n_xis ark elements, host) -> sum_i alpha_i h_i coefficients (ark) at d_out
 // (2^(n_xis - 1) entries), on stream s.  Uses scratch[6] for the xis/alphas and tables.
 static int hpoly_device(DeviceState* st, int field, const halo_fe_t* xis, size_t k, size_t n_xis,
                         const halo_fe_t* alphas, void* d_out, hipStream_t s) {
     const uint32_t lg_n = (uint32_t)(n_xis - 1);
-    const uint32_t lb = lg_n / 2;
-    const size_t nlo = (size_t)1 << lb, nhi = (size_t)1 << (lg_n - lb);
     const size_t in_elems = k * n_xis + (alphas ? k : 0);
-    HALO_CHECK(st->scratch[6].reserve((in_elems + k * (nlo + nhi)) * 32));
+    HALO_CHECK(st->scratch[6].reserve((in_elems + hpoly_table_elems(k, lg_n)) * 32));
     uint4* d_xis = st->scratch[6].as<uint4>();
     uint4* d_alpha = alphas ? d_xis + 2 * k * n_xis : nullptr;
-    uint4* t_lo = d_xis + 2 * in_elems;
-    uint4* t_hi = t_lo + 2 * k * nlo;
     HALO_CHECK(copy_h2d(d_xis, xis, k * n_xis * 32, s));
     if (alphas) HALO_CHECK(copy_h2d(d_alpha, alphas, k * 32, s));
-    DISPATCH_FIELD(field, F, {
-        hipLaunchKernelGGL(k_hpoly_tables<F>, dim3(grid_for(k * (nlo + nhi), 128)), dim3(128), 0, s, (const uint4*)d_xis, k,
-                           lg_n, lb, (const uint4*)d_alpha, t_lo, t_hi);
-        hipLaunchKernelGGL(k_hpoly_coeffs<F>, dim3(grid_for((size_t)1 << lg_n, 256)), dim3(256), 0, s, (const uint4*)t_lo,
-                           (const uint4*)t_hi, k, lg_n, lb, (uint4*)d_out);
-    });
-    HALO_HIP(hipGetLastError());
-    return HALO_OK;
+    return hpoly_combine_device(field, d_xis, k, lg_n, d_alpha, d_xis + 2 * in_elems, d_out, s, nullptr);
 }
 
 extern "C" int halo_hpoly_combine(halo_field_t field, const halo_fe_t* xis, size_t k, size_t n_xis,

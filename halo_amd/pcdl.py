@@ -563,14 +563,9 @@ def succinct_check_fs_verdicts(Cs, d: int, zs, vs, Ls, Rs, Us, cs, hiding=None, 
     return ok, xis, alphas
 
 
-def succinct_check_device(instances, curve="pallas"):
-    """succinct_check_many without transcripts: the device derives every challenge itself
-    (halo_pcdl_succinct_check_fs_batch, one call per distinct d).  Returns [(HPoly, U)]; raises CheckFailed
-    naming the first failing instance."""
+def _check_shapes(insts, cid: int) -> None:
+    """What succinct_check asserts before any device call (pcdl.rs:491-494), for every instance of a list."""
     from .group import PublicParams
-    H.ensure_device()
-    cid = _curve(curve)
-    insts = [Instance(*q) for q in instances]
     D = PublicParams.len(cid) - 1
     for i, q in enumerate(insts):
         n = q.d + 1
@@ -581,6 +576,16 @@ def succinct_check_device(instances, curve="pallas"):
         lg = n.bit_length() - 1
         if len(H.point_array(q.pi["Ls"])) != lg or len(H.point_array(q.pi["Rs"])) != lg:
             raise ValueError(f"instance {i}: the proof has {len(q.pi['Ls'])} rounds, d = {q.d} needs {lg}")
+
+
+def succinct_check_device(instances, curve="pallas"):
+    """succinct_check_many without transcripts: the device derives every challenge itself
+    (halo_pcdl_succinct_check_fs_batch, one call per distinct d).  Returns [(HPoly, U)]; raises CheckFailed
+    naming the first failing instance."""
+    H.ensure_device()
+    cid = _curve(curve)
+    insts = [Instance(*q) for q in instances]
+    _check_shapes(insts, cid)
     ok = np.zeros(len(insts), dtype=np.uint8)
     xis = [None] * len(insts)
     zero_pt, zero_fe = np.zeros(8, dtype=np.uint64), np.zeros(4, dtype=np.uint64)
@@ -615,6 +620,83 @@ def check_device(C, d: int, z, v, pi: dict, curve="pallas") -> None:
         raise CheckFailed(e.msg) from None
     if not np.array_equal(decider_commit(h.xis, d, curve), U):
         raise CheckFailed(DECIDER_MSG)
+
+
+def decide_batch(xis, Us, d: int, rhos=None, live=None, curve="pallas") -> np.ndarray:
+    """halo_pcdl_decide_batch: acc::decider for k instances of degree bound d.  xis (k, lg n + 1, 4) challenges
+    (the layout succinct_check_fs_verdicts returns), Us (k, 8).  rhos None: one commitment per instance (exact
+    mode); rhos (k, 4) nonzero scalars drawn by the caller AFTER the proofs were fixed: one random linear
+    combination and one MSM, with an exact rerun if it fails.  live: k flags, 0 skips the instance (verdict 0).
+    Returns k bytes, 1 where U == CM.Commit(ck, h_vec)."""
+    H.ensure_device()
+    U = H.point_array(Us)
+    k = len(U)
+    lg = (d + 1).bit_length() - 1
+    ok = np.zeros(k, dtype=np.uint8)
+    lv = np.ascontiguousarray(np.asarray(live, dtype=np.uint8).reshape(k)) if live is not None else None
+    rh = H.fe_array(rhos, k) if rhos is not None else None
+    H.check(H.load().halo_pcdl_decide_batch(_curve(curve), d, k, H.ptr(H.fe_array(xis, k * (lg + 1))), H.ptr(U), H.ptr(lv),
+                                            H.ptr(rh), H.ptr(ok)))
+    return ok
+
+
+def check_fs_codes(Cs, d: int, zs, vs, Ls, Rs, Us, cs, hiding=None, C_bars=None, w_primes=None, rhos=None,
+                   curve="pallas") -> np.ndarray:
+    """halo_pcdl_check_fs_batch: pcdl::check of k raw instances of degree bound d (the arguments of
+    succinct_check_fs_verdicts, plus rhos as in decide_batch).  Returns k codes: 0 accept, 1 the succinct check
+    failed, 2 the decider failed."""
+    H.ensure_device()
+    C = H.point_array(Cs)
+    k = len(C)
+    lg = (d + 1).bit_length() - 1
+    code = np.zeros(k, dtype=np.uint8)
+    hid = cb = wp = None
+    if hiding is not None:
+        hid = np.ascontiguousarray(np.asarray(hiding, dtype=np.uint8).reshape(k))
+        cb, wp = H.point_array(C_bars), H.fe_array(w_primes, k)
+        assert len(cb) == k
+    rh = H.fe_array(rhos, k) if rhos is not None else None
+    H.check(H.load().halo_pcdl_check_fs_batch(
+        _curve(curve), d, k, H.ptr(C), H.ptr(H.fe_array(zs, k)), H.ptr(H.fe_array(vs, k)),
+        H.ptr(H.point_array(Ls)) if lg else None, H.ptr(H.point_array(Rs)) if lg else None, H.ptr(H.point_array(Us)),
+        H.ptr(H.fe_array(cs, k)), H.ptr(hid), H.ptr(cb), H.ptr(wp), H.ptr(rh), H.ptr(code)))
+    return code
+
+
+def check_batch(instances, rhos=None, curve="pallas", verdicts: bool = False):
+    """pcdl::check (pcdl.rs:563-583) for many instances (C, d, z, v, pi), every transcript and every decider on
+    the device: one halo_pcdl_check_fs_batch call per distinct d.  rhos: one nonzero scalar per instance, drawn
+    by the caller after the proofs were fixed (decide_batch), or None for exact deciders.  Raises
+    CheckFailed(msg, index) for the first failing instance; with verdicts=True returns the codes instead
+    (0 accept, 1 succinct check, 2 decider) and raises only for a d beyond the SRS."""
+    H.ensure_device()
+    cid = _curve(curve)
+    insts = [Instance(*q) for q in instances]
+    rh = H.fe_array(rhos, len(insts)) if rhos is not None else None
+    _check_shapes(insts, cid)
+    codes = np.zeros(len(insts), dtype=np.uint8)
+    zero_pt, zero_fe = np.zeros(8, dtype=np.uint64), np.zeros(4, dtype=np.uint64)
+    for d in sorted({q.d for q in insts}):
+        idx = [i for i, q in enumerate(insts) if q.d == d]
+        qs = [insts[i] for i in idx]
+        hid = [q.pi.get("C_bar") is not None for q in qs]
+        codes[idx] = check_fs_codes(
+            np.stack([H.point_array(q.C).reshape(8) for q in qs]), d, np.stack([H.fe_array(q.z, 1)[0] for q in qs]),
+            np.stack([H.fe_array(q.v, 1)[0] for q in qs]),
+            np.concatenate([H.point_array(q.pi["Ls"]) for q in qs]) if d else None,
+            np.concatenate([H.point_array(q.pi["Rs"]) for q in qs]) if d else None,
+            np.stack([H.point_array(q.pi["U"]).reshape(8) for q in qs]),
+            np.stack([H.fe_array(q.pi["c"], 1)[0] for q in qs]),
+            hiding=hid if any(hid) else None,
+            C_bars=np.stack([H.point_array(q.pi["C_bar"]).reshape(8) if h else zero_pt for q, h in zip(qs, hid)]),
+            w_primes=np.stack([H.fe_array(q.pi["w_prime"], 1)[0] if h else zero_fe for q, h in zip(qs, hid)]),
+            rhos=rh[idx] if rh is not None else None, curve=cid)
+    if verdicts:
+        return codes
+    for i, c in enumerate(codes):
+        if c:
+            raise CheckFailed(SUCCINCT_MSG if c == 1 else DECIDER_MSG, i)
+    return None
 
 
 def trace_commit_batch(evals, d: int, curve="pallas", want_coeffs: bool = False):

@@ -1,6 +1,7 @@
 """Mirror of ``PlonkProof::verify_succinct`` / ``verify`` (crates/plonk/src/plonk/protocol.rs:357-502) on the
 MI355X backend: batches of raw proofs of one circuit, every Fiat-Shamir transcript (PLONK, PCDL, ASDL) derived
-on the device (halo_plonk_verify_succinct_batch, halo_amd/csrc/plonk_verify.hip).
+on the device (halo_plonk_verify_succinct_batch, halo_amd/csrc/plonk_verify.hip); ``verify_batch`` adds the deciders
+of the batch's accumulators in the same call (halo_plonk_verify_batch, halo_amd/csrc/decider.hip).
 
 Points are WrappedPoints (8 u64), scalars ark Montgomery limbs (4 u64), as everywhere in halo_amd.  The proofs
 do not hide (naive_prover and acc::prover open with w = None).
@@ -20,11 +21,12 @@ from .prover import Q_POLYS, R_POLYS, S_POLYS, T_POLYS, W_POLYS
 N_EVALS = W_POLYS + R_POLYS + Q_POLYS + T_POLYS + 2 * S_POLYS + 2 + 3  # HALO_PLONK_EVALS
 
 # halo_plonk_verdict_t
-ACCEPT, IDENTITY, INSTANCE_0, INSTANCE_1, INSTANCE_2, C_BAR, Z, V, MALFORMED = range(9)
+ACCEPT, IDENTITY, INSTANCE_0, INSTANCE_1, INSTANCE_2, C_BAR, Z, V, MALFORMED, DECIDER_SUCCINCT, DECIDER = range(11)
 IDENTITY_MSG = "T(𝔷) ≠ (F_GC(𝔷) + α F_CC1(𝔷) + α² F_CC2(𝔷) + α³ F_PL1(𝔷) + α⁴ F_PL2(𝔷)) / Zₕ(𝔷)"
 MESSAGES = {IDENTITY: IDENTITY_MSG, INSTANCE_0: pcdl.SUCCINCT_MSG, INSTANCE_1: pcdl.SUCCINCT_MSG,
             INSTANCE_2: pcdl.SUCCINCT_MSG, C_BAR: "C_bar' ≠ C_bar", Z: "z' = z", V: "h(z) = v",
-            MALFORMED: "malformed proof: a point off the curve or a zero denominator at xi"}
+            MALFORMED: "malformed proof: a point off the curve or a zero denominator at xi",
+            DECIDER_SUCCINCT: pcdl.SUCCINCT_MSG, DECIDER: pcdl.DECIDER_MSG}
 
 
 class PlonkProofEvals(NamedTuple):
@@ -174,6 +176,37 @@ def verify_succinct_batch(circuit: PlonkCircuit, public_inputs, acc_prevs, proof
         _curve(curve), circuit.rows, k, H.ptr(a["C_qs"]), H.ptr(a["public_inputs"]), circuit.public_input_count,
         *[H.ptr(a[name]) for name in ARG_ORDER], H.ptr(verdict), H.ptr(chal), H.ptr(sides), H.ptr(asdl)))
     return (verdict, chal, sides, asdl) if readbacks else verdict
+
+
+def verify_batch(circuit: PlonkCircuit, public_inputs, acc_prevs, proofs, rhos=None, curve="pallas") -> np.ndarray:
+    """PlonkProof::verify (protocol.rs:493-502) of k proofs of one circuit in one device call
+    (halo_plonk_verify_batch): verify_succinct, then acc::decider of every acc_next, whose PCDL transcript runs
+    beside the proof's three instances.  rhos None: one commitment per decider; rhos (k, 4) nonzero scalars
+    drawn by the caller AFTER the proofs were fixed: one random linear combination of the deciders and one MSM,
+    with an exact rerun if it fails (pcdl.decide_batch).  Returns the k verdict bytes: the verify_succinct code
+    if nonzero, else DECIDER_SUCCINCT, DECIDER or ACCEPT."""
+    a = pack_batch(circuit, public_inputs, acc_prevs, proofs)
+    k = len(proofs)
+    verdict = np.zeros(k, dtype=np.uint8)
+    if k == 0:
+        return verdict
+    lg = circuit.rows.bit_length() - 1
+    pis = [Instance(*p.acc_next).pi for p in proofs]
+    for pi in pis:
+        if len(H.point_array(pi["Ls"])) != lg or len(H.point_array(pi["Rs"])) != lg:
+            raise ValueError(f"acc_next's evaluation proof has {len(pi['Ls'])} rounds, {circuit.rows} rows need {lg}")
+    nLs = np.ascontiguousarray(np.stack([H.point_array(pi["Ls"]).reshape(lg, 8) for pi in pis]))
+    nRs = np.ascontiguousarray(np.stack([H.point_array(pi["Rs"]).reshape(lg, 8) for pi in pis]))
+    nU = np.ascontiguousarray(np.stack([H.point_array(pi["U"]).reshape(8) for pi in pis]))
+    nc = np.ascontiguousarray(np.stack([H.fe_array(pi["c"], 1)[0] for pi in pis]))
+    rh = H.fe_array(rhos, k) if rhos is not None else None
+    H.ensure_device()
+    names = ARG_ORDER[:-1]  # mds comes after acc_next's evaluation proof
+    H.check(H.load().halo_plonk_verify_batch(
+        _curve(curve), circuit.rows, k, H.ptr(a["C_qs"]), H.ptr(a["public_inputs"]), circuit.public_input_count,
+        *[H.ptr(a[name]) for name in names], H.ptr(nLs), H.ptr(nRs), H.ptr(nU), H.ptr(nc), H.ptr(a["mds"]), H.ptr(rh),
+        H.ptr(verdict)))
+    return verdict
 
 
 def verify_succinct(proof: PlonkProof, circuit: PlonkCircuit, public_inputs, acc_prev, curve="pallas") -> None:

@@ -82,7 +82,8 @@ int halo_stream_sync(void* stream);
  * buffers; default 2^30), "ipa_pair_max" (weighted rounds up to this half-length form L and R as one
  * MSM; default 2^19), "ntt_big_max_log" (NTTs up to 2^this use 11-bit passes; default 22),
  * "ntt_even_split" (1: stages split evenly over the passes; default 0), "poseidon_lanes" (lanes per sponge
- * of the batched Poseidon kernels, 1 or 3; default 0: by batch size).  Every setting yields the same results; the parity tests pin each path with it.  The
+ * of the batched Poseidon kernels, 1 or 3; default 0: by batch size), "decide_group_scalars" (the exact batched
+ * decider commits its instances in groups whose coefficient rows hold at most this many scalars; default 2^25).  Every setting yields the same results; the parity tests pin each path with it.  The
  * reference has no counterpart (host-side knob of this backend only).  HALO_EINVAL on an unknown key. */
 int halo_set_tuning(const char* key, long long value);
 int halo_get_tuning(const char* key, long long* value);
@@ -501,6 +502,48 @@ int halo_pcdl_succinct_check_fs_batch_dev(halo_curve_t curve, size_t d, size_t k
         const void* d_v, const void* d_Ls, const void* d_Rs, const void* d_U, const void* d_c, const void* d_hiding,
         const void* d_C_bar, const void* d_w_prime, void* d_xis_out, void* d_alpha_out, void* d_ok, void* stream);
 
+/* acc::decider for k instances of one degree bound d (n = d + 1 a power of two): ok_out[i] = 1 iff
+ * U[i] == Commit(Gs[0..d], h_i.coeffs), h_i from xis[i (lg n + 1) + j] = xi_j (the layout xis_out returns; xi_0 is
+ * not read).  live (may be NULL: all) live[i] = 0 skips instance i, verdict 0.  A U that is neither (0, 0) nor on
+ * the curve gives verdict 0.  A zero xi is legal: h then has zero coefficients, as DensePolynomial would trim.
+ * rho NULL, or k = 1: exact mode, one commitment per instance, in groups whose coefficient rows hold at most
+ * the tuning key "decide_group_scalars" scalars (default 2^25); up to "msm_multi_max" coefficients a group is one
+ * MSM, above it pipelined ones.
+ * rho given (k scalars of `curve`): combined mode, sum_i rho_i U_i == Commit(sum_i rho_i h_i) over the live
+ * instances, ONE MSM whatever k.  If that fails the live instances are decided again in exact mode, so the
+ * verdicts are always per instance and exact for rejects.  An accept in combined mode is sound up to a prover
+ * guessing rho (probability about k / 2^254 over a uniform choice): rho must be drawn AFTER the proofs are
+ * fixed, uniformly, from the caller's random number generator -- the library draws no randomness.
+ * Before any device work: HALO_ENOTPOW2 "n ({n}) is not a power of two", HALO_EINVAL for a null required pointer,
+ * an xi that is not below the modulus, a rho entry that is zero (its instance would go unchecked) or not below
+ * the modulus; then HALO_ESRSRANGE "d was larger than D!".  k = 0: HALO_OK. */
+int halo_pcdl_decide_batch(halo_curve_t curve, size_t d, size_t k, const halo_fe_t* xis, const halo_wrapped_point_t* U,
+                           const uint8_t* live, const halo_fe_t* rho, uint8_t* ok_out);
+/* The same over device pointers, asynchronous on `stream`, no host wait.  d_combined (1 byte, may be NULL) is
+ * written only with d_rho: 1 iff the combined check held.  It never falls back: with d_combined = 0 every d_ok
+ * byte is 0 and the caller calls again with d_rho NULL.  Skipped instances are still computed in exact mode (the
+ * host form leaves them out).  A rho or xi that is not below the modulus gives combined = 0 / an unspecified
+ * verdict for its instance. */
+int halo_pcdl_decide_batch_dev(halo_curve_t curve, size_t d, size_t k, const void* d_xis, const void* d_U,
+                               const void* d_live, const void* d_rho, void* d_ok, void* d_combined, void* stream);
+/* pcdl::check (pcdl.rs:563-583) for k raw instances: halo_pcdl_succinct_check_fs_batch, then the decider above
+ * with live = the succinct verdicts, the challenges never leaving the device.  The inputs and errors of
+ * halo_pcdl_succinct_check_fs_batch, plus rho (NULL: exact mode) with the rule and the errors of
+ * halo_pcdl_decide_batch.  ok_out[i]: 0 accept, 1 the succinct check failed ("C_(log_n) != CM.Commit_Sigma(c || v')"),
+ * 2 the decider failed ("U != CM.Commit(ck, h_vec)"). */
+int halo_pcdl_check_fs_batch(halo_curve_t curve, size_t d, size_t k,
+        const halo_wrapped_point_t* C, const halo_fe_t* z, const halo_fe_t* v,
+        const halo_wrapped_point_t* Ls, const halo_wrapped_point_t* Rs,
+        const halo_wrapped_point_t* U, const halo_fe_t* c,
+        const uint8_t* hiding, const halo_wrapped_point_t* C_bar, const halo_fe_t* w_prime,
+        const halo_fe_t* rho, uint8_t* ok_out);
+/* The same over device pointers, asynchronous on `stream`; d_combined as in halo_pcdl_decide_batch_dev: with
+ * d_rho and d_combined = 0 the codes 2 are not verdicts (every instance that passed the succinct check has one)
+ * and the caller calls again with d_rho NULL. */
+int halo_pcdl_check_fs_batch_dev(halo_curve_t curve, size_t d, size_t k, const void* d_C, const void* d_z,
+        const void* d_v, const void* d_Ls, const void* d_Rs, const void* d_U, const void* d_c, const void* d_hiding,
+        const void* d_C_bar, const void* d_w_prime, const void* d_rho, void* d_ok, void* d_combined, void* stream);
+
 /* ------------------------------------------------------------------ the Plonk verifier
  * PlonkProof::verify_succinct (crates/plonk/src/plonk/protocol.rs:357-491) for k raw proofs of one circuit:
  * rows = n (a power of two >= 4, d = n - 1, omega = 5^((r - 1) / n)), the circuit's selector commitments
@@ -538,7 +581,9 @@ typedef enum {
     HALO_PLONK_C_BAR = 5,      /* "C_bar' != C_bar" (acc.rs:207) */
     HALO_PLONK_Z = 6,          /* "z' = z" (acc.rs:208) */
     HALO_PLONK_V = 7,          /* "h(z) = v" (acc.rs:210) */
-    HALO_PLONK_MALFORMED = 8
+    HALO_PLONK_MALFORMED = 8,
+    HALO_PLONK_DECIDER_SUCCINCT = 9, /* halo_plonk_verify_batch: pcdl::check's succinct check of acc_next (pcdl.rs:547) */
+    HALO_PLONK_DECIDER = 10          /* ... "U != CM.Commit(ck, h_vec)" (pcdl.rs:580) */
 } halo_plonk_verdict_t;
 int halo_plonk_verify_succinct_batch(halo_curve_t curve, size_t rows, size_t k,
         const halo_wrapped_point_t* C_qs, const halo_fe_t* public_inputs, size_t npi,
@@ -556,6 +601,35 @@ int halo_plonk_verify_succinct_batch_dev(halo_curve_t curve, size_t rows, size_t
         const void* d_acc_prev_C, const void* d_acc_prev_z, const void* d_acc_prev_v,
         const void* d_acc_next_C, const void* d_acc_next_z, const void* d_acc_next_v, const void* d_mds,
         void* d_verdict, void* d_challenges_out, void* d_sides_out, void* d_asdl_out, void* stream);
+
+/* PlonkProof::verify (protocol.rs:493-502) for k raw proofs of one circuit: verify_succinct as above, then
+ * acc::decider of acc_next, i.e. pcdl::check of (acc_next.C, d, acc_next.z, acc_next.v) with
+ * acc_next.pi = acc_next_{Ls[i lg n + j], Rs[i lg n + j], U[i], c[i]}.  acc_next's PCDL transcript runs as a fourth
+ * instance per proof inside the same chain of launches; the deciders follow as in halo_pcdl_decide_batch, over
+ * the proofs whose verdict is still HALO_PLONK_ACCEPT, with rho (NULL: exact mode) under that call's rule and
+ * errors.  verdict[i] is the verify_succinct code if that is nonzero, else HALO_PLONK_DECIDER_SUCCINCT,
+ * HALO_PLONK_DECIDER or HALO_PLONK_ACCEPT.  A point of acc_next.pi that is neither (0, 0) nor on the curve gives
+ * HALO_PLONK_DECIDER_SUCCINCT.  The errors of halo_plonk_verify_succinct_batch, acc_next_c included. */
+int halo_plonk_verify_batch(halo_curve_t curve, size_t rows, size_t k,
+        const halo_wrapped_point_t* C_qs, const halo_fe_t* public_inputs, size_t npi,
+        const halo_wrapped_point_t* C_ws, const halo_wrapped_point_t* C_z, const halo_wrapped_point_t* C_ts,
+        const halo_fe_t* vs, const halo_wrapped_point_t* Ls, const halo_wrapped_point_t* Rs,
+        const halo_wrapped_point_t* U, const halo_fe_t* c,
+        const halo_wrapped_point_t* acc_prev_C, const halo_fe_t* acc_prev_z, const halo_fe_t* acc_prev_v,
+        const halo_wrapped_point_t* acc_next_C, const halo_fe_t* acc_next_z, const halo_fe_t* acc_next_v,
+        const halo_wrapped_point_t* acc_next_Ls, const halo_wrapped_point_t* acc_next_Rs,
+        const halo_wrapped_point_t* acc_next_U, const halo_fe_t* acc_next_c,
+        const halo_fe_t* mds, const halo_fe_t* rho, uint8_t* verdict);
+/* The same over device pointers, asynchronous on `stream`.  d_combined (1 byte, may be NULL) is written only with
+ * d_rho; with d_combined = 0 every proof that reached the decider reports HALO_PLONK_DECIDER and the caller calls
+ * again with d_rho NULL (it never falls back). */
+int halo_plonk_verify_batch_dev(halo_curve_t curve, size_t rows, size_t k,
+        const void* d_C_qs, const void* d_public_inputs, size_t npi, const void* d_C_ws, const void* d_C_z,
+        const void* d_C_ts, const void* d_vs, const void* d_Ls, const void* d_Rs, const void* d_U, const void* d_c,
+        const void* d_acc_prev_C, const void* d_acc_prev_z, const void* d_acc_prev_v,
+        const void* d_acc_next_C, const void* d_acc_next_z, const void* d_acc_next_v,
+        const void* d_acc_next_Ls, const void* d_acc_next_Rs, const void* d_acc_next_U, const void* d_acc_next_c,
+        const void* d_mds, const void* d_rho, void* d_verdict, void* d_combined, void* stream);
 
 /* ------------------------------------------------------------------ measurement hooks
  * When enabled, the library brackets its dominant kernels (MSM bucket accumulation, NTT passes)

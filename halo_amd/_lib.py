@@ -142,6 +142,7 @@ SIGNATURES = {
     "halo_pcdl_succinct_check_fs_batch_dev": [ctypes.c_int, _sz, _sz] + [_vp] * 14,
     "halo_pcdl_decide_batch": [ctypes.c_int, _sz, _sz] + [_vp] * 5,
     "halo_pcdl_decide_batch_dev": [ctypes.c_int, _sz, _sz] + [_vp] * 7,
+    "halo_pcdl_decide_bisect_dev": [ctypes.c_int, _sz, _sz] + [_vp] * 6,
     "halo_pcdl_check_fs_batch": [ctypes.c_int, _sz, _sz] + [_vp] * 12,
     "halo_pcdl_check_fs_batch_dev": [ctypes.c_int, _sz, _sz] + [_vp] * 14,
     "halo_plonk_verify_succinct_batch": [ctypes.c_int, _sz, _sz, _vp, _vp, _sz] + [_vp] * 19,
@@ -280,3 +281,9 @@ class tuning:
         for k, v in self.prev.items():
             set_tuning(k, v)
         return False
+
+
+def bisecting(on: bool) -> tuning:
+    """``with bisecting(bisect):`` around a batched decider call: decide_bisect = 1 when asked for, else no key is
+    touched (a rejected combined batch is then bisected on the device instead of rerun in exact mode)."""
+    return tuning(decide_bisect=1) if on else tuning()

@@ -14,12 +14,20 @@
 //   k_decide_negate      -P, the addend of
 //   (lincomb_device)     one item of t = k terms: -P + sum_i rho_i U_i; its "valid and the identity" byte is `combined`
 //   k_decide_spread      ok[i] = live[i] && combined
+// Bisect mode (decide_bisect_device, decider_bisect.hpp): the combined pass with k_bisect_mask in place of
+// k_decide_mask, and when it rejects, level by level through the halves that fail.  D(S) = sum_{i in S} rho_i U_i -
+// Commit(sum_{i in S} rho_i h_i) is additive, so a failing node needs one pass, over its left half:
+//   (hpoly_segments_device)  one coefficient row per node from the half-tables the root pass left
+//   (msm_batch_device)   their commitments P_s, in groups as in exact mode
+//   k_bisect_left        D(left_s) = -P_s + the root pass's terms rho_i U_i over the left half
+//   k_bisect_split       D(right_s) = D(node_s) - D(left_s), the two flags, ok[i] = 0 for a failing leaf
 // On top of the core: halo_pcdl_decide_batch, halo_pcdl_check_fs_batch (fs_device, then the decider with
 // live = the succinct verdicts, the xis never leaving the device) and their _dev forms.
 #include <vector>
 
 #include "curve.hpp"
 #include "decider.hpp"
+#include "decider_bisect.hpp"
 #include "decider_plan.hpp"
 #include "dispatch.hpp"
 #include "lincomb.hpp"
@@ -83,6 +91,84 @@ __global__ __launch_bounds__(DEC_THREADS) void k_decide_spread(const uint8_t* __
     const size_t i = (size_t)blockIdx.x * DEC_THREADS + threadIdx.x;
     if (i >= k) return;
     ok[i] = (!live || live[i] != 0) && combined[0] != 0 ? 1 : 0;
+}
+
+// Bisect mode's k_decide_mask: an instance that is live but whose U is neither (0, 0) nor on the curve, or whose
+// rho is zero or not below the modulus, is masked out as well and valid[i] = 0: it is rejected here and no node's
+// sum sees it.
+template <class Cv>
+__global__ __launch_bounds__(DEC_THREADS) void k_bisect_mask(const uint8_t* __restrict__ live, const uint4* __restrict__ rho,
+                                                             const uint4* __restrict__ U, size_t k, uint4* __restrict__ rho_m,
+                                                             uint4* __restrict__ U_m, uint8_t* __restrict__ valid) {
+    using F = typename Cv::Base;
+    using S = typename Cv::Scalar;
+    const size_t i = (size_t)blockIdx.x * DEC_THREADS + threadIdx.x;
+    if (i >= k) return;
+    const uint4 r0 = rho[2 * i], r1 = rho[2 * i + 1];
+    const bool nonzero = (r0.x | r0.y | r0.z | r0.w | r1.x | r1.y | r1.z | r1.w) != 0;
+    const bool below = ark_is_canonical<S>(rho + 2 * i);
+    const bool curve_ok = aff_on_curve_or_id(aff_from_wrapped<F>(U + 4 * i), fe_from_const<F>(Cv::K::B));
+    const bool on = (!live || live[i] != 0) && nonzero && below && curve_ok;
+    const uint32_t keep = on ? ~0u : 0u;
+    rho_m[2 * i] = make_uint4(r0.x & keep, r0.y & keep, r0.z & keep, r0.w & keep);
+    rho_m[2 * i + 1] = make_uint4(r1.x & keep, r1.y & keep, r1.z & keep, r1.w & keep);
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        const uint4 w = U[4 * i + q];
+        U_m[4 * i + q] = make_uint4(w.x & keep, w.y & keep, w.z & keep, w.w & keep);
+    }
+    valid[i] = on ? 1 : 0;
+}
+
+// Segment b = blockIdx.x, one wave: D(left_b) = -P_b + sum_{lo_b <= i < mid_b} terms[i] as packed XYZZ, P_b the
+// commitment of the segment's coefficient row (a WrappedPoint), the terms those of the root pass's lincomb.  Every
+// lane adds a strided share with the complete addition, then an LDS tree (k_lincomb_sum's shape).
+template <class Cv>
+__global__ __launch_bounds__(DEC_THREADS) void k_bisect_left(const uint4* __restrict__ terms, const uint4* __restrict__ P,
+                                                             const uint4* __restrict__ segs, uint4* __restrict__ left) {
+    using F = typename Cv::Base;
+    __shared__ uint4 red[DEC_THREADS * 8];
+    const size_t b = blockIdx.x;
+    const uint4 seg = segs[b];
+    XYZZ<F> acc = xyzz_id<F>();
+    if (threadIdx.x == 0) {
+        Affine<F> A = aff_from_wrapped<F>(P + 4 * b);
+        if (!aff_is_id(A)) A.y = fe_neg(A.y);
+        acc = xyzz_from_aff(A);
+    }
+    for (size_t j = (size_t)seg.x + threadIdx.x; j < seg.y; j += DEC_THREADS) acc = xyzz_add(acc, xyzz_load<F>(terms + 8 * j));
+    xyzz_store(red + 8 * threadIdx.x, acc);
+    __syncthreads();
+    for (int off = DEC_THREADS / 2; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off)
+            xyzz_store(red + 8 * threadIdx.x,
+                       xyzz_add(xyzz_load<F>(red + 8 * threadIdx.x), xyzz_load<F>(red + 8 * (threadIdx.x + off))));
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) xyzz_store(left + 8 * b, xyzz_load<F>(red));
+}
+
+// One lane per node s = (lo, mid, hi, src): D(right) = D(node) - D(left) by the general addition (the operands are
+// equal when only the left half fails, D(left) is the identity when only the right one does), the children's
+// defects at 2 s and 2 s + 1 of `next`, their flags (1 = not the identity: the half holds a wrong instance), and
+// ok = 0 for a failing half of one instance.  D(node) is entry src of `cur`.
+template <class Cv>
+__global__ __launch_bounds__(DEC_THREADS) void k_bisect_split(const uint4* __restrict__ cur, const uint4* __restrict__ left,
+                                                              const uint4* __restrict__ segs, size_t f, uint4* __restrict__ next,
+                                                              uint8_t* __restrict__ flags, uint8_t* __restrict__ ok) {
+    using F = typename Cv::Base;
+    const size_t sidx = (size_t)blockIdx.x * DEC_THREADS + threadIdx.x;
+    if (sidx >= f) return;
+    const uint4 seg = segs[sidx];
+    const XYZZ<F> Dl = xyzz_load<F>(left + 8 * sidx);
+    const XYZZ<F> Dr = xyzz_add(xyzz_load<F>(cur + 8 * (size_t)seg.w), xyzz_neg(Dl));
+    xyzz_store(next + 8 * (2 * sidx), Dl);
+    xyzz_store(next + 8 * (2 * sidx + 1), Dr);
+    const bool fl = !xyzz_is_id(Dl), fr = !xyzz_is_id(Dr);
+    flags[2 * sidx] = fl ? 1 : 0;
+    flags[2 * sidx + 1] = fr ? 1 : 0;
+    if (fl && seg.y - seg.x == 1) ok[seg.x] = 0;
+    if (fr && seg.z - seg.y == 1) ok[seg.y] = 0;
 }
 
 // k = 1 with a weight: the exact verdict is also the combined one
@@ -159,12 +245,20 @@ static int decide_exact(DeviceState* st, const DecideCall& a, hipStream_t s) {
     return HALO_OK;
 }
 
-static int decide_combined(DeviceState* st, const DecideCall& a, hipStream_t s) {
+// Where a combined pass left its `combined` byte and, in bisect mode, the batch's defect and the validity bytes.
+struct CombinedOut {
+    uint8_t* comb;
+    uint4* sum;
+    uint8_t* valid;
+};
+
+// bisect: k_bisect_mask's validity test up front; the pass's half-tables, terms and defect are what the descent reads.
+static int decide_combined(DeviceState* st, const DecideCall& a, hipStream_t s, bool bisect = false, CombinedOut* out = nullptr) {
     const size_t k = a.k, n = a.d + 1;
     const uint32_t lg = ilog2(n);
     const int field = a.curve == HALO_PALLAS ? HALO_FP : HALO_FQ;
     const size_t o_rho = 0, o_U = o_rho + align256(k * 32), o_P = o_U + align256(k * 64), o_neg = o_P + 256, o_sum = o_neg + 256,
-                 o_comb = o_sum + 256, total = o_comb + 256;
+                 o_comb = o_sum + 256, o_valid = o_comb + 256, total = o_valid + (bisect ? align256(k) : 0);
     HALO_CHECK(st->decider[0].reserve(n * 32));
     HALO_CHECK(st->decider[1].reserve(hpoly_table_elems(k, lg) * 32));
     HALO_CHECK(st->decider[2].reserve(total));
@@ -172,9 +266,17 @@ static int decide_combined(DeviceState* st, const DecideCall& a, hipStream_t s) 
     uint8_t* base = st->decider[2].as<uint8_t>();
     uint4 *rho_m = (uint4*)(base + o_rho), *U_m = (uint4*)(base + o_U), *P = (uint4*)(base + o_P), *neg = (uint4*)(base + o_neg);
     uint8_t* comb = a.combined ? (uint8_t*)a.combined : base + o_comb;
+    const uint8_t* live = (const uint8_t*)a.live;
     const dim3 per_lane(grid_for(k, DEC_THREADS)), blk(DEC_THREADS);
-    hipLaunchKernelGGL(k_decide_mask, per_lane, blk, 0, s, (const uint8_t*)a.live, (const uint4*)a.rho, (const uint4*)a.U, k, rho_m,
-                       U_m);
+    if (bisect) {
+        DISPATCH_CURVE(a.curve, Cv, {
+            hipLaunchKernelGGL(k_bisect_mask<Cv>, per_lane, blk, 0, s, live, (const uint4*)a.rho, (const uint4*)a.U, k, rho_m, U_m,
+                               base + o_valid);
+        });
+        live = base + o_valid;
+    } else {
+        hipLaunchKernelGGL(k_decide_mask, per_lane, blk, 0, s, live, (const uint4*)a.rho, (const uint4*)a.U, k, rho_m, U_m);
+    }
     HALO_HIP(hipGetLastError());
     HALO_CHECK(hpoly_combine_device(field, a.xis, k, lg, rho_m, st->decider[1].ptr, st->decider[0].ptr, s, "hpoly_combine"));
     {
@@ -185,8 +287,9 @@ static int decide_combined(DeviceState* st, const DecideCall& a, hipStream_t s) 
     DISPATCH_CURVE(a.curve, Cv, { hipLaunchKernelGGL(k_decide_negate<Cv>, dim3(1), dim3(1), 0, s, (const uint4*)P, neg); });
     HALO_HIP(hipGetLastError());
     HALO_CHECK(lincomb_device(st, a.curve, neg, U_m, rho_m, 1, k, base + o_sum, comb, s));
-    hipLaunchKernelGGL(k_decide_spread, per_lane, blk, 0, s, (const uint8_t*)a.live, (const uint8_t*)comb, k, (uint8_t*)a.ok);
+    hipLaunchKernelGGL(k_decide_spread, per_lane, blk, 0, s, live, (const uint8_t*)comb, k, (uint8_t*)a.ok);
     HALO_HIP(hipGetLastError());
+    if (out) *out = CombinedOut{comb, (uint4*)(base + o_sum), base + o_valid};
     return HALO_OK;
 }
 
@@ -200,6 +303,99 @@ int decide_device(DeviceState* st, const DecideCall& a, hipStream_t s) {
         HALO_HIP(hipGetLastError());
     }
     return HALO_OK;
+}
+
+// The work of one level of the descent (decider_bisect.hpp's Eval) on the device.
+struct BisectDevice {
+    DeviceState* st;
+    const DecideCall& a;
+    hipStream_t s;
+    const uint4* cur;   // the defects of this level's nodes (BisectNode::src indexes it)
+    uint4* pong[2];     // the children's defects, level by level in turn
+    int turn = 0;
+    uint4 *segs, *P, *left;  // per level: the node table, the rows' commitments, D(left)
+    uint8_t* flags;
+    const uint4* terms;  // the root pass's rho_i U_i
+    std::vector<const void*> ptrs;
+    std::vector<size_t> lens;
+
+    int rows(const BisectNode* level, size_t f, size_t r0, size_t m) {
+        const size_t n = a.d + 1;
+        const int field = a.curve == HALO_PALLAS ? HALO_FP : HALO_FQ;
+        if (r0 == 0) HALO_CHECK(copy_h2d(segs, level, f * sizeof(BisectNode), s));
+        // (every launch of the level above has completed: its flags were read)
+        HALO_CHECK(st->bisect[0].reserve(m * n * 32));
+        uint8_t* rows = st->bisect[0].as<uint8_t>();
+        HALO_CHECK(hpoly_segments_device(field, st->decider[1].ptr, a.k, ilog2(n), segs + r0, m, rows, s));
+        ptrs.resize(m);
+        lens.assign(m, n);
+        for (size_t j = 0; j < m; j++) ptrs[j] = rows + j * n * 32;
+        {
+            StageScope st_msm("decide_msm", s);
+            HALO_CHECK(msm_batch_device(st, a.curve, ptrs.data(), lens.data(), m, P + 4 * r0, s));
+            HALO_CHECK(msm_join(st, s));  // the next group rewrites the rows
+            st_msm.end();
+        }
+        DISPATCH_CURVE(a.curve, Cv, {
+            hipLaunchKernelGGL(k_bisect_left<Cv>, dim3((unsigned)m), dim3(DEC_THREADS), 0, s, terms, (const uint4*)P + 4 * r0,
+                               (const uint4*)segs + r0, left + 8 * r0);
+        });
+        HALO_HIP(hipGetLastError());
+        return HALO_OK;
+    }
+
+    int split(const BisectNode*, size_t f, uint8_t* host_flags) {
+        uint4* next = pong[turn];
+        DISPATCH_CURVE(a.curve, Cv, {
+            hipLaunchKernelGGL(k_bisect_split<Cv>, dim3(grid_for(f, DEC_THREADS)), dim3(DEC_THREADS), 0, s, cur, (const uint4*)left,
+                               (const uint4*)segs, f, next, flags, (uint8_t*)a.ok);
+        });
+        HALO_HIP(hipGetLastError());
+        cur = next;
+        turn ^= 1;
+        return copy_d2h(host_flags, flags, 2 * f, s);  // the level's one host wait
+    }
+};
+static_assert(sizeof(BisectNode) == sizeof(uint4), "the kernels read a node as one uint4");
+
+int decide_bisect_device(DeviceState* st, const DecideCall& a, hipStream_t s) {
+    if (!a.rho || a.k < 2) return decide_device(st, a, s);
+    HALO_CHECK(check_decider_srs(st, a.curve, a.d));
+    const SrsState& srs = st->srs[a.curve];
+    const size_t k = a.k, n = a.d + 1;
+    CombinedOut root;
+    HALO_CHECK(decide_combined(st, a, s, true, &root));
+    uint8_t combined = 0;
+    HALO_CHECK(copy_d2h(&combined, root.comb, 1, s));
+    if (combined) return HALO_OK;  // ok = the validity bytes
+    // The descent's own buffers: the root pass's tables, terms and defect stay where they are.  A level has at
+    // most k / 2 nodes and k children.
+    const size_t fmax = k / 2, o_pong0 = align256(k * 128), o_pong1 = o_pong0 + align256(k * 128);
+    const size_t o_P = align256(fmax * 16), o_left = o_P + align256(fmax * 64), o_flags = o_left + align256(fmax * 128);
+    HALO_CHECK(st->bisect[1].reserve(o_pong1 + align256(k * 128)));
+    HALO_CHECK(st->bisect[2].reserve(o_flags + align256(2 * fmax)));
+    uint8_t *b1 = st->bisect[1].as<uint8_t>(), *b2 = st->bisect[2].as<uint8_t>();
+    HALO_HIP(hipMemcpyAsync(b1, st->lincomb_terms.ptr, k * 128, hipMemcpyDeviceToDevice, s));  // lincomb_device reuses its buffer
+    HALO_HIP(hipMemcpyAsync(a.ok, root.valid, k, hipMemcpyDeviceToDevice, s));
+    BisectDevice ev{st, a, s, root.sum, {(uint4*)(b1 + o_pong0), (uint4*)(b1 + o_pong1)}, 0, (uint4*)b2, (uint4*)(b2 + o_P),
+                    (uint4*)(b2 + o_left), b2 + o_flags, (const uint4*)b1, {}, {}};
+    const int W = srs.shifted_c ? msm_windows(srs.shifted_c) : 1;
+    std::vector<uint8_t> host_ok(k, 1);  // the kernels clear a.ok themselves
+    return bisect_descend(k, n, (size_t)std::max<long long>(tuning(TUNE_DECIDE_GROUP_SCALARS), 1), W, ev, host_ok.data());
+}
+
+int decide_resolved(DeviceState* st, const DecideCall& a, hipStream_t s) {
+    if (!a.rho || a.k < 2) return decide_device(st, a, s);
+    if (tuning(TUNE_DECIDE_BISECT) > 0) return decide_bisect_device(st, a, s);
+    HALO_CHECK(check_decider_srs(st, a.curve, a.d));
+    CombinedOut root;
+    HALO_CHECK(decide_combined(st, a, s, false, &root));
+    uint8_t combined = 0;
+    HALO_CHECK(copy_d2h(&combined, root.comb, 1, s));
+    if (combined) return HALO_OK;
+    DecideCall exact = a;  // some instance fails: the exact verdicts
+    exact.rho = nullptr;
+    return decide_device(st, exact, s);
 }
 
 // Everything that needs no device; done: an empty batch.
@@ -255,6 +451,22 @@ extern "C" int halo_pcdl_decide_batch_dev(halo_curve_t curve, size_t d, size_t k
     return decide_device(st, DecideCall{(int)curve, d, k, d_xis, d_U, d_live, d_rho, d_ok, d_combined}, s);
 }
 
+extern "C" int halo_pcdl_decide_bisect_dev(halo_curve_t curve, size_t d, size_t k, const void* d_xis, const void* d_U,
+                                           const void* d_live, const void* d_rho, void* d_ok, void* stream) {
+    clear_error();
+    const char* call = "halo_pcdl_decide_bisect_dev";
+    bool done;
+    HALO_CHECK(check_decide_args(call, curve, d, k, d_xis, d_U, d_ok, done));
+    if (done) return HALO_OK;
+    if (!d_rho) return set_error(HALO_EINVAL, "%s: null d_rho", call);
+    DeviceState* st = current_state();
+    if (!st) return HALO_EDEVICE;
+    std::lock_guard<std::mutex> g(st->mu);
+    hipStream_t s = (hipStream_t)stream;
+    ScratchUse su(st, s);
+    return decide_bisect_device(st, DecideCall{(int)curve, d, k, d_xis, d_U, d_live, d_rho, d_ok, nullptr}, s);
+}
+
 extern "C" int halo_pcdl_decide_batch(halo_curve_t curve, size_t d, size_t k, const halo_fe_t* xis,
                                       const halo_wrapped_point_t* U, const uint8_t* live, const halo_fe_t* rho,
                                       uint8_t* ok_out) {
@@ -307,15 +519,7 @@ extern "C" int halo_pcdl_decide_batch(halo_curve_t curve, size_t d, size_t k, co
     }
     uint8_t* d_comb = dout + align256(m);
     DecideCall a{(int)curve, d, m, di + o_xis, di + o_U, nullptr, rho ? di + o_rho : nullptr, dout, d_comb};
-    HALO_CHECK(decide_device(st, a, s));
-    if (rho && m > 1) {
-        uint8_t combined = 0;
-        HALO_CHECK(copy_d2h(&combined, d_comb, 1, s));
-        if (!combined) {  // some instance fails: the exact verdicts
-            a.rho = nullptr;
-            HALO_CHECK(decide_device(st, a, s));
-        }
-    }
+    HALO_CHECK(decide_resolved(st, a, s));
     std::vector<uint8_t> got(m);
     HALO_CHECK(copy_d2h(got.data(), dout, m, s));
     for (size_t j = 0; j < m; j++) ok_out[idx[j]] = got[j];
@@ -323,7 +527,7 @@ extern "C" int halo_pcdl_decide_batch(halo_curve_t curve, size_t d, size_t k, co
 }
 
 // pcdl::check over device pointers: fs_device, then the decider over the xis it leaves in st->decider[3].
-// host_fallback: read `combined` back and rerun a rejected combined batch in exact mode.
+// host_fallback: a rejected combined batch is resolved to per-instance verdicts (decide_resolved).
 static int check_fs_run(const char* call, DeviceState* st, FsCall a, const void* d_rho, void* d_code, void* d_combined,
                         bool host_fallback, hipStream_t s) {
     const size_t k = a.k, lg = ilog2(a.d + 1);
@@ -337,15 +541,7 @@ static int check_fs_run(const char* call, DeviceState* st, FsCall a, const void*
     HALO_CHECK(fs_device(call, st, a, s));
     uint8_t* comb = d_combined ? (uint8_t*)d_combined : base + o_comb;
     DecideCall dc{a.curve, a.d, k, base + o_xis, a.U, base + o_succ, d_rho, base + o_dec, comb};
-    HALO_CHECK(decide_device(st, dc, s));
-    if (host_fallback && d_rho && k > 1) {
-        uint8_t combined = 0;
-        HALO_CHECK(copy_d2h(&combined, comb, 1, s));
-        if (!combined) {
-            dc.rho = nullptr;
-            HALO_CHECK(decide_device(st, dc, s));
-        }
-    }
+    HALO_CHECK(host_fallback ? decide_resolved(st, dc, s) : decide_device(st, dc, s));
     hipLaunchKernelGGL(k_check_codes, dim3(grid_for(k, DEC_THREADS)), dim3(DEC_THREADS), 0, s, (const uint8_t*)(base + o_succ),
                        (const uint8_t*)(base + o_dec), k, (uint8_t*)d_code);
     HALO_HIP(hipGetLastError());

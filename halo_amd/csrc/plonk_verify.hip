@@ -569,8 +569,7 @@ struct PlonkCall {  // the arguments of either entry point
     void* combined = nullptr;
 };
 
-// What the decider of a full call reads, left in scratch by plonk_device (plonk_decide runs it, and runs it again
-// in exact mode when the host form's combined check failed).
+// What the decider of a full call reads, left in scratch by plonk_device (plonk_decide runs it).
 struct PlonkDecide {
     const void *xis, *live;
     void *decided, *combined;
@@ -609,10 +608,12 @@ static int check_plonk_srs(const char* call, const DeviceState* st, const PlonkC
     return HALO_OK;
 }
 
-// acc::decider of the proofs that are still accepted (rho null: exact mode), then their verdicts.
-static int plonk_decide(DeviceState* st, const PlonkCall& a, const PlonkDecide& pd, const void* rho, hipStream_t s) {
+// acc::decider of the proofs that are still accepted (rho null: exact mode), then their verdicts.  resolve: the
+// host form, which waits for a rejected combined batch's per-proof verdicts (decide_resolved).
+static int plonk_decide(DeviceState* st, const PlonkCall& a, const PlonkDecide& pd, const void* rho, bool resolve,
+                        hipStream_t s) {
     const DecideCall dc{a.curve, a.rows - 1, a.k, pd.xis, a.next_U, pd.live, rho, pd.decided, pd.combined};
-    HALO_CHECK(decide_device(st, dc, s));
+    HALO_CHECK(resolve ? decide_resolved(st, dc, s) : decide_device(st, dc, s));
     hipLaunchKernelGGL(k_plonk_decided, dim3(grid_for(a.k, PV_THREADS)), dim3(PV_THREADS), 0, s, (const uint8_t*)pd.live,
                        (const uint8_t*)pd.decided, a.k, (uint8_t*)a.verdict);
     HALO_HIP(hipGetLastError());
@@ -621,9 +622,8 @@ static int plonk_decide(DeviceState* st, const PlonkCall& a, const PlonkDecide& 
 
 // The launches of one call over device pointers, all on `s`.  st->mu and a ScratchUse of `s` held; a.k >= 1,
 // check_plonk_srs passed.  ipp = 3 instances per proof (verify_succinct), or 4 with acc_next (a.full), whose PCDL
-// transcript then runs inside the same fs_device chain and whose decider follows (pd, when given, receives what
-// a second decider pass needs).
-static int plonk_device(const char* call, DeviceState* st, const PlonkCall& a, hipStream_t s, PlonkDecide* pd = nullptr) {
+// transcript then runs inside the same fs_device chain and whose decider follows (resolve: see plonk_decide).
+static int plonk_device(const char* call, DeviceState* st, const PlonkCall& a, hipStream_t s, bool resolve = false) {
     const size_t k = a.k, lg = ilog2(a.rows), d = a.rows - 1, m = a.npi ? a.npi : 1, ipp = a.full ? 4 : 3;
     const size_t nx = a.full ? k : 0;  // proofs with a fourth instance
     const uint32_t* params;
@@ -741,8 +741,7 @@ static int plonk_device(const char* call, DeviceState* st, const PlonkCall& a, h
     HALO_HIP(hipGetLastError());
     if (!a.full) return HALO_OK;
     const PlonkDecide dec{base + o_nxis, base + o_live, base + o_dec, a.combined ? a.combined : (void*)(base + o_comb)};
-    if (pd) *pd = dec;
-    return plonk_decide(st, a, dec, a.rho, s);
+    return plonk_decide(st, a, dec, a.rho, resolve, s);
 }
 
 static bool fe_all_below(int curve, const halo_fe_t* x, size_t n) {
@@ -759,8 +758,8 @@ static bool fe_all_below(int curve, const halo_fe_t* x, size_t n) {
     return true;
 }
 
-// Either host entry point: the scalar checks, one buffer of inputs and one of outputs, the chain, and for a full
-// call the exact rerun of the deciders when the combined check failed.
+// Either host entry point: the scalar checks, one buffer of inputs and one of outputs and the chain; in a full
+// call a rejected combined batch of deciders is resolved to per-proof verdicts.
 static int plonk_host(const char* call, const PlonkCall& host) {
     bool done;
     HALO_CHECK(check_plonk_args(call, host, done));
@@ -816,13 +815,7 @@ static int plonk_host(const char* call, const PlonkCall& host) {
                 host.sides_out ? dout + o_sides : nullptr, host.asdl_out ? dout + o_asdl : nullptr};
     a.full = host.full;
     a.next_Ls = dev(17), a.next_Rs = dev(18), a.next_U = dev(19), a.next_c = dev(20), a.rho = dev(21);
-    PlonkDecide pd{};
-    HALO_CHECK(plonk_device(call, st, a, s, &pd));
-    if (a.full && a.rho && k > 1) {
-        uint8_t combined = 0;
-        HALO_CHECK(copy_d2h(&combined, pd.combined, 1, s));
-        if (!combined) HALO_CHECK(plonk_decide(st, a, pd, nullptr, s));  // some decider fails: the exact verdicts
-    }
+    HALO_CHECK(plonk_device(call, st, a, s, true));
     if (host.chal_out) HALO_CHECK(copy_d2h(host.chal_out, dout + o_chal, k * 5 * 32, s));
     if (host.sides_out) HALO_CHECK(copy_d2h(host.sides_out, dout + o_sides, k * 2 * 32, s));
     if (host.asdl_out) HALO_CHECK(copy_d2h(host.asdl_out, dout + o_asdl, k * 2 * 32, s));

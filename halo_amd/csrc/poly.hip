@@ -413,6 +413,29 @@ __global__ __launch_bounds__(256) void k_hpoly_rows(const uint4* __restrict__ t_
     fe_to_ark(rows_ark + 2 * idx, fe_mul(fe_load<F>(t_lo + 2 * (i * nlo + lo)), fe_load<F>(t_hi + 2 * (i * nhi + hi))));
 }
 
+// One coefficient row per segment of instances: rows[s n + j] = sum_{lo_s <= i < mid_s} T_lo,i[lo] T_hi,i[hi], the
+// partial sums of k_hpoly_coeffs over the half-tables it read (weights folded into T_hi).  segs[s] = (lo_s, mid_s,
+// ., .) with lo_s < mid_s; two instances per step as in k_hpoly_coeffs, a last odd one alone.
+template <class F>
+__global__ __launch_bounds__(256) void k_hpoly_segments(const uint4* __restrict__ t_lo, const uint4* __restrict__ t_hi,
+                                                        const uint4* __restrict__ segs, size_t g, uint32_t lg_n, uint32_t lb,
+                                                        uint4* __restrict__ rows_ark) {
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if ((idx >> lg_n) >= g) return;
+    const size_t nlo = (size_t)1 << lb, nhi = (size_t)1 << (lg_n - lb);
+    const size_t j = idx & (((size_t)1 << lg_n) - 1);
+    const size_t lo = j & (nlo - 1), hi = j >> lb;
+    const uint4 seg = segs[idx >> lg_n];
+    const size_t end = seg.y;
+    Fe<F> acc = fe_zero<F>();
+    size_t i = seg.x;
+    for (; i + 1 < end; i += 2)
+        acc = fe_add(acc, fe_mul2(fe_load<F>(t_lo + 2 * (i * nlo + lo)), fe_load<F>(t_hi + 2 * (i * nhi + hi)),
+                                  fe_load<F>(t_lo + 2 * ((i + 1) * nlo + lo)), fe_load<F>(t_hi + 2 * ((i + 1) * nhi + hi))));
+    if (i < end) acc = fe_add(acc, fe_mul(fe_load<F>(t_lo + 2 * (i * nlo + lo)), fe_load<F>(t_hi + 2 * (i * nhi + hi))));
+    fe_to_ark(rows_ark + 2 * idx, acc);
+}
+
 namespace halo {
 
 size_t hpoly_table_elems(size_t k, uint32_t lg_n) {
@@ -457,6 +480,22 @@ int hpoly_rows_device(int field, const void* d_xis, size_t g, uint32_t lg_n, voi
     DISPATCH_FIELD(field, F, {
         HALO_LAUNCH(prof, k_hpoly_rows<F>, dim3(grid_for(g << lg_n, 256)), dim3(256), 0, s, (const uint4*)t_lo,
                     (const uint4*)t_hi, g, lg_n, lb, (uint4*)d_rows);
+    });
+    HALO_HIP(hipGetLastError());
+    return HALO_OK;
+}
+
+// g coefficient rows (ark, row s at d_rows + 32 s 2^lg_n) from the half-tables hpoly_combine_device left at d_tables
+// for k instances: row s sums the instances [x, y) of d_segs[s] (uint4 each, x < y <= k); g 2^lg_n < 2^32.
+int hpoly_segments_device(int field, const void* d_tables, size_t k, uint32_t lg_n, const void* d_segs, size_t g, void* d_rows,
+                          hipStream_t s) {
+    const uint32_t lb = lg_n / 2;
+    const uint4* t_lo = (const uint4*)d_tables;
+    const uint4* t_hi = t_lo + 2 * k * ((size_t)1 << lb);
+    ProfScope prof("hpoly_segments", s);
+    DISPATCH_FIELD(field, F, {
+        HALO_LAUNCH(prof, k_hpoly_segments<F>, dim3(grid_for(g << lg_n, 256)), dim3(256), 0, s, t_lo, t_hi, (const uint4*)d_segs, g,
+                    lg_n, lb, (uint4*)d_rows);
     });
     HALO_HIP(hipGetLastError());
     return HALO_OK;

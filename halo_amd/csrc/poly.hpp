@@ -17,5 +17,9 @@ int hpoly_combine_device(int field, const void* d_xis, size_t k, uint32_t lg_n, 
                          void* d_out, hipStream_t s, const char* prof_name);
 // the g separate coefficient rows (ark, row i at d_rows + 32 i 2^lg_n); g 2^lg_n < 2^32
 int hpoly_rows_device(int field, const void* d_xis, size_t g, uint32_t lg_n, void* d_tables, void* d_rows, hipStream_t s);
+// g partial sums of hpoly_combine_device's k weighted polynomials, from the half-tables it left at d_tables: row s
+// (ark, at d_rows + 32 s 2^lg_n) sums the instances [x, y) of the uint4 d_segs[s], x < y <= k; g 2^lg_n < 2^32
+int hpoly_segments_device(int field, const void* d_tables, size_t k, uint32_t lg_n, const void* d_segs, size_t g, void* d_rows,
+                          hipStream_t s);
 
 }  // namespace halo

@@ -622,12 +622,13 @@ def check_device(C, d: int, z, v, pi: dict, curve="pallas") -> None:
         raise CheckFailed(DECIDER_MSG)
 
 
-def decide_batch(xis, Us, d: int, rhos=None, live=None, curve="pallas") -> np.ndarray:
+def decide_batch(xis, Us, d: int, rhos=None, live=None, curve="pallas", bisect: bool = False) -> np.ndarray:
     """halo_pcdl_decide_batch: acc::decider for k instances of degree bound d.  xis (k, lg n + 1, 4) challenges
     (the layout succinct_check_fs_verdicts returns), Us (k, 8).  rhos None: one commitment per instance (exact
     mode); rhos (k, 4) nonzero scalars drawn by the caller AFTER the proofs were fixed: one random linear
-    combination and one MSM, with an exact rerun if it fails.  live: k flags, 0 skips the instance (verdict 0).
-    Returns k bytes, 1 where U == CM.Commit(ck, h_vec)."""
+    combination and one MSM, with an exact rerun if it fails, or with bisect=True a descent through the halves
+    that fail (one MSM per failing node; tuning key decide_bisect).  live: k flags, 0 skips the instance
+    (verdict 0).  Returns k bytes, 1 where U == CM.Commit(ck, h_vec)."""
     H.ensure_device()
     U = H.point_array(Us)
     k = len(U)
@@ -635,15 +636,16 @@ def decide_batch(xis, Us, d: int, rhos=None, live=None, curve="pallas") -> np.nd
     ok = np.zeros(k, dtype=np.uint8)
     lv = np.ascontiguousarray(np.asarray(live, dtype=np.uint8).reshape(k)) if live is not None else None
     rh = H.fe_array(rhos, k) if rhos is not None else None
-    H.check(H.load().halo_pcdl_decide_batch(_curve(curve), d, k, H.ptr(H.fe_array(xis, k * (lg + 1))), H.ptr(U), H.ptr(lv),
-                                            H.ptr(rh), H.ptr(ok)))
+    with H.bisecting(bisect):
+        H.check(H.load().halo_pcdl_decide_batch(_curve(curve), d, k, H.ptr(H.fe_array(xis, k * (lg + 1))), H.ptr(U),
+                                                H.ptr(lv), H.ptr(rh), H.ptr(ok)))
     return ok
 
 
 def check_fs_codes(Cs, d: int, zs, vs, Ls, Rs, Us, cs, hiding=None, C_bars=None, w_primes=None, rhos=None,
-                   curve="pallas") -> np.ndarray:
+                   curve="pallas", bisect: bool = False) -> np.ndarray:
     """halo_pcdl_check_fs_batch: pcdl::check of k raw instances of degree bound d (the arguments of
-    succinct_check_fs_verdicts, plus rhos as in decide_batch).  Returns k codes: 0 accept, 1 the succinct check
+    succinct_check_fs_verdicts, plus rhos and bisect as in decide_batch).  Returns k codes: 0 accept, 1 the succinct check
     failed, 2 the decider failed."""
     H.ensure_device()
     C = H.point_array(Cs)
@@ -656,17 +658,19 @@ def check_fs_codes(Cs, d: int, zs, vs, Ls, Rs, Us, cs, hiding=None, C_bars=None,
         cb, wp = H.point_array(C_bars), H.fe_array(w_primes, k)
         assert len(cb) == k
     rh = H.fe_array(rhos, k) if rhos is not None else None
-    H.check(H.load().halo_pcdl_check_fs_batch(
-        _curve(curve), d, k, H.ptr(C), H.ptr(H.fe_array(zs, k)), H.ptr(H.fe_array(vs, k)),
-        H.ptr(H.point_array(Ls)) if lg else None, H.ptr(H.point_array(Rs)) if lg else None, H.ptr(H.point_array(Us)),
-        H.ptr(H.fe_array(cs, k)), H.ptr(hid), H.ptr(cb), H.ptr(wp), H.ptr(rh), H.ptr(code)))
+    with H.bisecting(bisect):
+        H.check(H.load().halo_pcdl_check_fs_batch(
+            _curve(curve), d, k, H.ptr(C), H.ptr(H.fe_array(zs, k)), H.ptr(H.fe_array(vs, k)),
+            H.ptr(H.point_array(Ls)) if lg else None, H.ptr(H.point_array(Rs)) if lg else None, H.ptr(H.point_array(Us)),
+            H.ptr(H.fe_array(cs, k)), H.ptr(hid), H.ptr(cb), H.ptr(wp), H.ptr(rh), H.ptr(code)))
     return code
 
 
-def check_batch(instances, rhos=None, curve="pallas", verdicts: bool = False):
+def check_batch(instances, rhos=None, curve="pallas", verdicts: bool = False, bisect: bool = False):
     """pcdl::check (pcdl.rs:563-583) for many instances (C, d, z, v, pi), every transcript and every decider on
     the device: one halo_pcdl_check_fs_batch call per distinct d.  rhos: one nonzero scalar per instance, drawn
-    by the caller after the proofs were fixed (decide_batch), or None for exact deciders.  Raises
+    by the caller after the proofs were fixed (decide_batch), or None for exact deciders; bisect as in
+    decide_batch.  Raises
     CheckFailed(msg, index) for the first failing instance; with verdicts=True returns the codes instead
     (0 accept, 1 succinct check, 2 decider) and raises only for a d beyond the SRS."""
     H.ensure_device()
@@ -690,7 +694,7 @@ def check_batch(instances, rhos=None, curve="pallas", verdicts: bool = False):
             hiding=hid if any(hid) else None,
             C_bars=np.stack([H.point_array(q.pi["C_bar"]).reshape(8) if h else zero_pt for q, h in zip(qs, hid)]),
             w_primes=np.stack([H.fe_array(q.pi["w_prime"], 1)[0] if h else zero_fe for q, h in zip(qs, hid)]),
-            rhos=rh[idx] if rh is not None else None, curve=cid)
+            rhos=rh[idx] if rh is not None else None, curve=cid, bisect=bisect)
     if verdicts:
         return codes
     for i, c in enumerate(codes):

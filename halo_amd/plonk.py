@@ -178,12 +178,13 @@ def verify_succinct_batch(circuit: PlonkCircuit, public_inputs, acc_prevs, proof
     return (verdict, chal, sides, asdl) if readbacks else verdict
 
 
-def verify_batch(circuit: PlonkCircuit, public_inputs, acc_prevs, proofs, rhos=None, curve="pallas") -> np.ndarray:
+def verify_batch(circuit: PlonkCircuit, public_inputs, acc_prevs, proofs, rhos=None, curve="pallas",
+                 bisect: bool = False) -> np.ndarray:
     """PlonkProof::verify (protocol.rs:493-502) of k proofs of one circuit in one device call
     (halo_plonk_verify_batch): verify_succinct, then acc::decider of every acc_next, whose PCDL transcript runs
     beside the proof's three instances.  rhos None: one commitment per decider; rhos (k, 4) nonzero scalars
     drawn by the caller AFTER the proofs were fixed: one random linear combination of the deciders and one MSM,
-    with an exact rerun if it fails (pcdl.decide_batch).  Returns the k verdict bytes: the verify_succinct code
+    with an exact rerun if it fails, or with bisect=True a bisection of the batch (pcdl.decide_batch).  Returns the k verdict bytes: the verify_succinct code
     if nonzero, else DECIDER_SUCCINCT, DECIDER or ACCEPT."""
     a = pack_batch(circuit, public_inputs, acc_prevs, proofs)
     k = len(proofs)
@@ -202,10 +203,11 @@ def verify_batch(circuit: PlonkCircuit, public_inputs, acc_prevs, proofs, rhos=N
     rh = H.fe_array(rhos, k) if rhos is not None else None
     H.ensure_device()
     names = ARG_ORDER[:-1]  # mds comes after acc_next's evaluation proof
-    H.check(H.load().halo_plonk_verify_batch(
-        _curve(curve), circuit.rows, k, H.ptr(a["C_qs"]), H.ptr(a["public_inputs"]), circuit.public_input_count,
-        *[H.ptr(a[name]) for name in names], H.ptr(nLs), H.ptr(nRs), H.ptr(nU), H.ptr(nc), H.ptr(a["mds"]), H.ptr(rh),
-        H.ptr(verdict)))
+    with H.bisecting(bisect):
+        H.check(H.load().halo_plonk_verify_batch(
+            _curve(curve), circuit.rows, k, H.ptr(a["C_qs"]), H.ptr(a["public_inputs"]), circuit.public_input_count,
+            *[H.ptr(a[name]) for name in names], H.ptr(nLs), H.ptr(nRs), H.ptr(nU), H.ptr(nc), H.ptr(a["mds"]), H.ptr(rh),
+            H.ptr(verdict)))
     return verdict
 
 

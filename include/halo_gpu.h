@@ -83,7 +83,10 @@ int halo_stream_sync(void* stream);
  * MSM; default 2^19), "ntt_big_max_log" (NTTs up to 2^this use 11-bit passes; default 22),
  * "ntt_even_split" (1: stages split evenly over the passes; default 0), "poseidon_lanes" (lanes per sponge
  * of the batched Poseidon kernels, 1 or 3; default 0: by batch size), "decide_group_scalars" (the exact batched
- * decider commits its instances in groups whose coefficient rows hold at most this many scalars; default 2^25).  Every setting yields the same results; the parity tests pin each path with it.  The
+ * decider commits its instances in groups whose coefficient rows hold at most this many scalars; default 2^25),
+ * "decide_bisect" (what the host forms of the batched decider do with a combined batch that is rejected: 0, the
+ * default, decide every live instance again in exact mode; 1 bisect the batch on the device, see
+ * halo_pcdl_decide_bisect_dev).  Every setting yields the same results; the parity tests pin each path with it.  The
  * reference has no counterpart (host-side knob of this backend only).  HALO_EINVAL on an unknown key. */
 int halo_set_tuning(const char* key, long long value);
 int halo_get_tuning(const char* key, long long* value);
@@ -510,8 +513,9 @@ int halo_pcdl_succinct_check_fs_batch_dev(halo_curve_t curve, size_t d, size_t k
  * the tuning key "decide_group_scalars" scalars (default 2^25); up to "msm_multi_max" coefficients a group is one
  * MSM, above it pipelined ones.
  * rho given (k scalars of `curve`): combined mode, sum_i rho_i U_i == Commit(sum_i rho_i h_i) over the live
- * instances, ONE MSM whatever k.  If that fails the live instances are decided again in exact mode, so the
- * verdicts are always per instance and exact for rejects.  An accept in combined mode is sound up to a prover
+ * instances, ONE MSM whatever k.  If that fails the live instances are decided again in exact mode (or, with the
+ * tuning key "decide_bisect" = 1, the batch is bisected: halo_pcdl_decide_bisect_dev), so the verdicts are always
+ * per instance and exact for rejects.  An accept in combined mode is sound up to a prover
  * guessing rho (probability about k / 2^254 over a uniform choice): rho must be drawn AFTER the proofs are
  * fixed, uniformly, from the caller's random number generator -- the library draws no randomness.
  * Before any device work: HALO_ENOTPOW2 "n ({n}) is not a power of two", HALO_EINVAL for a null required pointer,
@@ -526,6 +530,24 @@ int halo_pcdl_decide_batch(halo_curve_t curve, size_t d, size_t k, const halo_fe
  * verdict for its instance. */
 int halo_pcdl_decide_batch_dev(halo_curve_t curve, size_t d, size_t k, const void* d_xis, const void* d_U,
                                const void* d_live, const void* d_rho, void* d_ok, void* d_combined, void* stream);
+/* Per-instance verdicts of a weighted batch by bisection, over device pointers; d_rho is required.  The combined
+ * pass runs first; when it rejects, D(S) = sum_{i in S} rho_i U_i - Commit(sum_{i in S} rho_i h_i) is followed down
+ * a binary tree over the instances (left half = the first floor(size / 2) of a node): one combined pass over the
+ * left half of every failing node gives D(left), and D(right) = D(node) - D(left) is one point subtraction, so b
+ * wrong instances among k cost at most min(k - 1, b ceil(lg k)) MSMs beyond the first, where exact mode costs k.
+ * The half-tables and the terms rho_i U_i of the first pass are reused; no scalar multiplication is repeated.
+ * UNLIKE THE OTHER _dev FORMS THIS ONE WAITS FOR `stream`: once after the first pass and once per level of the
+ * tree, at most 1 + ceil(lg k) times (the launches of a level depend on the flags of the one above).
+ * A live instance whose U is neither (0, 0) nor on the curve, or whose rho is zero or not below the modulus, is
+ * rejected before the first pass and weighs nothing in any node; U = (0, 0) is a legal point and is decided.
+ * Soundness: a reject is exact (a single instance has D != 0 iff it is wrong, because rho_i != 0).  An accept of
+ * any subset is sound up to a prover guessing rho: the union bound over the at most 2 k - 1 nodes of the tree
+ * gives about 2 k / 2^254 for rho drawn uniformly after the proofs are fixed.  k = 1 is exact mode.
+ * The host forms halo_pcdl_decide_batch, halo_pcdl_check_fs_batch and halo_plonk_verify_batch take this route for
+ * a rejected combined batch when the tuning key "decide_bisect" is 1 (the default 0 keeps the exact rerun).
+ * Errors: those of halo_pcdl_decide_batch_dev, and HALO_EINVAL for a null d_rho. */
+int halo_pcdl_decide_bisect_dev(halo_curve_t curve, size_t d, size_t k, const void* d_xis, const void* d_U,
+                                const void* d_live, const void* d_rho, void* d_ok, void* stream);
 /* pcdl::check (pcdl.rs:563-583) for k raw instances: halo_pcdl_succinct_check_fs_batch, then the decider above
  * with live = the succinct verdicts, the challenges never leaving the device.  The inputs and errors of
  * halo_pcdl_succinct_check_fs_batch, plus rho (NULL: exact mode) with the rule and the errors of

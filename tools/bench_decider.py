@@ -5,6 +5,8 @@ same session.  DESIGN §4.9 records the numbers.
 
     python tools/bench_decider.py [--reps 20] [--ks 1,64,4096] [--lgs 16,20] [--out profiles/decider_bench.json]
                                   [--budget-ms 4000] [--loop-max 256] [--modes combined]
+    python tools/bench_decider.py --ks 64,4096 --out profiles/decider_bisect_bench.json --alternations 3 \
+                                  --modes combined,combined_one_bad,bisect_one_bad,bisect_all_bad,one_bad_alternated
 
 Per lg n and k:
   * exact mode and combined mode (all valid): the event-timed median of the _dev call (inputs resident) and the
@@ -12,7 +14,13 @@ Per lg n and k:
   * combined mode with one bad instance: the host-array call, which falls back to exact mode (wall time);
   * the stages from the library's profiling hooks, per call: "hpoly_rows", "hpoly_combine" (kernel times) and
     "decide_msm" (the span of the MSMs on the stream), with the number of "decide_msm" stages;
-  * the parent's loop (wall time).
+  * the parent's loop (wall time);
+  * "bisect_one_bad": the same one-bad host call with the tuning key decide_bisect = 1 (the batch is bisected on the
+    device instead of rerun in exact mode), with its stages; "bisect_all_bad" (k <= 64): every U wrong, bisected,
+    beside exact mode on the same batch;
+  * "one_bad_alternated": the two one-bad routes (key off, key on) alternated --alternations times, each a median,
+    and whether their ranges are apart.
+A library without the key (HALO_LIB pointing at an older build) can run every mode that does not set it.
 Medians of --reps calls after warm-up; a call that takes longer than --budget-ms is repeated fewer times (at
 least twice; the count is recorded).  The parent's loop over more than --loop-max instances is measured over
 --loop-max of them and scaled, which the entry says.  The xi rows are random; min(k, 64) of them are distinct and
@@ -38,7 +46,7 @@ from halo_amd import group, pcdl  # noqa: E402
 
 from bench_pcdl_check import dev, scalars  # noqa: E402
 
-STAGES = ("hpoly_rows", "hpoly_combine", "decide_msm")
+STAGES = ("hpoly_rows", "hpoly_combine", "hpoly_segments", "lincomb_terms", "decide_msm")
 
 
 def median_ms(fn, reps, budget_ms, events):
@@ -95,6 +103,7 @@ def main():
     ap.add_argument("--loop-max", type=int, default=256)
     ap.add_argument("--modes", default="exact,combined,combined_one_bad,parent_loop",
                     help="what to measure (an A/B of one stage needs only its mode)")
+    ap.add_argument("--alternations", type=int, default=3)
     ap.add_argument("--out")
     a = ap.parse_args()
     modes = set(a.modes.split(","))
@@ -122,6 +131,8 @@ def main():
             rho[:, 0] |= np.uint64(1)
             bad = U.copy()
             bad[k // 2] = U_d[(idx[k // 2] + 1) % distinct]  # a valid point, another instance's commitment
+            all_bad = np.ascontiguousarray(U_d[(idx + 1) % distinct])
+            one_bad = [0 if i == k // 2 else 1 for i in range(k)]
             ok = np.zeros(k, dtype=np.uint8)
             d_x, d_U, d_rho = dev(xis), dev(U), dev(rho)
             d_ok = torch.zeros(k, dtype=torch.uint8, device="cuda")
@@ -154,7 +165,28 @@ def main():
             if "combined_one_bad" in modes:
                 entry["combined_one_bad"] = {"host_wall": median_ms(lambda: host_call(True, bad), a.reps, a.budget_ms, False),
                                              "stages": stages(L, lambda: host_call(True, bad))}
-                assert ok.tolist() == [0 if i == k // 2 else 1 for i in range(k)]
+                assert ok.tolist() == one_bad
+            if "bisect_one_bad" in modes and k > 1:
+                with H.tuning(decide_bisect=1):
+                    entry["bisect_one_bad"] = {"host_wall": median_ms(lambda: host_call(True, bad), a.reps, a.budget_ms, False),
+                                               "stages": stages(L, lambda: host_call(True, bad))}
+                assert ok.tolist() == one_bad
+            if "bisect_all_bad" in modes and 1 < k <= 64:
+                with H.tuning(decide_bisect=1):
+                    entry["bisect_all_bad"] = {"host_wall": median_ms(lambda: host_call(True, all_bad), a.reps, a.budget_ms, False),
+                                               "stages": stages(L, lambda: host_call(True, all_bad))}
+                assert ok.tolist() == [0] * k
+                entry["exact_all_bad"] = {"host_wall": median_ms(lambda: host_call(False, all_bad), a.reps, a.budget_ms, False)}
+                assert ok.tolist() == [0] * k
+            if "one_bad_alternated" in modes and k > 1:
+                runs = {"exact_rerun": [], "bisect": []}
+                for _ in range(a.alternations):
+                    for name, key in (("exact_rerun", 0), ("bisect", 1)):
+                        with H.tuning(decide_bisect=key):
+                            runs[name].append(median_ms(lambda: host_call(True, bad), a.reps, a.budget_ms, False)["ms_median"])
+                        assert ok.tolist() == one_bad
+                runs["apart"] = max(runs["bisect"]) < min(runs["exact_rerun"])
+                entry["one_bad_alternated"] = runs
             if "parent_loop" in modes:
                 loop = median_ms(parent_loop, a.reps, a.budget_ms, False)
                 assert all(parent_loop())

@@ -122,6 +122,8 @@ SIGNATURES = {
     "halo_pcdl_open_blind": [_vp, _vp, _vp, _vp],
     "halo_pcdl_open_combine": [_vp, _vp, _vp, _vp, _vp, _vp],
     "halo_pcdl_open_start": [_vp, _vp, _vp],
+    "halo_pcdl_open_fs": [ctypes.c_int, _vp, _sz, _sz] + [_vp] * 13,
+    "halo_pcdl_open_fs_dev_multi": [ctypes.c_int, _sz, _vp, _vp, _sz] + [_vp] * 7,
     "halo_ipa_round_lr": [_vp, _vp, _vp],
     "halo_ipa_fold": [_vp, _vp, _vp],
     "halo_ipa_state": [_vp, ctypes.POINTER(_sz), _vp, _vp, _vp],

@@ -6,7 +6,7 @@ reference's interface (absorb_g, absorb_fr, challenge over WrappedPoints / ark s
 "ASDL" (one per common_subroutine, acc.rs:135) or "PCDL" (one per succinct check and per opening,
 pcdl.rs:336,496).  The m succinct checks of common_subroutine run as one batch on the device
 (pcdl.succinct_check_many; with ``device_transcripts=True`` their PCDL sponges run there too,
-pcdl.succinct_check_device).  An accumulator is the ``pcdl.Instance`` acc.q of the reference.
+pcdl.succinct_check_device, and so does the sponge of the prover's opening, pcdl.open_device).  An accumulator is the ``pcdl.Instance`` acc.q of the reference.
 """
 from __future__ import annotations
 
@@ -60,12 +60,18 @@ def common_subroutine(qs, new_transcript, curve="pallas", device_transcripts=Fal
     return C, d, z, hs, alphas
 
 
-def prover(qs, new_transcript, curve="pallas") -> Instance:
-    """acc.rs:178-198: the accumulator ((C_bar, d, z, v), pi) of the instances qs."""
+def prover(qs, new_transcript, curve="pallas", device_transcripts=False) -> Instance:
+    """acc.rs:178-198: the accumulator ((C_bar, d, z, v), pi) of the instances qs.  device_transcripts: the PCDL
+    sponges of the succinct checks and of the opening run on the device (pcdl.succinct_check_device,
+    pcdl.open_device); the ASDL sponge stays new_transcript's, as in ``verifier``."""
     cid = _curve(curve)
-    C_bar, d, z, hs, alphas = common_subroutine(qs, new_transcript, cid)
+    C_bar, d, z, hs, alphas = common_subroutine(qs, new_transcript, cid, device_transcripts)
     v = _alphas_dot_h(hs, alphas, z, cid)
-    pi = pcdl.open(pcdl.HPoly.combine(hs, alphas), C_bar, d, z, w=None, transcript=new_transcript("PCDL"), curve=cid)
+    h = pcdl.HPoly.combine(hs, alphas)
+    if device_transcripts:
+        pi = pcdl.open_device(h, C_bar, d, z, curve=cid)
+    else:
+        pi = pcdl.open(h, C_bar, d, z, w=None, transcript=new_transcript("PCDL"), curve=cid)
     return Instance(C_bar, d, z, v, pi)
 
 

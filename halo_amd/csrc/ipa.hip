@@ -12,7 +12,8 @@
 //    round never round-trips scalars through the host.
 //  * Here: the fold and weighted-round kernels, the session pool and the session entry points.  The
 //    session's declarations are in ipa_session.hpp, the tail rounds' multiples-table sums in tail.hip,
-//    the dot products and powers in poly.hip, the hiding open's steps in pcdl_open.hip.
+//    the dot products and powers in poly.hip, the hiding open's steps in pcdl_open.hip, the opening with its
+//    transcript on the device in pcdl_open_fs.hip.
 #include <algorithm>
 #include <cstring>
 #include <unordered_set>
@@ -215,6 +216,26 @@ __global__ __launch_bounds__(256) void k_tail_fold(uint4* cs, uint4* zs, size_t 
     }
 }
 
+// k_tail_fold with xi | xi^-1 (ark, 64 B) read from device memory: the fold of an opening whose transcript
+// runs on the device (pcdl_open_fs.hip)
+template <class Cv>
+__global__ __launch_bounds__(256) void k_tail_fold_dev(uint4* cs, uint4* zs, size_t m, const uint4* x_dev,
+                                                       const uint4* w_in, uint4* w_out, size_t wlen) {
+    using S = typename Cv::Scalar;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const Fe<S> xi = fe_from_ark<S>(x_dev);
+    if (i < m) {
+        const Fe<S> xinv = fe_from_ark<S>(x_dev + 2);
+        fe_to_ark(cs + 2 * i, fe_add(fe_from_ark<S>(cs + 2 * i), fe_mul(fe_from_ark<S>(cs + 2 * (i + m)), xinv)));
+        fe_to_ark(zs + 2 * i, fe_add(fe_from_ark<S>(zs + 2 * i), fe_mul(fe_from_ark<S>(zs + 2 * (i + m)), xi)));
+    }
+    if (i < wlen) {
+        const Fe<S> wv = fe_from_ark<S>(w_in + 2 * i);
+        fe_to_ark(w_out + 2 * (2 * i), wv);
+        fe_to_ark(w_out + 2 * (2 * i + 1), fe_mul(wv, xi));
+    }
+}
+
 // Weighted rounds (sessions over the resident SRS, length > IPA_TAIL_N): G is never folded.  With
 // len = 2m and the fold weights w (as in the tail rounds, G_i = sum_u w[u] SRS[i + u len]),
 //   L = sum_{u, i < m} c[m + i] w[u] SRS[u len + i],   R = sum_{u, i < m} c[i] w[u] SRS[u len + m + i],
@@ -371,7 +392,7 @@ halo_ipa_session* halo::ipa_acquire(DeviceState* st) {
     // round; the prover's and pcdl::open's sessions use the resident 2^i H tables and build none)
     if (hipStreamCreateWithFlags(&ses->s, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&ses->htab_ready, hipEventDisableTiming) != hipSuccess ||
-        hipHostMalloc((void**)&ses->pinned, 1024, hipHostMallocCoherent) != hipSuccess) {
+        hipHostMalloc((void**)&ses->pinned, PIN_BYTES, hipHostMallocCoherent) != hipSuccess) {
         ipa_destroy(ses);
         set_error(HALO_EDEVICE, "halo_ipa_begin: stream / pinned buffer allocation failed");
         return nullptr;
@@ -578,14 +599,14 @@ static int ipa_ensure_gs(DeviceState* st, halo_ipa_session* ses) {
 // Phase 2: the hiding terms' table.  xi mode (xi0 and H): the shared 2^i H table and dots scaled by
 // xi_0; otherwise (H_prime) a per-session 2^i H' table.  The rounds may run afterwards.
 int halo::ipa_start(DeviceState* st, halo_ipa_session* ses, const halo_wrapped_point_t* H_prime, const halo_fe_t* xi0,
-                    const halo_wrapped_point_t* Hpt) {
+                    const halo_wrapped_point_t* Hpt, bool xi0_resident) {
     hipStream_t s = ses->s;
     char* sm = (char*)ses->small.ptr;
-    ses->xi_mode = xi0 != nullptr;
+    ses->xi_mode = xi0 != nullptr || xi0_resident;
     const halo_wrapped_point_t* own = H_prime;  // the point of a per-session table, if one is needed
     if (ses->xi_mode) {  // xi_0 at [192, 224)
         HALO_CHECK(ipa_h_table(st, ses->curve, Hpt, &ses->htab_ptr));
-        HALO_CHECK(copy_h2d(sm + SM_XI0, xi0, 32, s));
+        if (!xi0_resident) HALO_CHECK(copy_h2d(sm + SM_XI0, xi0, 32, s));
         own = ses->htab_ptr ? nullptr : Hpt;
     }
     ses->started = true;
@@ -676,6 +697,18 @@ extern "C" int halo_ipa_begin_vectors(halo_curve_t curve, const halo_wrapped_poi
 // v = c(z) over the session's first len coefficients, to the host (stream sync): the dot product of c
 // with the session's z^i vector (ipa_setup wrote it), one parallel multiplication per coefficient
 // instead of chunked Horner chains (2^10: 44 + 5 us of dependent chains -> one short dot launch pair)
+int halo::ipa_eval_cs_enqueue(halo_ipa_session* ses, size_t len) {
+    hipStream_t s = ses->s;
+    char* sm = ses->small.as<char>();
+    if (!len) {
+        HALO_HIP(hipMemsetAsync(sm + SM_V, 0, 32, s));
+        return HALO_OK;
+    }
+    HALO_CHECK(ses->tmp.reserve(4096 * 32));  // dot_device: at most 1024 block partials
+    const int sf = ses->curve == HALO_PALLAS ? HALO_FP : HALO_FQ;
+    return dot_device(sf, ses->cs.ptr, ses->zs.ptr, len, sm + SM_V, ses->tmp.ptr, s);
+}
+
 int halo::ipa_eval_cs(halo_ipa_session* ses, size_t len, halo_fe_t* v_out) {
     hipStream_t s = ses->s;
     char* sm = ses->small.as<char>();
@@ -683,9 +716,7 @@ int halo::ipa_eval_cs(halo_ipa_session* ses, size_t len, halo_fe_t* v_out) {
         memset(v_out, 0, 32);
         return HALO_OK;
     }
-    HALO_CHECK(ses->tmp.reserve(4096 * 32));  // dot_device: at most 1024 block partials
-    const int sf = ses->curve == HALO_PALLAS ? HALO_FP : HALO_FQ;
-    HALO_CHECK(dot_device(sf, ses->cs.ptr, ses->zs.ptr, len, sm + SM_V, ses->tmp.ptr, s));
+    HALO_CHECK(ipa_eval_cs_enqueue(ses, len));
     HALO_HIP(hipMemcpyAsync(ses->pinned + PIN_FE, sm + SM_V, 32, hipMemcpyDeviceToHost, s));
     HALO_HIP(hipStreamSynchronize(s));
     memcpy(v_out, ses->pinned + PIN_FE, 32);
@@ -748,6 +779,7 @@ static int ipa_tail_sums(const DeviceState* st, halo_ipa_session* ses, int mode,
         if (f.active) {  // the previous round's fold, applied here (halo_ipa_fold deferred it)
             memcpy(&f.xi, &ses->pend_xi, 32);
             memcpy(&f.xinv, &ses->pend_xinv, 32);
+            if (ses->xi_dev) f.xi_dev = (const uint4*)(sm + SM_XI);
             f.cs_out = ses->cs2.as<uint4>();
             f.zs_out = ses->zs2.as<uint4>();
             f.w_out = ses->w[ses->wcur ^ 1].as<uint4>();
@@ -838,7 +870,7 @@ static int ipa_copy_out(halo_ipa_session* ses) {
 }
 
 // Enqueues one round's L and R (with their H' terms) and their D2H copy into ses->pinned.
-static int ipa_round_launch(DeviceState* st, halo_ipa_session* ses) {
+int halo::ipa_round_launch(DeviceState* st, halo_ipa_session* ses) {
     if (ses->m == 0) return set_error(HALO_EINVAL, "halo_ipa_round_lr: no rounds left");
     if (!ses->started) return set_error(HALO_EINVAL, "halo_ipa_round_lr: session not started (halo_pcdl_open_start)");
     hipStream_t s = ses->s;
@@ -985,13 +1017,16 @@ static int ipa_apply_pending_fold(DeviceState* st, halo_ipa_session* ses) {
     return ipa_fold_now(st, ses, &ses->pend_xi, &ses->pend_xinv);
 }
 
-static int ipa_fold_launch(DeviceState* st, halo_ipa_session* ses, const halo_fe_t* xi, const halo_fe_t* xi_inv) {
+int halo::ipa_fold_launch(DeviceState* st, halo_ipa_session* ses, const halo_fe_t* xi, const halo_fe_t* xi_inv) {
     if (ses->m == 0) return set_error(HALO_EINVAL, "halo_ipa_fold: no rounds left");
     if (!ses->started) return set_error(HALO_EINVAL, "halo_ipa_fold: session not started (halo_pcdl_open_start)");
+    if (!ses->xi_dev && (!xi || !xi_inv)) return set_error(HALO_EINVAL, "halo_ipa_fold: null argument");
     if (ses->tail) {  // applied by the next round's k_tail_prep (no launch, no copy now)
         HALO_CHECK(ipa_apply_pending_fold(st, ses));
-        ses->pend_xi = *xi;
-        ses->pend_xinv = *xi_inv;
+        if (!ses->xi_dev) {  // (a device transcript's challenge stays at SM_XI until the round that applies it)
+            ses->pend_xi = *xi;
+            ses->pend_xinv = *xi_inv;
+        }
         ses->pend_m = ses->m;
         ses->fold_pending = true;
         ses->srs_round0 = false;
@@ -1008,16 +1043,24 @@ static int ipa_fold_now(DeviceState* st, halo_ipa_session* ses, const halo_fe_t*
     // synchronises the stream; two folds in a row wait here)
     if (ses->fold_inflight) HALO_HIP(hipStreamSynchronize(s));
     const size_t m = ses->m;
+    // a device transcript's xi | xi^-1 are already at SM_XI (no by-value pair, no staging copy)
+    const uint4* x_dev = ses->xi_dev ? (const uint4*)(sm + SM_XI) : nullptr;
     if (ses->tail || ses->weighted) {
         // xi, xi^-1 as kernel arguments: no staging copy, so nothing for a later fold to wait on
-        ArkScalarPair x;
-        memcpy(&x.v[0], xi, 32);
-        memcpy(&x.v[2], xi_inv, 32);
+        ArkScalarPair x{};
+        if (!x_dev) {
+            memcpy(&x.v[0], xi, 32);
+            memcpy(&x.v[2], xi_inv, 32);
+        }
         ses->srs_round0 = false;
+        const dim3 grid(grid_for(std::max(m, ses->wlen), 256));
         DISPATCH_CURVE(ses->curve, Cv, {
-            hipLaunchKernelGGL(k_tail_fold<Cv>, dim3(grid_for(std::max(m, ses->wlen), 256)), dim3(256), 0, s,
-                               ses->cs.as<uint4>(), ses->zs.as<uint4>(), m, x, ses->w[ses->wcur].as<const uint4>(),
-                               ses->w[ses->wcur ^ 1].as<uint4>(), ses->wlen);
+            if (x_dev)
+                hipLaunchKernelGGL(k_tail_fold_dev<Cv>, grid, dim3(256), 0, s, ses->cs.as<uint4>(), ses->zs.as<uint4>(), m,
+                                   x_dev, ses->w[ses->wcur].as<const uint4>(), ses->w[ses->wcur ^ 1].as<uint4>(), ses->wlen);
+            else
+                hipLaunchKernelGGL(k_tail_fold<Cv>, grid, dim3(256), 0, s, ses->cs.as<uint4>(), ses->zs.as<uint4>(), m, x,
+                                   ses->w[ses->wcur].as<const uint4>(), ses->w[ses->wcur ^ 1].as<uint4>(), ses->wlen);
         });
         HALO_HIP(hipGetLastError());
         ses->wcur ^= 1;
@@ -1025,10 +1068,12 @@ static int ipa_fold_now(DeviceState* st, halo_ipa_session* ses, const halo_fe_t*
         ses->m /= 2;
         return HALO_OK;
     }
-    ses->fold_inflight = true;
-    memcpy(ses->pinned + PIN_XI, xi, 32);
-    memcpy(ses->pinned + PIN_XINV, xi_inv, 32);
-    HALO_HIP(hipMemcpyAsync(sm + SM_XI, ses->pinned + PIN_XI, 64, hipMemcpyHostToDevice, s));
+    if (!x_dev) {
+        ses->fold_inflight = true;
+        memcpy(ses->pinned + PIN_XI, xi, 32);
+        memcpy(ses->pinned + PIN_XINV, xi_inv, 32);
+        HALO_HIP(hipMemcpyAsync(sm + SM_XI, ses->pinned + PIN_XI, 64, hipMemcpyHostToDevice, s));
+    }
     ses->srs_round0 = false;
     if (!ses->tail && !ses->weighted) {  // G itself is folded below
         HALO_CHECK(ipa_ensure_gs(st, ses));
@@ -1187,7 +1232,7 @@ extern "C" int halo_ipa_state(halo_ipa_session* ses, size_t* m, halo_wrapped_poi
 // halo_ipa_end in two halves: the device work enqueued on the session's stream (st->mu held), then the
 // wait, the host conversion and the release -- halo_ipa_end_multi enqueues every session's end before
 // it waits for any, so the lockstep openings' final U sums overlap on the device.
-static int ipa_end_enqueue(DeviceState* st, halo_ipa_session* ses) {
+int halo::ipa_end_enqueue(DeviceState* st, halo_ipa_session* ses) {
     hipStream_t s = ses->s;
     char* sm = (char*)ses->small.ptr;
     int rc = HALO_OK;
@@ -1220,7 +1265,7 @@ static int ipa_end_enqueue(DeviceState* st, halo_ipa_session* ses) {
     return rc;
 }
 
-static int ipa_end_finish(halo_ipa_session* ses, halo_wrapped_point_t* U, halo_fe_t* c) {
+int halo::ipa_end_finish(halo_ipa_session* ses, halo_wrapped_point_t* U, halo_fe_t* c) {
     const bool u_xyzz = ses->tail;
     if (hipStreamSynchronize(ses->s) != hipSuccess) return set_error(HALO_EDEVICE, "ipa end synchronisation failed");
     if (U) {

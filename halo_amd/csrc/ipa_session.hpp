@@ -1,6 +1,6 @@
-// The IPA session as its two units see it (ipa.hip: the pool, the rounds and folds; pcdl_open.hip: the
-// hiding open that fills a session before its rounds): the struct, the pool, the layouts of the
-// session's small device buffer and pinned staging.
+// The IPA session as its units see it (ipa.hip: the pool, the rounds and folds; pcdl_open.hip: the
+// hiding open that fills a session before its rounds; pcdl_open_fs.hip: the opening whose transcript runs
+// on the device): the struct, the pool, the layouts of the session's small device buffer and pinned staging.
 #pragma once
 #include <memory>
 
@@ -64,6 +64,9 @@ struct halo_ipa_session {
     bool started = false;            // rounds may run (a pcdl open session starts at halo_pcdl_open_start)
     bool blinded = false;            // halo_pcdl_open_blind ran (pbar holds p_bar)
     bool combined = false;           // halo_pcdl_open_combine ran
+    // the transcript runs on the device (pcdl_open_fs.hip): the folds read xi | xi^-1 at SM_XI, which the
+    // round's transcript kernel wrote, and no round or fold waits for the host
+    bool xi_dev = false;
 
     void reset_state() {
         curve = 0;
@@ -75,7 +78,7 @@ struct halo_ipa_session {
         table_ld = 0;
         fold_inflight = htab_waited = xi_mode = fold_pending = slots_reset = w_one_pending = false;
         htab_ptr = nullptr;
-        started = blinded = combined = false;
+        started = blinded = combined = xi_dev = false;
     }
     size_t buffer_bytes() const {
         size_t b = 0;
@@ -116,20 +119,26 @@ struct halo_ipa_session {
     }
 };
 
-// layout of a session's pinned staging (ses->pinned, 1024 B of coherent host memory):
+// layout of a session's pinned staging (ses->pinned, PIN_BYTES of coherent host memory):
 //   [128, 192) xi|xi_inv (H2D), [256, 512) L|R XYZZ (D2H or tail_emit_host),
 //   [512, 520) the L / R flags of tail_emit_host: coherent, several sessions in flight
 //   [0, 32) a scalar out (v, w') | [32, 96) C' out (wrapped); the hiding open's XYZZ sums C_bar / C' at
 //   [128, 256) with w' beside them; at the end U at [256) with c after it (wrapped: [320), XYZZ: [384))
+//   an opening with its transcript on the device: [528) status word, [544) v, [576) alpha, [1024, 5120) the
+//   proof's L_j | R_j (WrappedPoints, 128 B per round)
 constexpr size_t PIN_FE = 0, PIN_CP = 32, PIN_XI = 128, PIN_XINV = 160, PIN_T = 128, PIN_T_WP = 256, PIN_L = 256,
                  PIN_R = 384, PIN_FLAGS = 512, PIN_U = 256, PIN_U_C = 320, PIN_U_C_XYZZ = 384;
+constexpr size_t PIN_STATUS = 528, PIN_V = 544, PIN_ALPHA = 576, PIN_PROOF = 1024, PIN_BYTES = 5120;
 
 // small-buffer layout of a session (ses->small, device):
 //   [0, 32) z | [64, 128) H' (or H) | [128, 192) dots | [192, 224) xi_0 | [256, 384) U | c
 //   [384, 448) xi | xi^-1 | [512, 768) L | R XYZZ
 //   hiding open: [1024) w_bar, [1056) alpha, [1088) w, [1120) w' out, [1152) C, [1216) C_bar out,
 //   [1280) S (internal), [1344) C' out
-constexpr size_t SM_BYTES = 2048;
+//   transcript on the device (pcdl_open_fs.hip): [2048, 2160) the PCDL sponge's state (poseidon::STATE_U4: three
+//   base-field elements, then the squeezed flag and the counter n), [2176) the status word (nonzero: a round
+//   challenge was zero), [4096, 8192) the proof's L_j | R_j as WrappedPoints (SM_ROUNDS_MAX rounds)
+constexpr size_t SM_BYTES = 8192;
 constexpr size_t SM_Z = 0, SM_HP = 64, SM_DOT_L = 128, SM_DOT_R = 160, SM_XI0 = 192, SM_U = 256,
                  SM_U_C = 320, SM_U_C_XYZZ = 384,  // c beside U: after a WrappedPoint, after a packed XYZZ point
                  SM_XI = 384, SM_XINV = 416, SM_L = 512, SM_R = 640;
@@ -137,6 +146,7 @@ constexpr size_t SM_WBAR = 1024, SM_ALPHA = 1056, SM_W = 1088, SM_WP = 1120, SM_
                  SM_CP = 1344, SM_NEGW = 1408, SM_T = 1536, SM_V = 1696,  // SM_T: 128 B XYZZ
                  SM_HKW = 1728,  // 2 x 10 words: the dots' GLV splits (k_tail_digits -> k_tail_round)
                  SM_CTR = 1856;  // 2 x u32 arrival counters of k_tail_round, 1 of k_weighted_prep (zero between launches)
+constexpr size_t SM_SPONGE = 2048, SM_STATUS = 2176, SM_PROOF = 4096, SM_ROUNDS_MAX = 32;
 
 namespace halo {
 
@@ -158,9 +168,22 @@ void ipa_release(halo_ipa_session* ses);
 int ipa_setup(DeviceState* st, halo_ipa_session* ses, int curve, size_t n, const halo_wrapped_point_t* gs_host,
               const halo_fe_t* cs, size_t cs_len, bool cs_on_device, const halo_fe_t* zs_host, const halo_fe_t* z);
 // Phase 2: the hiding terms' table; the rounds may run afterwards
+// (xi0_resident: xi mode with xi_0 already at SM_XI0, written by a kernel on the session's stream)
 int ipa_start(DeviceState* st, halo_ipa_session* ses, const halo_wrapped_point_t* H_prime, const halo_fe_t* xi0,
-              const halo_wrapped_point_t* Hpt);
+              const halo_wrapped_point_t* Hpt, bool xi0_resident = false);
 // v = c(z) over the session's first len coefficients, to the host (stream sync)
 int ipa_eval_cs(halo_ipa_session* ses, size_t len, halo_fe_t* v_out);
+// ... its launches alone: v (ark) at SM_V, no copy and no wait
+int ipa_eval_cs_enqueue(halo_ipa_session* ses, size_t len);
+
+// ---- what an opening with its transcript on the device (pcdl_open_fs.hip) drives, st->mu held -----
+// Enqueues one round's L and R (packed XYZZ at SM_L / SM_R when the session's stream reaches that point)
+int ipa_round_launch(DeviceState* st, halo_ipa_session* ses);
+// Enqueues one fold; xi / xi_inv may be null for a session with xi_dev set (SM_XI / SM_XINV are read)
+int ipa_fold_launch(DeviceState* st, halo_ipa_session* ses, const halo_fe_t* xi, const halo_fe_t* xi_inv);
+// halo_ipa_end in two halves: U and c enqueued with their copy to the pinned staging; the wait and the
+// host conversion
+int ipa_end_enqueue(DeviceState* st, halo_ipa_session* ses);
+int ipa_end_finish(halo_ipa_session* ses, halo_wrapped_point_t* U, halo_fe_t* c);
 
 }  // namespace halo

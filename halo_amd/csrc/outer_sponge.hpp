@@ -46,6 +46,10 @@ struct OuterSponge {
 
     // A fresh sponge; the first element of every transcript is label_element(protocol).
     HALO_DEV void init(const uint32_t* lds_tab) { inner.init(lds_tab); }
+    // A transcript carried through device memory between two kernels (poseidon::STATE_U4 uint4, the same
+    // bytes in both lane layouts); mine: this lane belongs to the sponge that is stored.
+    HALO_DEV void store(uint4* dst, bool mine) const { inner.store(dst, mine); }
+    HALO_DEV void load(const uint32_t* lds_tab, const uint4* src) { inner.load(lds_tab, src); }
 
     // Protocols::{PCDL = 0, ASDL = 1, PLONK = 2, SIGNATURE = 3} as a field element (outer_sponge.rs:17-29)
     static HALO_DEV Fe<F> label_element(int protocol) {

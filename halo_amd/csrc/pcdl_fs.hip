@@ -24,49 +24,18 @@
 #include "lincomb.hpp"
 #include "outer_sponge.hpp"
 #include "pcdl_fs.hpp"
+#include "pcdl_transcript.hpp"
 #include "quad_ladder.hpp"
 #include "runtime.hpp"
 #include "sponge_launch.hpp"
 
 namespace halo {
 
-constexpr int PCDL_LABEL = 0;  // Protocols::PCDL (outer_sponge.rs:17-22)
 constexpr int FS_THREADS = 64;  // k_pcdl_cprime, k_pcdl_terms: one lane per instance
 
 struct PackedAffine {  // SrsState::S
     uint32_t w[16];
 };
-
-// One stretch of a transcript, between two challenges: [the label] [the scalar w] the coordinates of np <= 2
-// points [z, v], every element through the one absorb call, then the next challenge into w.
-template <class Cv, int LANES>
-HALO_DEV void transcript_stretch(poseidon::OuterSponge<Cv, LANES>& sp, bool label, bool pre, const uint4* p0, const uint4* p1,
-                                 int np, bool post, const uint4* z, const uint4* v, uint32_t (&w)[8]) {
-    using Sp = poseidon::OuterSponge<Cv, LANES>;
-    using F = typename Cv::Base;
-    constexpr int NS = Sp::FR_ELEMENTS;
-    const int n_label = label ? 1 : 0, n_pre = pre ? NS : 0, n_g = 2 * np, total = n_label + n_pre + n_g + (post ? 2 * NS : 0);
-#pragma unroll 1
-    for (int e = 0; e < total; e++) {
-        int q = e - n_label;
-        Fe<F> x;
-        if (q < 0) {
-            x = Sp::label_element(PCDL_LABEL);
-        } else if (q < n_pre) {
-            x = Sp::fr_element(w, q);
-        } else if (q < n_pre + n_g) {
-            q -= n_pre;
-            x = Sp::g_element(q < 2 ? p0 : p1, q & 1);
-        } else {
-            q -= n_pre + n_g;
-            uint32_t sw[8];
-            fe_ark_to_canonical_words<typename Cv::Scalar>(q < NS ? z : v, sw);
-            x = Sp::fr_element(sw, q < NS ? q : q - NS);
-        }
-        sp.absorb(x);
-    }
-    sp.challenge(w);
-}
 
 // alpha of every instance of a call that has hiding ones (pcdl.rs:506-510), and the rows of the t = 2 linear
 // combination C + alpha C_bar - w' S.  An instance that does not hide gets alpha = 0 and two empty rows;

@@ -22,6 +22,7 @@ constexpr int WIDTH = 3, RATE = 2, ROUNDS = 55;
 constexpr int N_CONST = WIDTH * WIDTH + ROUNDS * WIDTH;  // 174
 constexpr int TABLE_WORDS = N_CONST * NLIMB;
 constexpr int SPONGES_PER_WAVE_3 = 21;
+constexpr int STATE_U4 = 2 * WIDTH + 1;  // a sponge's state in memory (Sponge::store): 3 x 32 B, then (squeezed, n)
 
 // global table -> LDS, by the whole block
 HALO_DEV void stage_params(const uint32_t* __restrict__ g, uint32_t* lds) {
@@ -76,6 +77,20 @@ struct Sponge<F, 1> {
         for (int i = 0; i < WIDTH; i++) s[i] = fe_zero<F>();
         squeezed = false;
         n = 0;
+    }
+    // The stored state (STATE_U4 uint4): the three elements below 2p as packed words, then (squeezed, n).
+    // mine: this lane's sponge is the one stored.
+    HALO_DEV void store(uint4* dst, bool mine) const {
+        if (!mine) return;
+        for (int i = 0; i < WIDTH; i++) fe_store(dst + 2 * i, fe_reduce_8p(s[i]));
+        dst[2 * WIDTH] = make_uint4(squeezed ? 1u : 0u, (uint32_t)n, 0u, 0u);
+    }
+    HALO_DEV void load(const uint32_t* lds_tab, const uint4* src) {
+        tab = lds_tab;
+        for (int i = 0; i < WIDTH; i++) s[i] = fe_load<F>(src + 2 * i);
+        const uint4 fl = src[2 * WIDTH];
+        squeezed = fl.x != 0;
+        n = (int)fl.y;
     }
     HALO_DEV void permute() {
 #pragma unroll 1
@@ -141,6 +156,19 @@ struct Sponge<F, 3> {
         s = fe_zero<F>();
         squeezed = false;
         n = 0;
+    }
+    // The same stored state as the one-lane layout's: each of the sponge's three lanes stores / loads its element.
+    HALO_DEV void store(uint4* dst, bool mine) const {
+        if (!mine) return;
+        fe_store(dst + 2 * role, fe_reduce_8p(s));
+        if (role == 0) dst[2 * WIDTH] = make_uint4(squeezed ? 1u : 0u, (uint32_t)n, 0u, 0u);
+    }
+    HALO_DEV void load(const uint32_t* lds_tab, const uint4* src) {
+        init(lds_tab);
+        s = fe_load<F>(src + 2 * role);
+        const uint4 fl = src[2 * WIDTH];
+        squeezed = fl.x != 0;
+        n = (int)fl.y;
     }
     HALO_DEV void permute() {
 #pragma unroll 1

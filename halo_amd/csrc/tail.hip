@@ -258,7 +258,7 @@ HALO_DEV void tail_side_final(const TailRoundArgs& a, uint32_t sd, uint4* red) {
 // 2 sd and its GLV split to kw (10 words: k1, k2 words, signs; visible to the block on return).  With a
 // deferred fold the block folds the halves its dot reads and writes them to the ping-pong buffers (side
 // 0: c_r, z_l and the even w'; side 1: c_l, z_r and the odd w').
-template <class Cv>
+template <class Cv, bool XI_DEV>
 HALO_DEV void tail_side_dot(const uint4* cs, const uint4* zs, const uint4* w, size_t m, uint32_t sd, const TailFoldArgs& f,
                             const uint4* xi0_ark, uint4* dots_ark, uint32_t* kw) {
     using S = typename Cv::Scalar;
@@ -267,7 +267,7 @@ HALO_DEV void tail_side_dot(const uint4* cs, const uint4* zs, const uint4* w, si
     const size_t oc = sd ? 0 : m, oz = sd ? m : 0;  // c_r z_l (side 0), c_l z_r (side 1)
     Fe<S> acc_s = fe_zero<S>();
     if (f.active) {
-        const Fe<S> xi = fe_from_ark<S>(f.xi), xinv = fe_from_ark<S>(f.xinv);
+        const Fe<S> xi = tail_fold_xi<S, XI_DEV>(f), xinv = tail_fold_xinv<S, XI_DEV>(f);
         for (size_t i = tid; i < m; i += TAIL_THREADS) {
             const Fe<S> c = fe_add(fe_from_ark<S>(cs + 2 * (oc + i)), fe_mul(fe_from_ark<S>(cs + 2 * (oc + i + len)), xinv));
             const Fe<S> z = fe_add(fe_from_ark<S>(zs + 2 * (oz + i)), fe_mul(fe_from_ark<S>(zs + 2 * (oz + i + len)), xi));
@@ -319,7 +319,7 @@ HALO_DEV void tail_side_dot(const uint4* cs, const uint4* zs, const uint4* w, si
 // k_tail_msm's hiding terms) and the folded c, z, w: the first launch of a tail round over more than
 // TAIL_FUSE_N points, where forming the scalars once per point beats forming them in each point's
 // wave of k_tail_round (64 times the instructions).
-template <class Cv>
+template <class Cv, bool XI_DEV>
 __global__ __launch_bounds__(256) void k_tail_digits(const uint4* cs, const uint4* zs, const uint4* w, size_t n0, size_t m,
                                                      const TailFoldArgs f, uint32_t* scal, uint8_t* side,
                                                      const uint4* xi0_ark, uint4* dots_ark, uint32_t* hkw) {
@@ -328,7 +328,7 @@ __global__ __launch_bounds__(256) void k_tail_digits(const uint4* cs, const uint
     if (blockIdx.x >= nsb) {
         __shared__ uint32_t kw[10];
         const uint32_t sd = blockIdx.x - nsb;
-        tail_side_dot<Cv>(cs, zs, w, m, sd, f, xi0_ark, dots_ark, kw);
+        tail_side_dot<Cv, XI_DEV>(cs, zs, w, m, sd, f, xi0_ark, dots_ark, kw);
         if (threadIdx.x < 10) hkw[10 * sd + threadIdx.x] = kw[threadIdx.x];
         return;
     }
@@ -338,9 +338,9 @@ __global__ __launch_bounds__(256) void k_tail_digits(const uint4* cs, const uint
     const size_t ci = (j < m) ? m + j : j - m;
     Fe<S> c, wu;
     if (f.active) {
-        c = fe_add(fe_from_ark<S>(cs + 2 * ci), fe_mul(fe_from_ark<S>(cs + 2 * (ci + len)), fe_from_ark<S>(f.xinv)));
+        c = fe_add(fe_from_ark<S>(cs + 2 * ci), fe_mul(fe_from_ark<S>(cs + 2 * (ci + len)), tail_fold_xinv<S, XI_DEV>(f)));
         wu = fe_from_ark<S>(w + 2 * (u >> 1));
-        if (u & 1) wu = fe_mul(wu, fe_from_ark<S>(f.xi));
+        if (u & 1) wu = fe_mul(wu, tail_fold_xi<S, XI_DEV>(f));
     } else {
         c = fe_from_ark<S>(cs + 2 * ci);
         wu = f.w_one ? fe_one<S>() : fe_from_ark<S>(w + 2 * u);
@@ -363,7 +363,7 @@ __global__ __launch_bounds__(256) void k_tail_digits(const uint4* cs, const uint
 // side's counter); the last block to arrive on a side takes an agent acquire, sums the side's nbs + 1
 // partials and writes the side's XYZZ sum to out_xyzz + 8 sd, then resets the counter.  No block waits
 // for another.
-template <class Cv>
+template <class Cv, bool XI_DEV>
 __global__ __launch_bounds__(TAIL_THREADS, 1) void k_tail_round(const TailRoundArgs a, const TailFoldArgs f) {
     using F = typename Cv::Base;
     using S = typename Cv::Scalar;
@@ -380,9 +380,9 @@ __global__ __launch_bounds__(TAIL_THREADS, 1) void k_tail_round(const TailRoundA
             const size_t ci = sd ? j : m + j;
             Fe<S> c, wu;
             if (f.active) {  // c' = c_l + xi^-1 c_r over the unfolded c; w'[u] = w[u / 2] (xi w[u / 2] for odd u)
-                c = fe_add(fe_from_ark<S>(a.cs + 2 * ci), fe_mul(fe_from_ark<S>(a.cs + 2 * (ci + len)), fe_from_ark<S>(f.xinv)));
+                c = fe_add(fe_from_ark<S>(a.cs + 2 * ci), fe_mul(fe_from_ark<S>(a.cs + 2 * (ci + len)), tail_fold_xinv<S, XI_DEV>(f)));
                 wu = fe_from_ark<S>(a.w + 2 * (u >> 1));
-                if (u & 1) wu = fe_mul(wu, fe_from_ark<S>(f.xi));
+                if (u & 1) wu = fe_mul(wu, tail_fold_xi<S, XI_DEV>(f));
             } else {
                 c = fe_from_ark<S>(a.cs + 2 * ci);
                 wu = f.w_one ? fe_one<S>() : fe_from_ark<S>(a.w + 2 * u);
@@ -416,7 +416,7 @@ __global__ __launch_bounds__(TAIL_THREADS, 1) void k_tail_round(const TailRoundA
     // ---- hiding blocks 2 nbs + sd: side sd's dot, its GLV split and the term dot_sd H'
     const uint32_t sd = blockIdx.x - 2 * a.nbs;
     __shared__ uint32_t kw[10];
-    tail_side_dot<Cv>(a.cs, a.zs, a.w, m, sd, f, a.xi0_ark, a.dots_ark, kw);
+    tail_side_dot<Cv, XI_DEV>(a.cs, a.zs, a.w, m, sd, f, a.xi0_ark, a.dots_ark, kw);
     // dot H': lane t < 128 bit t of k1 with 2^t H', t >= 128 bit t - 128 of k2 with phi(2^(t-128) H')
     XYZZ<F> acc = xyzz_id<F>();
     if ((kw[tid >> 5] >> (tid & 31)) & 1u) {
@@ -524,7 +524,12 @@ int halo::tail_sums(int curve, const TailSums& a, bool with_final, hipStream_t s
 }
 
 int halo::tail_round_launch(int curve, const TailRoundArgs& a, const TailFoldArgs& f, hipStream_t s) {
-    DISPATCH_CURVE(curve, Cv, { hipLaunchKernelGGL(k_tail_round<Cv>, dim3(2 * a.nbs + 2), dim3(TAIL_THREADS), 0, s, a, f); });
+    DISPATCH_CURVE(curve, Cv, {
+        if (f.xi_dev)
+            hipLaunchKernelGGL((k_tail_round<Cv, true>), dim3(2 * a.nbs + 2), dim3(TAIL_THREADS), 0, s, a, f);
+        else
+            hipLaunchKernelGGL((k_tail_round<Cv, false>), dim3(2 * a.nbs + 2), dim3(TAIL_THREADS), 0, s, a, f);
+    });
     HALO_HIP(hipGetLastError());
     return HALO_OK;
 }
@@ -532,8 +537,12 @@ int halo::tail_round_launch(int curve, const TailRoundArgs& a, const TailFoldArg
 int halo::tail_digits_launch(int curve, const TailRoundArgs& a, const TailFoldArgs& f, uint32_t* scal, uint8_t* side,
                              uint32_t* hkw, hipStream_t s) {
     DISPATCH_CURVE(curve, Cv, {
-        hipLaunchKernelGGL(k_tail_digits<Cv>, dim3(grid_for(a.n0, 256) + 2), dim3(256), 0, s, a.cs, a.zs, a.w, a.n0, a.m, f,
-                           scal, side, a.xi0_ark, a.dots_ark, hkw);
+        if (f.xi_dev)
+            hipLaunchKernelGGL((k_tail_digits<Cv, true>), dim3(grid_for(a.n0, 256) + 2), dim3(256), 0, s, a.cs, a.zs, a.w, a.n0,
+                               a.m, f, scal, side, a.xi0_ark, a.dots_ark, hkw);
+        else
+            hipLaunchKernelGGL((k_tail_digits<Cv, false>), dim3(grid_for(a.n0, 256) + 2), dim3(256), 0, s, a.cs, a.zs, a.w, a.n0,
+                               a.m, f, scal, side, a.xi0_ark, a.dots_ark, hkw);
     });
     HALO_HIP(hipGetLastError());
     return HALO_OK;

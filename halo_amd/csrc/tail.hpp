@@ -71,7 +71,20 @@ struct TailFoldArgs {
     size_t wlen_in;  // fold weights before the fold
     int active;
     uint4* w_one;  // the first tail round: w = [1] (not yet in memory): use 1, and store it here
+    // non-null: xi | xi^-1 (ark, 64 B) are read from device memory instead of xi / xinv above (an opening whose
+    // transcript runs on the device, pcdl_open_fs.hip: the host never sees the challenge).  The launchers then
+    // pick the kernels' XI_DEV instantiation, so the by-value kernels carry no test of it.
+    const uint4* xi_dev;
 };
+// The fold's challenge and its inverse: the arguments, or (XI_DEV) device memory
+template <class S, bool XI_DEV>
+HALO_DEV Fe<S> tail_fold_xi(const TailFoldArgs& f) {
+    return XI_DEV ? fe_from_ark<S>(f.xi_dev) : fe_from_ark<S>(f.xi);
+}
+template <class S, bool XI_DEV>
+HALO_DEV Fe<S> tail_fold_xinv(const TailFoldArgs& f) {
+    return XI_DEV ? fe_from_ark<S>(f.xi_dev + 2) : fe_from_ark<S>(f.xinv);
+}
 
 // One tail round's inputs and outputs (k_tail_round; k_tail_digits reads the scalar vectors)
 struct TailRoundArgs {

@@ -3,9 +3,11 @@ MI355X backend.
 
 The Fiat-Shamir transcript (Poseidon sponge, crates/poseidon) stays with the caller: the round loop
 of ``open_without_eval`` (pcdl.rs:404-438) asks a ``challenge(xi_prev, L, R) -> xi`` callable for
-each round's challenge, exactly where the reference calls ``transcript.challenge()``.  The verifier alone
-also exists without a caller's transcript: ``succinct_check_device`` / ``check_device`` derive the PCDL
-challenges of a batch of instances on the device (halo_pcdl_succinct_check_fs_batch).
+each round's challenge, exactly where the reference calls ``transcript.challenge()``.  Both sides also exist
+without a caller's transcript: ``succinct_check_device`` / ``check_device`` derive the PCDL challenges of a batch
+of instances on the device (halo_pcdl_succinct_check_fs_batch), and ``open_device`` /
+``open_without_eval_device`` / ``open_device_many`` are the opening in one call with its sponge on the device
+(halo_pcdl_open_fs, halo_pcdl_open_fs_dev_multi).
 """
 from __future__ import annotations
 
@@ -325,6 +327,62 @@ def open(p, C, d: int, z, w=None, transcript=None, q=None, w_bar=None, curve="pa
     """pcdl::open (pcdl.rs:463-473): v = p(z) (evaluated on the device inside the session start,
     halo_pcdl_open_begin), then open_without_eval.  The EvalProof dict carries v."""
     return open_without_eval(p, C, d, z, None, w=w, transcript=transcript, q=q, w_bar=w_bar, curve=curve)
+
+
+def open_without_eval_device(p, C, d: int, z, v, w=None, q=None, w_bar=None, curve="pallas") -> dict:
+    """pcdl::open_without_eval (pcdl.rs:326-453) in one call with the PCDL transcript on the device
+    (halo_pcdl_open_fs): no caller's sponge and no host trip per round.  The arguments and the returned
+    EvalProof dict are open_without_eval's; v None is pcdl::open (v = p(z) on the device).
+    halo_poseidon_set_params must have installed the parameters of the curve's base field."""
+    H.ensure_device()
+    cid = _curve(curve)
+    lg = (d + 1).bit_length() - 1
+    p = H.fe_array(p) if len(p) else np.zeros((0, 4), dtype=np.uint64)
+    hid = w is not None
+    Ls, Rs = np.zeros((max(lg, 1), 8), dtype=np.uint64), np.zeros((max(lg, 1), 8), dtype=np.uint64)
+    U, c, v_out = np.zeros(8, dtype=np.uint64), np.zeros(4, dtype=np.uint64), np.zeros(4, dtype=np.uint64)
+    C_bar = np.zeros(8, dtype=np.uint64) if hid else None
+    w_prime = np.zeros(4, dtype=np.uint64) if hid else None
+    H.check(H.load().halo_pcdl_open_fs(
+        cid, H.ptr(p) if len(p) else None, len(p), d, H.ptr(H.fe_array(z, 1)),
+        H.ptr(H.fe_array(v, 1)) if v is not None else None, H.ptr(H.point_array(C).reshape(8)),
+        H.ptr(H.fe_array(w, 1)) if hid else None, H.ptr(H.fe_array(q, d)) if hid and q is not None else None,
+        H.ptr(H.fe_array(w_bar, 1)) if hid and w_bar is not None else None, H.ptr(Ls), H.ptr(Rs), H.ptr(U), H.ptr(c),
+        H.ptr(C_bar), H.ptr(w_prime), H.ptr(v_out)))
+    return {"Ls": [Ls[j].copy() for j in range(lg)], "Rs": [Rs[j].copy() for j in range(lg)], "U": U, "c": c,
+            "C_bar": C_bar, "w_prime": w_prime, "v": v_out}
+
+
+def open_device(p, C, d: int, z, w=None, q=None, w_bar=None, curve="pallas") -> dict:
+    """pcdl::open (pcdl.rs:463-473) in one call with the transcript on the device: open_without_eval_device with
+    v = p(z) formed on the device."""
+    return open_without_eval_device(p, C, d, z, None, w=w, q=q, w_bar=w_bar, curve=curve)
+
+
+def open_device_many(ps, Cs, d: int, zs, curve="pallas") -> list:
+    """k plain pcdl::open calls of one degree bound over device-resident coefficient vectors
+    (halo_pcdl_open_fs_dev_multi): ps are k torch device tensors of ark scalars (int64, 4 words per
+    coefficient, at most d + 1 coefficients), Cs their commitments (k, 8), zs the points (k, 4).  Every
+    opening's whole chain of launches is enqueued before any is waited for.  Returns k EvalProof dicts."""
+    import torch
+    H.ensure_device()
+    k = len(ps)
+    if k == 0:
+        return []
+    lg = (d + 1).bit_length() - 1
+    ts = [t.contiguous() for t in ps]
+    torch.cuda.current_stream().synchronize()  # the library orders its reads after the null stream only
+    ptrs = (ctypes.c_void_p * k)(*[t.data_ptr() for t in ts])
+    lens = (ctypes.c_size_t * k)(*[t.numel() // 4 for t in ts])
+    Ls, Rs = np.zeros((k, max(lg, 1), 8), dtype=np.uint64), np.zeros((k, max(lg, 1), 8), dtype=np.uint64)
+    U, c, v = np.zeros((k, 8), dtype=np.uint64), np.zeros((k, 4), dtype=np.uint64), np.zeros((k, 4), dtype=np.uint64)
+    if lg:
+        Ls, Rs = Ls.reshape(k * lg, 8), Rs.reshape(k * lg, 8)
+    H.check(H.load().halo_pcdl_open_fs_dev_multi(_curve(curve), k, ptrs, lens, d, H.ptr(H.fe_array(zs, k)),
+                                                 H.ptr(H.point_array(Cs)), H.ptr(Ls), H.ptr(Rs), H.ptr(U), H.ptr(c),
+                                                 H.ptr(v)))
+    return [{"Ls": [Ls[i * lg + j].copy() for j in range(lg)], "Rs": [Rs[i * lg + j].copy() for j in range(lg)],
+             "U": U[i].copy(), "c": c[i].copy(), "C_bar": None, "w_prime": None, "v": v[i].copy()} for i in range(k)]
 
 
 class HPoly:

@@ -22,7 +22,8 @@ backend ``B``; with ``DeviceBackend`` every data-parallel step runs in libhalo_g
 Out of scope (SURVEY §8 "out of scope"): circuit construction and witness generation (the witness
 polynomials here are synthetic), the Poseidon Fiat-Shamir transcript on the benchmarked path (challenges
 come from a seeded stand-in, ``Challenges``; ``naive_prover(..., transcript=new_transcript)`` runs the
-reference's sponges instead, so that halo_amd.plonk can verify the proof), the succinct checks of acc::prover (verifier arithmetic over lg n
+reference's sponges instead, so that halo_amd.plonk can verify the proof; on
+``DeviceBackend(curve, device_transcripts=True)`` the PCDL sponges of that mode run on the device), the succinct checks of acc::prover (verifier arithmetic over lg n
 elements) and the hiding terms (``naive_prover`` opens with w = None).  The generic pipeline also
 runs on the CPU restatement backend (oracle/prover_ref.py) at small n: tests/test_gpu_prover.py
 checks every commitment, evaluation and opening bit-exact against it.
@@ -335,7 +336,9 @@ def naive_prover(B, wit, n: int, chal: Challenges, acc_prev=None, keep=None, tra
         acc_prev = synthetic_accumulator(B, n, chal)
     B.sync()
     t5a = time.perf_counter()
-    if real:
+    if real and getattr(B, "device_transcripts", False):  # the two openings as one k = 2 call
+        q_r, q_r_omega = B.instances_open_device([(r, xi), (r_omega, xi * omega % m)], d)
+    elif real:
         q_r = B.instance_open(r, d, xi, transcript)
         q_r_omega = B.instance_open(r_omega, d, xi * omega % m, transcript)
     else:
@@ -420,13 +423,16 @@ def acc_prover(B, qs, d: int, chal: Challenges):
 class DeviceBackend:
     """Values are torch int64 (len, 4) device tensors of ark words; scalars are canonical ints."""
 
-    def __init__(self, curve: str = "pallas"):
+    def __init__(self, curve: str = "pallas", device_transcripts: bool = False):
         import torch
 
         from . import _lib as H
 
         H.ensure_device()
         self.torch, self.H, self.L = torch, H, H.load()
+        # round 5 under transcripts: the PCDL sponges run on the device (halo_pcdl_open_fs_dev_multi,
+        # pcdl.succinct_check_device) and the opened polynomials stay there
+        self.device_transcripts = device_transcripts
         self.curve = H.CURVES[curve]
         self.field = H.SCALAR_FIELD[self.curve]
         self.m = SCALAR_MODULUS[curve]
@@ -759,17 +765,32 @@ class DeviceBackend:
         return self.ipa_many([(p, n, z, h_prime)], [chal])[0]
 
     # -- round 5 under the reference's transcripts (naive_prover(..., transcript=new_transcript)): the
-    # host-array entry points of halo_amd.pcdl / halo_amd.acc; this mode is for correctness, not the benchmark
+    # host-array entry points of halo_amd.pcdl / halo_amd.acc; this mode is for correctness, not the benchmark.
+    # With device_transcripts the PCDL sponges run on the device and p is opened where it lies.
     def instance_open(self, p, d: int, z: int, new_transcript):
         """Instance::open (pcdl.rs:41-51) with w = None: C = commit(p), v = p(z), pi = open under a fresh
         PCDL sponge.  Returns dict(C, z, v, Ls, Rs, U, c); z, v, c canonical integers."""
         from . import pcdl
 
+        if self.device_transcripts:
+            return self.instances_open_device([(p, z)], d)[0]
         ph = np.ascontiguousarray(p.cpu().numpy().view(np.uint64))
         C = pcdl.commit(ph, d, curve=self.curve)
         pi = pcdl.open(ph, C, d, self.fe(z), transcript=new_transcript("PCDL"), curve=self.curve)
         return {"C": C, "z": z, "v": self.to_int(pi["v"]), "Ls": pi["Ls"], "Rs": pi["Rs"], "U": pi["U"],
                 "c": self.to_int(pi["c"])}
+
+    def instances_open_device(self, polys_points, d: int):
+        """Instance::open for k independent (p, z) with the transcripts on the device: the commitments as one
+        batch, then the k openings side by side in one halo_pcdl_open_fs_dev_multi call; p never leaves the
+        device.  Returns instance_open's dicts."""
+        from . import pcdl
+
+        Cs = self.commit_many([p for p, _ in polys_points])
+        pis = pcdl.open_device_many([p for p, _ in polys_points], np.stack(Cs), d,
+                                    np.stack([self.fe(z) for _, z in polys_points]), curve=self.curve)
+        return [{"C": C, "z": z, "v": self.to_int(pi["v"]), "Ls": pi["Ls"], "Rs": pi["Rs"], "U": pi["U"],
+                 "c": self.to_int(pi["c"])} for C, (_, z), pi in zip(Cs, polys_points, pis)]
 
     def acc_prove(self, qs, d: int, new_transcript):
         """acc::prover (acc.rs:178-198) over instances in instance_open's form; the accumulator in the same form."""
@@ -778,7 +799,7 @@ class DeviceBackend:
         insts = [pcdl.Instance(np.asarray(q["C"], dtype=np.uint64), d, self.fe(q["z"]), self.fe(q["v"]),
                                {"Ls": np.stack(q["Ls"]), "Rs": np.stack(q["Rs"]), "U": np.asarray(q["U"], dtype=np.uint64),
                                 "c": self.fe(q["c"]), "C_bar": None, "w_prime": None}) for q in qs]
-        a = acc.prover(insts, new_transcript, self.curve)
+        a = acc.prover(insts, new_transcript, self.curve, device_transcripts=self.device_transcripts)
         return {"C": a.C, "z": self.to_int(a.z), "v": self.to_int(a.v), "Ls": a.pi["Ls"], "Rs": a.pi["Rs"],
                 "U": a.pi["U"], "c": self.to_int(a.pi["c"])}
 

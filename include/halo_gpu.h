@@ -372,6 +372,35 @@ int halo_pcdl_open_blind(halo_ipa_session* s, const halo_fe_t* q, const halo_fe_
 int halo_pcdl_open_combine(halo_ipa_session* s, const halo_fe_t* alpha, const halo_wrapped_point_t* C,
                            const halo_fe_t* w, halo_fe_t* w_prime, halo_wrapped_point_t* C_prime);
 int halo_pcdl_open_start(halo_ipa_session* s, const halo_wrapped_point_t* H, const halo_fe_t* xi0);
+/* pcdl::open_without_eval / pcdl::open (pcdl.rs:326-473) as ONE call over host arrays and the resident SRS
+ * with its (S, H): the PCDL transcript (Sponge::new(Protocols::PCDL), pcdl.rs:336) runs on the device, so
+ * the lg n rounds are one chain of launches with one wait at the end; the caller brings no sponge.
+ * halo_poseidon_set_params must have installed the parameters of the curve's base field.
+ *   p: len coefficients; the assertions of halo_pcdl_open_begin: n = d + 1 > 1 a power of two,
+ *      p.degree() <= d, d <= D
+ *   v: the claimed evaluation, or NULL: pcdl::open, v = p(z) is formed on the device (pcdl.rs:471)
+ *   w: the commitment's randomness, or NULL: the plain branch.  With w: q (d coefficients) and w_bar are the
+ *      draws the reference takes from its rng (pcdl.rs:347,352), and C_bar, w_prime receive the proof's
+ *      hiding part (all four required; alpha comes back to the host once, between halo_pcdl_open_blind's
+ *      and halo_pcdl_open_combine's work)
+ *   Ls, Rs: lg n WrappedPoints each; U, c; v_out (optional): the v the transcript absorbed
+ * A round challenge that is zero (the reference unwraps its inverse, pcdl.rs:430) is HALO_EINVAL.  Argument
+ * errors name the call and are reported before the device is touched; missing Poseidon parameters are
+ * HALO_EINVAL, no GPU is HALO_EDEVICE.  The session the call uses goes back to the pool on every path. */
+int halo_pcdl_open_fs(halo_curve_t curve, const halo_fe_t* p, size_t len, size_t d, const halo_fe_t* z,
+                      const halo_fe_t* v, const halo_wrapped_point_t* C, const halo_fe_t* w, const halo_fe_t* q,
+                      const halo_fe_t* w_bar, halo_wrapped_point_t* Ls, halo_wrapped_point_t* Rs,
+                      halo_wrapped_point_t* U, halo_fe_t* c, halo_wrapped_point_t* C_bar, halo_fe_t* w_prime,
+                      halo_fe_t* v_out);
+/* k plain pcdl::open calls of one degree bound d over device-resident coefficient vectors (d_p[i]: lens[i] <=
+ * d + 1 ark scalars on the device, ordered on the null stream as for halo_ipa_begin_dev; the length
+ * stands for the degree), at z[i] with commitment C[i]: each opening has its own pooled session and
+ * stream, and every session's whole chain is enqueued before any is waited for (Instance::open twice
+ * in the prover's round 5).  Opening i's rounds are Ls[i lg n + j], Rs[i lg n + j]; U[i], c[i]; v_out
+ * (optional) receives v[i] = p_i(z[i]).  k = 0 is HALO_OK.  An argument error opens no session. */
+int halo_pcdl_open_fs_dev_multi(halo_curve_t curve, size_t k, const void* const* d_p, const size_t* lens, size_t d,
+                                const halo_fe_t* z, const halo_wrapped_point_t* C, halo_wrapped_point_t* Ls,
+                                halo_wrapped_point_t* Rs, halo_wrapped_point_t* U, halo_fe_t* c, halo_fe_t* v_out);
 /* L = <c_r, G_l> + H' <c_r, z_l>,  R = <c_l, G_r> + H' <c_l, z_r>  (pcdl.rs:412-418) */
 int halo_ipa_round_lr(halo_ipa_session* s, halo_wrapped_point_t* L, halo_wrapped_point_t* R);
 /* G_l[j] = G_l[j] + xi G_r[j] (affine), c_l[j] += xi^-1 c_r[j], z_l[j] += xi z_r[j]; m /= 2

@@ -22,7 +22,8 @@
 //   k_bisect_left        D(left_s) = -P_s + the root pass's terms rho_i U_i over the left half
 //   k_bisect_split       D(right_s) = D(node_s) - D(left_s), the two flags, ok[i] = 0 for a failing leaf
 // On top of the core: halo_pcdl_decide_batch, halo_pcdl_check_fs_batch (fs_device, then the decider with
-// live = the succinct verdicts, the xis never leaving the device) and their _dev forms.
+// live = the succinct verdicts, the xis never leaving the device) and their _dev forms.  The scratch carving and
+// the uploads are scratch_layout.hpp's / upload_parts, the scalar checks host_scalar.hpp's (check_rho).
 #include <vector>
 
 #include "curve.hpp"
@@ -30,6 +31,7 @@
 #include "decider_bisect.hpp"
 #include "decider_plan.hpp"
 #include "dispatch.hpp"
+#include "host_scalar.hpp"
 #include "lincomb.hpp"
 #include "msm.hpp"
 #include "pcdl_fs.hpp"
@@ -189,8 +191,6 @@ __global__ __launch_bounds__(DEC_THREADS) void k_check_codes(const uint8_t* __re
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-static size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 // A stage that is more than one kernel (an MSM): its halo_profile_read time is the span on `s` between begin
 // and end, its launch count the number of stages.
 struct StageScope {
@@ -202,14 +202,6 @@ struct StageScope {
         if (p.slot >= 0) (void)hipEventRecord(p.b, p.s);
     }
 };
-
-static int check_decider_srs(const DeviceState* st, int curve, size_t d) {
-    const SrsState& srs = st->srs[curve];
-    // (n = d + 1 here, so the SRS prefix Gs[0..d] is never shorter than the coefficients: pedersen::commit's
-    // "ms must be larger than Gs", halo_pcdl_decider_commit's HALO_ELENGTH, cannot arise once d <= D)
-    if (!srs.n || d > srs.n - 1) return set_error(HALO_ESRSRANGE, "d was larger than D!");
-    return HALO_OK;
-}
 
 static int decide_exact(DeviceState* st, const DecideCall& a, hipStream_t s) {
     const SrsState& srs = st->srs[a.curve];
@@ -257,11 +249,12 @@ static int decide_combined(DeviceState* st, const DecideCall& a, hipStream_t s, 
     const size_t k = a.k, n = a.d + 1;
     const uint32_t lg = ilog2(n);
     const int field = a.curve == HALO_PALLAS ? HALO_FP : HALO_FQ;
-    const size_t o_rho = 0, o_U = o_rho + align256(k * 32), o_P = o_U + align256(k * 64), o_neg = o_P + 256, o_sum = o_neg + 256,
-                 o_comb = o_sum + 256, o_valid = o_comb + 256, total = o_valid + (bisect ? align256(k) : 0);
+    ScratchLayout lay;  // the masked weights and points, P, -P (WrappedPoints), the sum (XYZZ), its byte, the validity bytes
+    const size_t o_rho = lay.take(k * 32), o_U = lay.take(k * 64), o_P = lay.take(64), o_neg = lay.take(64), o_sum = lay.take(128),
+                 o_comb = lay.take(1), o_valid = lay.take(bisect ? k : 0);
     HALO_CHECK(st->decider[0].reserve(n * 32));
     HALO_CHECK(st->decider[1].reserve(hpoly_table_elems(k, lg) * 32));
-    HALO_CHECK(st->decider[2].reserve(total));
+    HALO_CHECK(st->decider[2].reserve(lay.total()));
     HALO_CHECK(st->lincomb_terms.reserve(k * 129));
     uint8_t* base = st->decider[2].as<uint8_t>();
     uint4 *rho_m = (uint4*)(base + o_rho), *U_m = (uint4*)(base + o_U), *P = (uint4*)(base + o_P), *neg = (uint4*)(base + o_neg);
@@ -294,7 +287,9 @@ static int decide_combined(DeviceState* st, const DecideCall& a, hipStream_t s, 
 }
 
 int decide_device(DeviceState* st, const DecideCall& a, hipStream_t s) {
-    HALO_CHECK(check_decider_srs(st, a.curve, a.d));
+    // (n = d + 1 here, so the SRS prefix Gs[0..d] is never shorter than the coefficients: pedersen::commit's
+    // "ms must be larger than Gs", halo_pcdl_decider_commit's HALO_ELENGTH, cannot arise once d <= D)
+    HALO_CHECK(check_verifier_srs(nullptr, st, a.curve, a.d, false));
     if (a.rho && a.k > 1) return decide_combined(st, a, s);
     HALO_CHECK(decide_exact(st, a, s));
     if (a.rho && a.combined) {  // k = 1 costs the same either way
@@ -360,7 +355,7 @@ static_assert(sizeof(BisectNode) == sizeof(uint4), "the kernels read a node as o
 
 int decide_bisect_device(DeviceState* st, const DecideCall& a, hipStream_t s) {
     if (!a.rho || a.k < 2) return decide_device(st, a, s);
-    HALO_CHECK(check_decider_srs(st, a.curve, a.d));
+    HALO_CHECK(check_verifier_srs(nullptr, st, a.curve, a.d, false));
     const SrsState& srs = st->srs[a.curve];
     const size_t k = a.k, n = a.d + 1;
     CombinedOut root;
@@ -370,15 +365,17 @@ int decide_bisect_device(DeviceState* st, const DecideCall& a, hipStream_t s) {
     if (combined) return HALO_OK;  // ok = the validity bytes
     // The descent's own buffers: the root pass's tables, terms and defect stay where they are.  A level has at
     // most k / 2 nodes and k children.
-    const size_t fmax = k / 2, o_pong0 = align256(k * 128), o_pong1 = o_pong0 + align256(k * 128);
-    const size_t o_P = align256(fmax * 16), o_left = o_P + align256(fmax * 64), o_flags = o_left + align256(fmax * 128);
-    HALO_CHECK(st->bisect[1].reserve(o_pong1 + align256(k * 128)));
-    HALO_CHECK(st->bisect[2].reserve(o_flags + align256(2 * fmax)));
+    const size_t fmax = k / 2;
+    ScratchLayout l1, l2;
+    const size_t o_terms = l1.take(k * 128), o_pong0 = l1.take(k * 128), o_pong1 = l1.take(k * 128);
+    const size_t o_segs = l2.take(fmax * 16), o_P = l2.take(fmax * 64), o_left = l2.take(fmax * 128), o_flags = l2.take(2 * fmax);
+    HALO_CHECK(st->bisect[1].reserve(l1.total()));
+    HALO_CHECK(st->bisect[2].reserve(l2.total()));
     uint8_t *b1 = st->bisect[1].as<uint8_t>(), *b2 = st->bisect[2].as<uint8_t>();
-    HALO_HIP(hipMemcpyAsync(b1, st->lincomb_terms.ptr, k * 128, hipMemcpyDeviceToDevice, s));  // lincomb_device reuses its buffer
+    HALO_HIP(hipMemcpyAsync(b1 + o_terms, st->lincomb_terms.ptr, k * 128, hipMemcpyDeviceToDevice, s));  // lincomb_device reuses its buffer
     HALO_HIP(hipMemcpyAsync(a.ok, root.valid, k, hipMemcpyDeviceToDevice, s));
-    BisectDevice ev{st, a, s, root.sum, {(uint4*)(b1 + o_pong0), (uint4*)(b1 + o_pong1)}, 0, (uint4*)b2, (uint4*)(b2 + o_P),
-                    (uint4*)(b2 + o_left), b2 + o_flags, (const uint4*)b1, {}, {}};
+    BisectDevice ev{st, a, s, root.sum, {(uint4*)(b1 + o_pong0), (uint4*)(b1 + o_pong1)}, 0, (uint4*)(b2 + o_segs), (uint4*)(b2 + o_P),
+                    (uint4*)(b2 + o_left), b2 + o_flags, (const uint4*)(b1 + o_terms), {}, {}};
     const int W = srs.shifted_c ? msm_windows(srs.shifted_c) : 1;
     std::vector<uint8_t> host_ok(k, 1);  // the kernels clear a.ok themselves
     return bisect_descend(k, n, (size_t)std::max<long long>(tuning(TUNE_DECIDE_GROUP_SCALARS), 1), W, ev, host_ok.data());
@@ -387,7 +384,7 @@ int decide_bisect_device(DeviceState* st, const DecideCall& a, hipStream_t s) {
 int decide_resolved(DeviceState* st, const DecideCall& a, hipStream_t s) {
     if (!a.rho || a.k < 2) return decide_device(st, a, s);
     if (tuning(TUNE_DECIDE_BISECT) > 0) return decide_bisect_device(st, a, s);
-    HALO_CHECK(check_decider_srs(st, a.curve, a.d));
+    HALO_CHECK(check_verifier_srs(nullptr, st, a.curve, a.d, false));
     CombinedOut root;
     HALO_CHECK(decide_combined(st, a, s, false, &root));
     uint8_t combined = 0;
@@ -402,7 +399,7 @@ int decide_resolved(DeviceState* st, const DecideCall& a, hipStream_t s) {
 static int check_decide_args(const char* call, int curve, size_t d, size_t k, const void* xis, const void* U, const void* ok,
                              bool& done) {
     done = false;
-    if (curve != HALO_PALLAS && curve != HALO_VESTA) return set_error(HALO_EINVAL, "%s: unknown curve", call);
+    if (!valid_curve(curve)) return set_error(HALO_EINVAL, "%s: unknown curve", call);
     if (k == 0) {
         done = true;
         return HALO_OK;
@@ -412,23 +409,6 @@ static int check_decide_args(const char* call, int curve, size_t d, size_t k, co
     if (ilog2(n) > 28) return set_error(HALO_EINVAL, "%s: n (%zu) out of range", call, n);
     if (!xis || !U || !ok) return set_error(HALO_EINVAL, "%s: null pointer", call);
     if (k > LINCOMB_MAX_ITEMS / 4) return set_error(HALO_EINVAL, "%s: %zu instances in one call", call, k);
-    return HALO_OK;
-}
-
-static bool host_below(int curve, const halo_fe_t& x) {
-    const uint64_t(&p)[4] = curve == HALO_PALLAS ? FpCfg::MODULUS64 : FqCfg::MODULUS64;  // the scalar field
-    for (int q = 3; q >= 0; q--)
-        if (x.l[q] != p[q]) return x.l[q] < p[q];
-    return false;
-}
-
-// A zero weight would leave its instance unchecked.
-static int check_rho(const char* call, int curve, const halo_fe_t* rho, size_t k) {
-    for (size_t i = 0; rho && i < k; i++) {
-        if (!(rho[i].l[0] | rho[i].l[1] | rho[i].l[2] | rho[i].l[3]))
-            return set_error(HALO_EINVAL, "%s: rho[%zu] is zero", call, i);
-        if (!host_below(curve, rho[i])) return set_error(HALO_EINVAL, "%s: rho[%zu] is not below the modulus", call, i);
-    }
     return HALO_OK;
 }
 
@@ -477,13 +457,13 @@ extern "C" int halo_pcdl_decide_batch(halo_curve_t curve, size_t d, size_t k, co
     if (done) return HALO_OK;
     const size_t lg = ilog2(d + 1), row = lg + 1;
     for (size_t j = 0; j < k * row; j++)
-        if (!host_below(curve, xis[j]))
+        if (!scalar_below(curve, xis[j]))
             return set_error(HALO_EINVAL, "%s: xi_%zu of instance %zu is not below the modulus", call, j % row, j / row);
     HALO_CHECK(check_rho(call, curve, rho, k));
     DeviceState* st = current_state();
     if (!st) return HALO_EDEVICE;
     std::lock_guard<std::mutex> g(st->mu);
-    HALO_CHECK(check_decider_srs(st, curve, d));
+    HALO_CHECK(check_verifier_srs(call, st, curve, d, false));
     // only the live instances travel
     std::vector<size_t> idx;
     for (size_t i = 0; i < k; i++) {
@@ -494,31 +474,23 @@ extern "C" int halo_pcdl_decide_batch(halo_curve_t curve, size_t d, size_t k, co
     if (!m) return HALO_OK;
     hipStream_t s = 0;
     ScratchUse su(st, s);
-    const size_t o_xis = 0, o_U = o_xis + align256(m * row * 32), o_rho = o_U + align256(m * 64),
-                 n_in = o_rho + align256(rho ? m * 32 : 0);
-    HALO_CHECK(st->scratch[0].reserve(n_in));
     HALO_CHECK(st->scratch[1].reserve(m + 256));
-    uint8_t *di = st->scratch[0].as<uint8_t>(), *dout = st->scratch[1].as<uint8_t>();
-    if (m == k) {
-        HALO_CHECK(copy_h2d(di + o_xis, xis, k * row * 32, s));
-        HALO_CHECK(copy_h2d(di + o_U, U, k * 64, s));
-        if (rho) HALO_CHECK(copy_h2d(di + o_rho, rho, k * 32, s));
-    } else {
-        std::vector<halo_fe_t> hx(m * row), hr(rho ? m : 0);
-        std::vector<halo_wrapped_point_t> hU(m);
+    uint8_t* dout = st->scratch[1].as<uint8_t>();
+    std::vector<halo_fe_t> hx, hr;
+    std::vector<halo_wrapped_point_t> hU;
+    if (m != k) {  // the live rows, gathered
+        hx.resize(m * row), hU.resize(m), hr.resize(rho ? m : 0);
         for (size_t j = 0; j < m; j++) {
             std::copy(xis + idx[j] * row, xis + (idx[j] + 1) * row, hx.begin() + j * row);
             hU[j] = U[idx[j]];
             if (rho) hr[j] = rho[idx[j]];
         }
-        // pageable sources: each copy returns once the source has been read
-        HALO_CHECK(copy_h2d(di + o_xis, hx.data(), m * row * 32, s));
-        HALO_CHECK(copy_h2d(di + o_U, hU.data(), m * 64, s));
-        if (rho) HALO_CHECK(copy_h2d(di + o_rho, hr.data(), m * 32, s));
-        HALO_HIP(hipStreamSynchronize(s));
+        xis = hx.data(), U = hU.data(), rho = rho ? hr.data() : nullptr;
     }
-    uint8_t* d_comb = dout + align256(m);
-    DecideCall a{(int)curve, d, m, di + o_xis, di + o_U, nullptr, rho ? di + o_rho : nullptr, dout, d_comb};
+    std::vector<const void*> at;
+    HALO_CHECK(upload_parts(st, HostParts{{xis, m * row * 32}, {U, m * 64}, {rho, rho ? m * 32 : 0}}, s, at));
+    if (m != k) HALO_HIP(hipStreamSynchronize(s));  // pageable sources: each copy returns once the source has been read
+    DecideCall a{(int)curve, d, m, at[0], at[1], nullptr, at[2], dout, dout + align256(m)};
     HALO_CHECK(decide_resolved(st, a, s));
     std::vector<uint8_t> got(m);
     HALO_CHECK(copy_d2h(got.data(), dout, m, s));
@@ -531,9 +503,10 @@ extern "C" int halo_pcdl_decide_batch(halo_curve_t curve, size_t d, size_t k, co
 static int check_fs_run(const char* call, DeviceState* st, FsCall a, const void* d_rho, void* d_code, void* d_combined,
                         bool host_fallback, hipStream_t s) {
     const size_t k = a.k, lg = ilog2(a.d + 1);
-    HALO_CHECK(check_decider_srs(st, a.curve, a.d));
-    const size_t o_xis = 0, o_succ = o_xis + align256(k * (lg + 1) * 32), o_dec = o_succ + align256(k), o_comb = o_dec + align256(k);
-    HALO_CHECK(st->decider[3].reserve(o_comb + 256));
+    HALO_CHECK(check_verifier_srs(call, st, a.curve, a.d, false));
+    ScratchLayout lay;
+    const size_t o_xis = lay.take(k * (lg + 1) * 32), o_succ = lay.take(k), o_dec = lay.take(k), o_comb = lay.take(1);
+    HALO_CHECK(st->decider[3].reserve(lay.total()));
     uint8_t* base = st->decider[3].as<uint8_t>();
     a.xis_out = base + o_xis;
     a.alpha_out = nullptr;
@@ -582,18 +555,15 @@ extern "C" int halo_pcdl_check_fs_batch(halo_curve_t curve, size_t d, size_t k, 
     DeviceState* st = current_state();
     if (!st) return HALO_EDEVICE;
     std::lock_guard<std::mutex> g(st->mu);
-    HALO_CHECK(check_decider_srs(st, curve, d));
+    HALO_CHECK(check_verifier_srs(call, st, curve, d, false));
     hipStream_t s = 0;
     ScratchUse su(st, s);
-    FsCall a;
-    HALO_CHECK(fs_upload(st, host, a, s));
-    HALO_CHECK(st->scratch[1].reserve(align256(k) + align256(rho ? k * 32 : 0)));
+    HostParts in = fs_host_parts(host);
+    in.add(rho, rho ? k * 32 : 0);  // the decider's weights, after the succinct check's own rows
+    std::vector<const void*> at;
+    HALO_CHECK(upload_parts(st, in, s, at));
+    HALO_CHECK(st->scratch[1].reserve(k));
     uint8_t* dout = st->scratch[1].as<uint8_t>();
-    void* d_rho = nullptr;
-    if (rho) {
-        d_rho = dout + align256(k);
-        HALO_CHECK(copy_h2d(d_rho, rho, k * 32, s));
-    }
-    HALO_CHECK(check_fs_run(call, st, a, d_rho, dout, nullptr, true, s));
+    HALO_CHECK(check_fs_run(call, st, fs_dev_call(host, at), at.back(), dout, nullptr, true, s));
     return copy_d2h(ok_out, dout, k, s);
 }

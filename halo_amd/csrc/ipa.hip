@@ -635,7 +635,7 @@ static int ipa_begin(halo_curve_t curve, size_t n, const halo_wrapped_point_t* g
                      const halo_fe_t* zs_host, const halo_fe_t* z, const halo_wrapped_point_t* H_prime,
                      halo_ipa_session** out, bool cs_on_device = false, const halo_fe_t* xi0 = nullptr,
                      const halo_wrapped_point_t* Hpt = nullptr) {
-    if (curve != HALO_PALLAS && curve != HALO_VESTA) return set_error(HALO_EINVAL, "unknown curve");
+    if (!valid_curve(curve)) return set_error(HALO_EINVAL, "unknown curve");
     if (!cs || !(z || zs_host) || !(H_prime || (xi0 && Hpt)) || !out)
         return set_error(HALO_EINVAL, "halo_ipa_begin: null argument");
     if (n <= 1) return set_error(HALO_EINVAL, "assertion failed: n > 1");
@@ -1330,7 +1330,7 @@ extern "C" int halo_ipa_end_multi(halo_ipa_session* const* ses, size_t k, halo_w
 extern "C" int halo_ipa_fold_host(halo_curve_t curve, halo_wrapped_point_t* gs, halo_fe_t* cs, halo_fe_t* zs, size_t m,
                                   const halo_fe_t* xi, const halo_fe_t* xi_inv) {
     clear_error();
-    if (curve != HALO_PALLAS && curve != HALO_VESTA) return set_error(HALO_EINVAL, "unknown curve");
+    if (!valid_curve(curve)) return set_error(HALO_EINVAL, "unknown curve");
     if (!xi || !xi_inv || (m && (!gs || !cs || !zs))) return set_error(HALO_EINVAL, "halo_ipa_fold_host: null argument");
     if (!m) return HALO_OK;
     DeviceState* st = current_state();

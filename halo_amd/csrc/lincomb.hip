@@ -9,10 +9,11 @@
 //                     four quad doublings and two table additions (phi applied as an entry is read)
 //   k_lincomb_sum     one wave per item: its t terms and the optional affine addend, summed with the
 //                     complete addition (equal and opposite partial sums, identity terms)
+// The host-scalar succinct check computes h(z) and e with HostScalar (host_scalar.hpp).
 #include "curve.hpp"
 #include "dispatch.hpp"
 #include "glv.hpp"
-#include "host_mont.hpp"
+#include "host_scalar.hpp"
 #include "lincomb.hpp"
 #include "points.hpp"
 #include "quad_ladder.hpp"
@@ -142,53 +143,10 @@ __global__ __launch_bounds__(LINCOMB_THREADS) void k_lincomb_sum(const uint4* __
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-static bool valid_curve(int c) { return c == HALO_PALLAS || c == HALO_VESTA; }
-
-// Scalar arithmetic of one curve on ark Montgomery limbs (host_mont.hpp), for the succinct check's
-// h(z) and e.  Inputs below the modulus.
-struct HostScalar {
-    const HostMont& M;
-    bool canonical(const uint64_t (&a)[4]) const { return !M.geq_p(a); }
-    static bool is_zero(const uint64_t (&a)[4]) { return !(a[0] | a[1] | a[2] | a[3]); }
-    void add(const uint64_t (&a)[4], const uint64_t (&b)[4], uint64_t (&r)[4]) const {  // a + b < 2^256
-        unsigned __int128 c = 0;
-        uint64_t t[4];
-        for (int i = 0; i < 4; i++) {
-            c += (unsigned __int128)a[i] + b[i];
-            t[i] = (uint64_t)c;
-            c >>= 64;
-        }
-        if (M.geq_p(t)) M.sub_p(t);
-        for (int i = 0; i < 4; i++) r[i] = t[i];
-    }
-    void neg(const uint64_t (&a)[4], uint64_t (&r)[4]) const {
-        if (is_zero(a)) {
-            for (int i = 0; i < 4; i++) r[i] = 0;
-            return;
-        }
-        unsigned __int128 bw = 0;
-        for (int i = 0; i < 4; i++) {
-            const unsigned __int128 d = (unsigned __int128)M.p[i] - a[i] - bw;
-            r[i] = (uint64_t)d;
-            bw = (d >> 64) & 1;
-        }
-    }
-    void sub(const uint64_t (&a)[4], const uint64_t (&b)[4], uint64_t (&r)[4]) const {
-        uint64_t nb[4];
-        neg(b, nb);
-        add(a, nb, r);
-    }
-};
-static const HostMont& scalar_mont(int curve) {
-    static const HostMont fp(FpCfg::MODULUS64), fq(FqCfg::MODULUS64);
-    return curve == HALO_PALLAS ? fp : fq;
-}
-static const HostMont& base_mont(int curve) { return scalar_mont(curve == HALO_PALLAS ? HALO_VESTA : HALO_PALLAS); }
-
 // (0, 0) or y^2 = x^3 + 5 over the curve's base field, ark limbs below the modulus
 static bool host_on_curve_or_id(int curve, const halo_wrapped_point_t& P) {
     const HostScalar F{base_mont(curve)};
-    if (!F.canonical(P.x) || !F.canonical(P.y)) return false;
+    if (F.M.geq_p(P.x) || F.M.geq_p(P.y)) return false;
     if (HostScalar::is_zero(P.x) && HostScalar::is_zero(P.y)) return true;
     uint64_t y2[4], x2[4], x3[4], five[4], rhs[4];
     F.M.mul(P.y, P.y, y2);
@@ -290,9 +248,8 @@ extern "C" int halo_point_lincomb_batch(halo_curve_t curve, const halo_wrapped_p
     bool done;
     HALO_CHECK(check_lincomb_args("halo_point_lincomb_batch", curve, pts, scalars, k, t, out, done));
     if (done) return HALO_OK;
-    const HostScalar Sc{scalar_mont(curve)};
     for (size_t j = 0; j < k * t; j++)
-        if (!Sc.canonical(scalars[j].l))
+        if (!scalar_below(curve, scalars[j]))
             return set_error(HALO_EINVAL, "halo_point_lincomb_batch: scalar %zu is not below the modulus", j);
     if (t == 0) {  // no term: the addends themselves, on the host
         for (size_t i = 0; i < k; i++) {
@@ -341,17 +298,16 @@ extern "C" int halo_pcdl_succinct_check_batch(halo_curve_t curve, size_t d, size
     DeviceState* st = current_state();
     if (!st) return HALO_EDEVICE;
     std::lock_guard<std::mutex> g(st->mu);
+    HALO_CHECK(check_verifier_srs(call, st, curve, d, true));
     const SrsState& srs = st->srs[curve];
-    if (!srs.n || d > srs.n - 1) return set_error(HALO_ESRSRANGE, "d was larger than D!");
-    if (!srs.has_sh) return set_error(HALO_ESRSRANGE, "%s: no (S, H) uploaded", call);
     // the scalars of every term, on the host
     const HostScalar Sc{scalar_mont(curve)};
     const HostMont& M = Sc.M;
     for (size_t i = 0; i < k; i++) {
-        if (!Sc.canonical(z[i].l) || !Sc.canonical(v[i].l) || !Sc.canonical(c[i].l))
+        if (!scalar_below(curve, z[i]) || !scalar_below(curve, v[i]) || !scalar_below(curve, c[i]))
             return set_error(HALO_EINVAL, "%s: a scalar of instance %zu is not below the modulus", call, i);
         for (size_t j = 0; j <= lg; j++)
-            if (!Sc.canonical(xis[i * (lg + 1) + j].l))
+            if (!scalar_below(curve, xis[i * (lg + 1) + j]))
                 return set_error(HALO_EINVAL, "%s: xi_%zu of instance %zu is not below the modulus", call, j, i);
         for (size_t j = 1; j <= lg; j++)
             if (HostScalar::is_zero(xis[i * (lg + 1) + j].l))

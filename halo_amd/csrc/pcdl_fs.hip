@@ -18,9 +18,10 @@
 // through device memory: both kernels are then the same walk over the transcript and no state format
 // exists.  Hiding and plain instances reach the rate-2 boundary at different elements, so a wave that
 // mixes them runs its permutations in two groups; a call whose instances all hide, or none, does not
-// diverge.
+// diverge.  The host side's shared pieces: scratch_layout.hpp, host_scalar.hpp, sponge_launch.hpp, runtime.hpp.
 #include "curve.hpp"
 #include "dispatch.hpp"
+#include "host_scalar.hpp"
 #include "lincomb.hpp"
 #include "outer_sponge.hpp"
 #include "pcdl_fs.hpp"
@@ -204,7 +205,7 @@ __global__ __launch_bounds__(FS_THREADS) void k_pcdl_terms(const uint4* __restri
 // Everything that needs no device; done: an empty batch.
 int check_fs_args(const char* call, const FsCall& a, bool& done) {
     done = false;
-    if (a.curve != HALO_PALLAS && a.curve != HALO_VESTA) return set_error(HALO_EINVAL, "%s: unknown curve", call);
+    if (!valid_curve(a.curve)) return set_error(HALO_EINVAL, "%s: unknown curve", call);
     if (a.k == 0) {
         done = true;
         return HALO_OK;
@@ -216,27 +217,22 @@ int check_fs_args(const char* call, const FsCall& a, bool& done) {
         return set_error(HALO_EINVAL, "%s: null pointer", call);
     if (a.hiding && (!a.C_bar || !a.w_prime)) return set_error(HALO_EINVAL, "%s: hiding without C_bar and w_prime", call);
     if (a.k > LINCOMB_MAX_ITEMS / (2 * lg + 2)) return set_error(HALO_EINVAL, "%s: %zu instances in one call", call, a.k);
-    if (!poseidon_params_set(base_field(a.curve)))
-        return set_error(HALO_EINVAL, "%s: no Poseidon parameters for the curve's base field (halo_poseidon_set_params)",
-                         call);
-    return HALO_OK;
+    return require_poseidon_params(call, a.curve);
 }
-
-static size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 
 // The launches of one call over device pointers, all on `s`.  st->mu and a ScratchUse of `s` held; a.k >= 1.
 int fs_device(const char* call, DeviceState* st, const FsCall& a, hipStream_t s) {
+    HALO_CHECK(check_verifier_srs(call, st, a.curve, a.d, true));
     const SrsState& srs = st->srs[a.curve];
-    if (!srs.n || a.d > srs.n - 1) return set_error(HALO_ESRSRANGE, "d was larger than D!");
-    if (!srs.has_sh) return set_error(HALO_ESRSRANGE, "%s: no (S, H) uploaded", call);
     const size_t k = a.k, lg = ilog2(a.d + 1), t = 2 * lg + 2;
     const uint32_t* params;
     HALO_CHECK(poseidon_device_params(st, base_field(a.curve), &params));
     // one scratch buffer: the term rows, the sums, and what the caller did not ask to see
-    const size_t o_pts = 0, o_sc = o_pts + align256(k * t * 64), o_sum = o_sc + align256(k * t * 32),
-                 o_xis = o_sum + align256(k * 128), o_cp = o_xis + (a.xis_out ? 0 : align256(k * (lg + 1) * 32)),
-                 o_bad = o_cp + (a.hiding ? align256(k * 64) : 0), total = o_bad + (a.hiding ? align256(k) : 0);
-    HALO_CHECK(st->scratch[7].reserve(total));
+    ScratchLayout lay;
+    const size_t o_pts = lay.take(k * t * 64), o_sc = lay.take(k * t * 32), o_sum = lay.take(k * 128),
+                 o_xis = lay.take(a.xis_out ? 0 : k * (lg + 1) * 32), o_cp = lay.take(a.hiding ? k * 64 : 0),
+                 o_bad = lay.take(a.hiding ? k : 0);
+    HALO_CHECK(st->scratch[7].reserve(lay.total()));
     HALO_CHECK(st->lincomb_terms.reserve(k * t * 129));  // both linear combinations, before anything is in flight
     uint8_t* base = st->scratch[7].as<uint8_t>();
     uint4 *pts = (uint4*)(base + o_pts), *sc = (uint4*)(base + o_sc), *sum = (uint4*)(base + o_sum);
@@ -253,14 +249,11 @@ int fs_device(const char* call, DeviceState* st, const FsCall& a, hipStream_t s)
         {
             ProfScope prof("pcdl_alpha", s);
             DISPATCH_CURVE(a.curve, Cv, {
-                if (lanes == 1)
-                    HALO_LAUNCH(prof, (k_pcdl_alpha<Cv, 1>), dim3(g.blocks), dim3(g.threads), 0, s, params,
+                DISPATCH_LANES(lanes, L, {
+                    HALO_LAUNCH(prof, (k_pcdl_alpha<Cv, L>), dim3(g.blocks), dim3(g.threads), 0, s, params,
                                 (const uint8_t*)a.hiding, (const uint4*)a.C, (const uint4*)a.C_bar, (const uint4*)a.z,
                                 (const uint4*)a.v, (const uint4*)a.w_prime, S_int, k, (uint4*)a.alpha_out, pts, sc, bad);
-                else
-                    HALO_LAUNCH(prof, (k_pcdl_alpha<Cv, 3>), dim3(g.blocks), dim3(g.threads), 0, s, params,
-                                (const uint8_t*)a.hiding, (const uint4*)a.C, (const uint4*)a.C_bar, (const uint4*)a.z,
-                                (const uint4*)a.v, (const uint4*)a.w_prime, S_int, k, (uint4*)a.alpha_out, pts, sc, bad);
+                });
             });
             HALO_HIP(hipGetLastError());
         }
@@ -278,14 +271,11 @@ int fs_device(const char* call, DeviceState* st, const FsCall& a, hipStream_t s)
     {
         ProfScope prof("pcdl_challenges", s);
         DISPATCH_CURVE(a.curve, Cv, {
-            if (lanes == 1)
-                HALO_LAUNCH(prof, (k_pcdl_challenges<Cv, 1>), dim3(g.blocks), dim3(g.threads), 0, s, params,
+            DISPATCH_LANES(lanes, L, {
+                HALO_LAUNCH(prof, (k_pcdl_challenges<Cv, L>), dim3(g.blocks), dim3(g.threads), 0, s, params,
                             (const uint8_t*)a.hiding, (const uint4*)a.C, (const uint4*)a.C_bar, Cp, (const uint4*)a.z,
                             (const uint4*)a.v, (const uint4*)a.Ls, (const uint4*)a.Rs, lg, k, xis);
-            else
-                HALO_LAUNCH(prof, (k_pcdl_challenges<Cv, 3>), dim3(g.blocks), dim3(g.threads), 0, s, params,
-                            (const uint8_t*)a.hiding, (const uint4*)a.C, (const uint4*)a.C_bar, Cp, (const uint4*)a.z,
-                            (const uint4*)a.v, (const uint4*)a.Ls, (const uint4*)a.Rs, lg, k, xis);
+            });
         });
         HALO_HIP(hipGetLastError());
     }
@@ -303,45 +293,27 @@ int fs_device(const char* call, DeviceState* st, const FsCall& a, hipStream_t s)
 
 // The host form's scalars: z, v, c and every w' that is read are below the modulus.
 int fs_host_scalars(const char* call, const FsCall& host) {
-    const uint64_t(&p)[4] = host.curve == HALO_PALLAS ? FpCfg::MODULUS64 : FqCfg::MODULUS64;  // the scalar field
-    auto below = [&](const halo_fe_t& x) {
-        for (int q = 3; q >= 0; q--)
-            if (x.l[q] != p[q]) return x.l[q] < p[q];
-        return false;
-    };
     const halo_fe_t *z = (const halo_fe_t*)host.z, *v = (const halo_fe_t*)host.v, *c = (const halo_fe_t*)host.c,
                     *w_prime = (const halo_fe_t*)host.w_prime;
     const uint8_t* hiding = (const uint8_t*)host.hiding;
     for (size_t i = 0; i < host.k; i++)
-        if (!below(z[i]) || !below(v[i]) || !below(c[i]) || (hiding && hiding[i] && !below(w_prime[i])))
+        if (!scalar_below(host.curve, z[i]) || !scalar_below(host.curve, v[i]) || !scalar_below(host.curve, c[i]) ||
+            (hiding && hiding[i] && !scalar_below(host.curve, w_prime[i])))
             return set_error(HALO_EINVAL, "%s: a scalar of instance %zu is not below the modulus", call, i);
     return HALO_OK;
 }
 
-// The inputs of a host call as one buffer (st->scratch[0]) on stream s; dev: the same call over device
-// pointers, its outputs null.
-int fs_upload(DeviceState* st, const FsCall& host, FsCall& dev, hipStream_t s) {
-    const size_t k = host.k, lg = ilog2(host.d + 1);
-    const bool hid = host.hiding != nullptr;
-    struct Part {
-        const void* src;
-        size_t bytes, off;
-    } in[10] = {{host.C, k * 64, 0},       {host.z, k * 32, 0},       {host.v, k * 32, 0},
-                {host.Ls, k * lg * 64, 0}, {host.Rs, k * lg * 64, 0}, {host.U, k * 64, 0},
-                {host.c, k * 32, 0},       {host.hiding, hid ? k : 0, 0}, {host.C_bar, hid ? k * 64 : 0, 0},
-                {host.w_prime, hid ? k * 32 : 0, 0}};
-    size_t n_in = 0;
-    for (Part& q : in) {
-        q.off = n_in;
-        n_in += align256(q.bytes);
-    }
-    HALO_CHECK(st->scratch[0].reserve(n_in));
-    uint8_t* di = st->scratch[0].as<uint8_t>();
-    for (const Part& q : in) HALO_CHECK(copy_h2d(di + q.off, q.src, q.bytes, s));
-    auto at = [&](int j) -> const void* { return in[j].bytes ? di + in[j].off : nullptr; };
-    dev = FsCall{host.curve, host.d, k, at(0), at(1), at(2), at(3), at(4), at(5), at(6), at(7), at(8), at(9),
-                 nullptr, nullptr, nullptr};
-    return HALO_OK;
+// The inputs of a host call as the rows of upload_parts, and the same call over the device pointers `at` that
+// upload_parts answers for them, its outputs null.
+HostParts fs_host_parts(const FsCall& host) {
+    const size_t k = host.k, lg = ilog2(host.d + 1), hid = host.hiding ? k : 0;
+    return HostParts{{host.C, k * 64},       {host.z, k * 32}, {host.v, k * 32}, {host.Ls, k * lg * 64},
+                     {host.Rs, k * lg * 64}, {host.U, k * 64}, {host.c, k * 32}, {host.hiding, hid},
+                     {host.C_bar, hid * 64}, {host.w_prime, hid * 32}};
+}
+FsCall fs_dev_call(const FsCall& host, const std::vector<const void*>& at) {
+    return FsCall{host.curve, host.d, host.k, at[0], at[1], at[2], at[3], at[4], at[5], at[6], at[7], at[8], at[9],
+                  nullptr, nullptr, nullptr};
 }
 
 }  // namespace halo
@@ -386,11 +358,12 @@ extern "C" int halo_pcdl_succinct_check_fs_batch(halo_curve_t curve, size_t d, s
     hipStream_t s = 0;
     ScratchUse su(st, s);
     const size_t lg = ilog2(d + 1);
-    FsCall a;
-    HALO_CHECK(fs_upload(st, host, a, s));
-    const size_t o_xis = 0, o_alpha = o_xis + align256(xis_out ? k * (lg + 1) * 32 : 0),
-                 o_ok = o_alpha + align256(alpha_out ? k * 32 : 0);
-    HALO_CHECK(st->scratch[1].reserve(o_ok + k));
+    std::vector<const void*> at;
+    HALO_CHECK(upload_parts(st, fs_host_parts(host), s, at));
+    FsCall a = fs_dev_call(host, at);
+    ScratchLayout out;
+    const size_t o_xis = out.take(xis_out ? k * (lg + 1) * 32 : 0), o_alpha = out.take(alpha_out ? k * 32 : 0), o_ok = out.total();
+    HALO_CHECK(st->scratch[1].reserve(o_ok + k));  // the last part is not padded
     uint8_t* dout = st->scratch[1].as<uint8_t>();
     a.xis_out = xis_out ? dout + o_xis : nullptr;
     a.alpha_out = alpha_out ? dout + o_alpha : nullptr;

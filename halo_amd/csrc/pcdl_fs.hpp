@@ -16,10 +16,11 @@ struct FsCall {  // the arguments of either entry point of halo_pcdl_succinct_ch
 int fs_device(const char* call, DeviceState* st, const FsCall& a, hipStream_t s);
 
 // What the host entry points share (halo_pcdl_check_fs_batch, decider.hip): the checks that need no device
-// (done: an empty batch), the scalars of a host call below the modulus, and the inputs of a host call as one
-// buffer in st->scratch[0] (dev: the call over device pointers, its outputs null).
+// (done: an empty batch), the scalars of a host call below the modulus (host_scalar.hpp), its inputs as the rows
+// of upload_parts, and the call over the device pointers `at` that upload_parts answers (its outputs null).
 int check_fs_args(const char* call, const FsCall& a, bool& done);
 int fs_host_scalars(const char* call, const FsCall& host);
-int fs_upload(DeviceState* st, const FsCall& host, FsCall& dev, hipStream_t s);
+HostParts fs_host_parts(const FsCall& host);
+FsCall fs_dev_call(const FsCall& host, const std::vector<const void*>& at);
 
 }  // namespace halo

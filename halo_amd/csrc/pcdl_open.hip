@@ -97,7 +97,7 @@ constexpr size_t COMBINE_MSM_MAX = (size_t)1 << 16;
 extern "C" int halo_pcdl_open_begin(halo_curve_t curve, const halo_fe_t* p, size_t len, size_t d, const halo_fe_t* z,
                                     halo_fe_t* v_out, halo_ipa_session** out) {
     clear_error();
-    if (curve != HALO_PALLAS && curve != HALO_VESTA) return set_error(HALO_EINVAL, "unknown curve");
+    if (!valid_curve(curve)) return set_error(HALO_EINVAL, "unknown curve");
     if ((len && !p) || !z || !out) return set_error(HALO_EINVAL, "halo_pcdl_open_begin: null argument");
     const size_t n = d + 1;
     if (n <= 1) return set_error(HALO_EINVAL, "assertion failed: n > 1");

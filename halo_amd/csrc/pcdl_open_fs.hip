@@ -119,8 +119,6 @@ __global__ __launch_bounds__(64) void k_open_fs_round(const uint32_t* __restrict
 
 namespace {
 
-#define OPEN_FS_PARAMS_MSG "%s: no Poseidon parameters for the curve's base field (halo_poseidon_set_params)"
-
 int launch_start(halo_ipa_session* ses, const uint32_t* params, int lanes, int mode, const halo_wrapped_point_t* p0,
                  const halo_wrapped_point_t* p1, const halo_fe_t* v) {
     OpenFsStart a{};
@@ -130,10 +128,9 @@ int launch_start(halo_ipa_session* ses, const uint32_t* params, int lanes, int m
     a.mode = mode;
     a.has_v = v != nullptr;
     DISPATCH_CURVE(ses->curve, Cv, {
-        if (lanes == 1)
-            hipLaunchKernelGGL((k_open_fs_start<Cv, 1>), dim3(1), dim3(64), 0, ses->s, params, ses->small.as<uint4>(), a);
-        else
-            hipLaunchKernelGGL((k_open_fs_start<Cv, 3>), dim3(1), dim3(64), 0, ses->s, params, ses->small.as<uint4>(), a);
+        DISPATCH_LANES(lanes, L, {
+            hipLaunchKernelGGL((k_open_fs_start<Cv, L>), dim3(1), dim3(64), 0, ses->s, params, ses->small.as<uint4>(), a);
+        });
     });
     HALO_HIP(hipGetLastError());
     return HALO_OK;
@@ -151,10 +148,9 @@ int enqueue_round(DeviceState* st, halo_ipa_session* ses, const uint32_t* params
     {
         ProfScope prof("open_fs_round", s);
         DISPATCH_CURVE(ses->curve, Cv, {
-            if (lanes == 1)
-                HALO_LAUNCH(prof, (k_open_fs_round<Cv, 1>), dim3(1), dim3(64), 0, s, params, (uint4*)sm, xi_prev, row);
-            else
-                HALO_LAUNCH(prof, (k_open_fs_round<Cv, 3>), dim3(1), dim3(64), 0, s, params, (uint4*)sm, xi_prev, row);
+            DISPATCH_LANES(lanes, L, {
+                HALO_LAUNCH(prof, (k_open_fs_round<Cv, L>), dim3(1), dim3(64), 0, s, params, (uint4*)sm, xi_prev, row);
+            });
         });
         HALO_HIP(hipGetLastError());
     }
@@ -203,7 +199,7 @@ int finish(const char* call, halo_ipa_session* ses, halo_wrapped_point_t* Ls, ha
 
 // what both entry points check before the device is touched
 int check_shape(const char* call, halo_curve_t curve, size_t d) {
-    if (curve != HALO_PALLAS && curve != HALO_VESTA) return set_error(HALO_EINVAL, "%s: unknown curve", call);
+    if (!valid_curve(curve)) return set_error(HALO_EINVAL, "%s: unknown curve", call);
     const size_t n = d + 1;
     if (n <= 1) return set_error(HALO_EINVAL, "%s: assertion failed: n > 1", call);
     if (!is_pow2(n)) return set_error(HALO_ENOTPOW2, "n (%zu) is not a power of two", n);
@@ -239,7 +235,7 @@ extern "C" int halo_pcdl_open_fs(halo_curve_t curve, const halo_fe_t* p, size_t 
     size_t deg_len = len;
     while (deg_len > 0 && !(p[deg_len - 1].l[0] | p[deg_len - 1].l[1] | p[deg_len - 1].l[2] | p[deg_len - 1].l[3])) deg_len--;
     if (deg_len > n) return set_error(HALO_EDEGREE, "assertion failed: p.degree() <= d");
-    if (!poseidon_params_set(base_field(curve))) return set_error(HALO_EINVAL, OPEN_FS_PARAMS_MSG, call);
+    HALO_CHECK(require_poseidon_params(call, curve));
     DeviceState* st = current_state();
     if (!st) return HALO_EDEVICE;
     halo_ipa_session* ses = nullptr;
@@ -289,7 +285,7 @@ extern "C" int halo_pcdl_open_fs_dev_multi(halo_curve_t curve, size_t k, const v
                                            halo_fe_t* v_out) {
     clear_error();
     const char* call = "halo_pcdl_open_fs_dev_multi";
-    if (curve != HALO_PALLAS && curve != HALO_VESTA) return set_error(HALO_EINVAL, "%s: unknown curve", call);
+    if (!valid_curve(curve)) return set_error(HALO_EINVAL, "%s: unknown curve", call);
     if (k == 0) return HALO_OK;
     if (!d_p || !lens || !z || !C || !Ls || !Rs || !U || !c) return set_error(HALO_EINVAL, "%s: null argument", call);
     HALO_CHECK(check_shape(call, curve, d));
@@ -299,7 +295,7 @@ extern "C" int halo_pcdl_open_fs_dev_multi(halo_curve_t curve, size_t k, const v
         // (the coefficients are on the device: the length stands for the degree)
         if (lens[i] > n) return set_error(HALO_EDEGREE, "assertion failed: p.degree() <= d");
     }
-    if (!poseidon_params_set(base_field(curve))) return set_error(HALO_EINVAL, OPEN_FS_PARAMS_MSG, call);
+    HALO_CHECK(require_poseidon_params(call, curve));
     DeviceState* st = current_state();
     if (!st) return HALO_EDEVICE;
     std::lock_guard<std::mutex> g(st->mu);

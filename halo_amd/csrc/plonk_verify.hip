@@ -30,10 +30,12 @@
 //   (decide_device)     the deciders of the proofs whose verdict is still ACCEPT; k_plonk_decided folds them in
 //
 // As in pcdl_fs.hip no sponge state passes between kernels, and lanes past the batch repeat its last
-// proof because they take part in the shuffles.
+// proof because they take part in the shuffles.  Host side: one ScratchLayout, one HostParts table
+// (scratch_layout.hpp), scalar_below / check_rho (host_scalar.hpp), DISPATCH_LANES (sponge_launch.hpp).
 #include "curve.hpp"
 #include "decider.hpp"
 #include "dispatch.hpp"
+#include "host_scalar.hpp"
 #include "lincomb.hpp"
 #include "outer_sponge.hpp"
 #include "pcdl_fs.hpp"
@@ -575,12 +577,10 @@ struct PlonkDecide {
     void *decided, *combined;
 };
 
-static size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 // Everything that needs no device; done: an empty batch.
 static int check_plonk_args(const char* call, const PlonkCall& a, bool& done) {
     done = false;
-    if (a.curve != HALO_PALLAS && a.curve != HALO_VESTA) return set_error(HALO_EINVAL, "%s: unknown curve", call);
+    if (!valid_curve(a.curve)) return set_error(HALO_EINVAL, "%s: unknown curve", call);
     if (a.k == 0) {
         done = true;
         return HALO_OK;
@@ -594,18 +594,7 @@ static int check_plonk_args(const char* call, const PlonkCall& a, bool& done) {
     const size_t lg = ilog2(a.rows), ipp = a.full ? 4 : 3;
     if (a.k > LINCOMB_MAX_ITEMS / (ipp * (2 * lg + 2)) || a.k > LINCOMB_MAX_ITEMS / R_TERMS || a.npi > (SIZE_MAX / 64) / a.k)
         return set_error(HALO_EINVAL, "%s: %zu proofs in one call", call, a.k);
-    if (!poseidon_params_set(base_field(a.curve)))
-        return set_error(HALO_EINVAL, "%s: no Poseidon parameters for the curve's base field (halo_poseidon_set_params)",
-                         call);
-    return HALO_OK;
-}
-
-// The resident SRS covers the circuit's degree bound and has (S, H).  st->mu held.
-static int check_plonk_srs(const char* call, const DeviceState* st, const PlonkCall& a) {
-    const SrsState& srs = st->srs[a.curve];
-    if (!srs.n || a.rows - 1 > srs.n - 1) return set_error(HALO_ESRSRANGE, "d was larger than D!");
-    if (!srs.has_sh) return set_error(HALO_ESRSRANGE, "%s: no (S, H) uploaded", call);
-    return HALO_OK;
+    return require_poseidon_params(call, a.curve);
 }
 
 // acc::decider of the proofs that are still accepted (rho null: exact mode), then their verdicts.  resolve: the
@@ -621,7 +610,7 @@ static int plonk_decide(DeviceState* st, const PlonkCall& a, const PlonkDecide& 
 }
 
 // The launches of one call over device pointers, all on `s`.  st->mu and a ScratchUse of `s` held; a.k >= 1,
-// check_plonk_srs passed.  ipp = 3 instances per proof (verify_succinct), or 4 with acc_next (a.full), whose PCDL
+// check_verifier_srs passed.  ipp = 3 instances per proof (verify_succinct), or 4 with acc_next (a.full), whose PCDL
 // transcript then runs inside the same fs_device chain and whose decider follows (resolve: see plonk_decide).
 static int plonk_device(const char* call, DeviceState* st, const PlonkCall& a, hipStream_t s, bool resolve = false) {
     const size_t k = a.k, lg = ilog2(a.rows), d = a.rows - 1, m = a.npi ? a.npi : 1, ipp = a.full ? 4 : 3;
@@ -629,22 +618,19 @@ static int plonk_device(const char* call, DeviceState* st, const PlonkCall& a, h
     const uint32_t* params;
     HALO_CHECK(poseidon_device_params(st, base_field(a.curve), &params));
     // one scratch buffer; the succinct checks work in scratch[7]
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off += align256(bytes);
-        return o;
-    };
-    const size_t o_rp = take(k * R_TERMS * 64), o_rs = take(k * R_TERMS * 32), o_op = take(k * RO_TERMS * 64),
-                 o_os = take(k * RO_TERMS * 32), o_sr = take(k * 128), o_so = take(k * 128), o_ic = take(ipp * k * 64),
-                 o_iz = take(ipp * k * 32), o_iv = take(ipp * k * 32), o_xis = take(ipp * k * (lg + 1) * 32),
-                 o_den = take(k * m * 32), o_ap = take(3 * k * 64), o_as = take(3 * k * 32), o_neg = take(k * 64),
-                 o_sum = take(k * 128), o_chal = take(a.chal_out ? 0 : k * 5 * 32),
-                 o_sides = take(a.sides_out ? 0 : k * 2 * 32), o_asdl = take(a.asdl_out ? 0 : k * 2 * 32), o_mal = take(k),
-                 o_bits = take(k), o_ok3 = take(ipp * k), o_cid = take(k), o_l4 = take(4 * nx * lg * 64),
-                 o_r4 = take(4 * nx * lg * 64), o_u4 = take(4 * nx * 64), o_c4 = take(4 * nx * 32),
-                 o_nxis = take(nx * (lg + 1) * 32), o_xis3 = take(3 * nx * (lg + 1) * 32), o_live = take(nx), o_dec = take(nx), o_comb = take(a.full ? 1 : 0);
-    HALO_CHECK(st->scratch[6].reserve(off));
+    ScratchLayout sl;
+    const size_t o_rp = sl.take(k * R_TERMS * 64), o_rs = sl.take(k * R_TERMS * 32), o_op = sl.take(k * RO_TERMS * 64),
+                 o_os = sl.take(k * RO_TERMS * 32), o_sr = sl.take(k * 128), o_so = sl.take(k * 128),
+                 o_ic = sl.take(ipp * k * 64), o_iz = sl.take(ipp * k * 32), o_iv = sl.take(ipp * k * 32),
+                 o_xis = sl.take(ipp * k * (lg + 1) * 32), o_den = sl.take(k * m * 32), o_ap = sl.take(3 * k * 64),
+                 o_as = sl.take(3 * k * 32), o_neg = sl.take(k * 64), o_sum = sl.take(k * 128),
+                 o_chal = sl.take(a.chal_out ? 0 : k * 5 * 32), o_sides = sl.take(a.sides_out ? 0 : k * 2 * 32),
+                 o_asdl = sl.take(a.asdl_out ? 0 : k * 2 * 32), o_mal = sl.take(k), o_bits = sl.take(k),
+                 o_ok3 = sl.take(ipp * k), o_cid = sl.take(k), o_l4 = sl.take(4 * nx * lg * 64),
+                 o_r4 = sl.take(4 * nx * lg * 64), o_u4 = sl.take(4 * nx * 64), o_c4 = sl.take(4 * nx * 32),
+                 o_nxis = sl.take(nx * (lg + 1) * 32), o_xis3 = sl.take(3 * nx * (lg + 1) * 32), o_live = sl.take(nx),
+                 o_dec = sl.take(nx), o_comb = sl.take(a.full ? 1 : 0);
+    HALO_CHECK(st->scratch[6].reserve(sl.total()));
     // every linear combination of the chain, before anything is in flight
     HALO_CHECK(st->lincomb_terms.reserve(k * std::max<size_t>(R_TERMS, ipp * (2 * lg + 2)) * 129));
     uint8_t* base = st->scratch[6].as<uint8_t>();
@@ -671,12 +657,10 @@ static int plonk_device(const char* call, DeviceState* st, const PlonkCall& a, h
     {
         ProfScope prof("plonk_challenges", s);
         DISPATCH_CURVE(a.curve, Cv, {
-            if (lanes == 1)
-                HALO_LAUNCH(prof, (k_plonk_challenges<Cv, 1>), dim3(g.blocks), dim3(g.threads), 0, s, params, cp(a.C_ws),
+            DISPATCH_LANES(lanes, L, {
+                HALO_LAUNCH(prof, (k_plonk_challenges<Cv, L>), dim3(g.blocks), dim3(g.threads), 0, s, params, cp(a.C_ws),
                             cp(a.C_z), cp(a.C_ts), k, chal);
-            else
-                HALO_LAUNCH(prof, (k_plonk_challenges<Cv, 3>), dim3(g.blocks), dim3(g.threads), 0, s, params, cp(a.C_ws),
-                            cp(a.C_z), cp(a.C_ts), k, chal);
+            });
         });
         HALO_HIP(hipGetLastError());
     }
@@ -718,12 +702,10 @@ static int plonk_device(const char* call, DeviceState* st, const PlonkCall& a, h
     {
         ProfScope prof("asdl_challenges", s);
         DISPATCH_CURVE(a.curve, Cv, {
-            if (lanes == 1)
-                HALO_LAUNCH(prof, (k_asdl_challenges<Cv, 1>), dim3(g.blocks), dim3(g.threads), 0, s, params, xis3,
-                            cp(a.U), lg, k, asdl);
-            else
-                HALO_LAUNCH(prof, (k_asdl_challenges<Cv, 3>), dim3(g.blocks), dim3(g.threads), 0, s, params, xis3,
-                            cp(a.U), lg, k, asdl);
+            DISPATCH_LANES(lanes, L, {
+                HALO_LAUNCH(prof, (k_asdl_challenges<Cv, L>), dim3(g.blocks), dim3(g.threads), 0, s, params, xis3, cp(a.U),
+                            lg, k, asdl);
+            });
         });
         HALO_HIP(hipGetLastError());
     }
@@ -744,20 +726,6 @@ static int plonk_device(const char* call, DeviceState* st, const PlonkCall& a, h
     return plonk_decide(st, a, dec, a.rho, resolve, s);
 }
 
-static bool fe_all_below(int curve, const halo_fe_t* x, size_t n) {
-    const uint64_t(&p)[4] = curve == HALO_PALLAS ? FpCfg::MODULUS64 : FqCfg::MODULUS64;  // the scalar field
-    for (size_t j = 0; j < n; j++) {
-        bool below = false;
-        for (int q = 3; q >= 0; q--)
-            if (x[j].l[q] != p[q]) {
-                below = x[j].l[q] < p[q];
-                break;
-            }
-        if (!below) return false;
-    }
-    return true;
-}
-
 // Either host entry point: the scalar checks, one buffer of inputs and one of outputs and the chain; in a full
 // call a rejected combined batch of deciders is resolved to per-proof verdicts.
 static int plonk_host(const char* call, const PlonkCall& host) {
@@ -765,56 +733,42 @@ static int plonk_host(const char* call, const PlonkCall& host) {
     HALO_CHECK(check_plonk_args(call, host, done));
     if (done) return HALO_OK;
     const size_t k = host.k, npi = host.npi, lg = ilog2(host.rows);
-    auto fes = [](const void* p) { return (const halo_fe_t*)p; };
-    if (!fe_all_below(host.curve, fes(host.mds), 9)) return set_error(HALO_EINVAL, "%s: an MDS entry is not below the modulus", call);
+    auto below = [&](const void* p, size_t first, size_t n) { return scalar_below(host.curve, (const halo_fe_t*)p + first, n); };
+    if (!below(host.mds, 0, 9)) return set_error(HALO_EINVAL, "%s: an MDS entry is not below the modulus", call);
     for (size_t i = 0; i < k; i++)
-        if (!fe_all_below(host.curve, fes(host.vs) + N_VS * i, N_VS) || !fe_all_below(host.curve, fes(host.pub) + npi * i, npi) ||
-            !fe_all_below(host.curve, fes(host.c) + 3 * i, 3) || !fe_all_below(host.curve, fes(host.prev_z) + i, 1) ||
-            !fe_all_below(host.curve, fes(host.prev_v) + i, 1) || !fe_all_below(host.curve, fes(host.next_z) + i, 1) ||
-            !fe_all_below(host.curve, fes(host.next_v) + i, 1) || (host.full && !fe_all_below(host.curve, fes(host.next_c) + i, 1)))
+        if (!below(host.vs, N_VS * i, N_VS) || !below(host.pub, npi * i, npi) || !below(host.c, 3 * i, 3) ||
+            !below(host.prev_z, i, 1) || !below(host.prev_v, i, 1) || !below(host.next_z, i, 1) || !below(host.next_v, i, 1) ||
+            (host.full && !below(host.next_c, i, 1)))
             return set_error(HALO_EINVAL, "%s: a scalar of proof %zu is not below the modulus", call, i);
-    for (size_t i = 0; host.rho && i < k; i++) {
-        const halo_fe_t& r = fes(host.rho)[i];
-        if (!(r.l[0] | r.l[1] | r.l[2] | r.l[3])) return set_error(HALO_EINVAL, "%s: rho[%zu] is zero", call, i);
-        if (!fe_all_below(host.curve, &r, 1)) return set_error(HALO_EINVAL, "%s: rho[%zu] is not below the modulus", call, i);
-    }
+    HALO_CHECK(check_rho(call, host.curve, (const halo_fe_t*)host.rho, k));
     DeviceState* st = current_state();
     if (!st) return HALO_EDEVICE;
     std::lock_guard<std::mutex> g(st->mu);
-    HALO_CHECK(check_plonk_srs(call, st, host));
+    HALO_CHECK(check_verifier_srs(call, st, host.curve, host.rows - 1, true));
     hipStream_t s = 0;
     ScratchUse su(st, s);
     const size_t nx = host.full ? k : 0;
-    struct Part {
-        const void* src;
-        size_t bytes, off;
-    } in[22] = {{host.C_qs, N_Q * 64, 0},     {host.pub, k * npi * 32, 0},   {host.C_ws, k * N_W * 64, 0},
-                {host.C_z, k * 64, 0},        {host.C_ts, k * N_T * 64, 0},  {host.vs, k * N_VS * 32, 0},
-                {host.Ls, k * 3 * lg * 64, 0}, {host.Rs, k * 3 * lg * 64, 0}, {host.U, k * 3 * 64, 0},
-                {host.c, k * 3 * 32, 0},      {host.prev_C, k * 64, 0},      {host.prev_z, k * 32, 0},
-                {host.prev_v, k * 32, 0},     {host.next_C, k * 64, 0},      {host.next_z, k * 32, 0},
-                {host.next_v, k * 32, 0},     {host.mds, 9 * 32, 0},         {host.next_Ls, nx * lg * 64, 0},
-                {host.next_Rs, nx * lg * 64, 0}, {host.next_U, nx * 64, 0},  {host.next_c, nx * 32, 0},
-                {host.rho, host.rho ? nx * 32 : 0, 0}};
-    size_t n_in = 0;
-    for (Part& q : in) {
-        q.off = n_in;
-        n_in += align256(q.bytes);
-    }
-    const size_t o_chal = 0, o_sides = o_chal + align256(host.chal_out ? k * 5 * 32 : 0),
-                 o_asdl = o_sides + align256(host.sides_out ? k * 2 * 32 : 0),
-                 o_v = o_asdl + align256(host.asdl_out ? k * 2 * 32 : 0);
-    HALO_CHECK(st->scratch[0].reserve(n_in));
-    HALO_CHECK(st->scratch[1].reserve(o_v + k));
-    uint8_t *di = st->scratch[0].as<uint8_t>(), *dout = st->scratch[1].as<uint8_t>();
-    for (const Part& q : in) HALO_CHECK(copy_h2d(di + q.off, q.src, q.bytes, s));
-    auto dev = [&](int j) -> const void* { return in[j].bytes ? di + in[j].off : nullptr; };
-    PlonkCall a{host.curve, host.rows, k,       npi,     dev(0),  dev(1),  dev(2),  dev(3),  dev(4),
-                dev(5),     dev(6),    dev(7),  dev(8),  dev(9),  dev(10), dev(11), dev(12), dev(13),
-                dev(14),    dev(15),   dev(16), dout + o_v, host.chal_out ? dout + o_chal : nullptr,
+    const HostParts in{{host.C_qs, N_Q * 64},        {host.pub, k * npi * 32},   {host.C_ws, k * N_W * 64},
+                       {host.C_z, k * 64},           {host.C_ts, k * N_T * 64},  {host.vs, k * N_VS * 32},
+                       {host.Ls, k * 3 * lg * 64},   {host.Rs, k * 3 * lg * 64}, {host.U, k * 3 * 64},
+                       {host.c, k * 3 * 32},         {host.prev_C, k * 64},      {host.prev_z, k * 32},
+                       {host.prev_v, k * 32},        {host.next_C, k * 64},      {host.next_z, k * 32},
+                       {host.next_v, k * 32},        {host.mds, 9 * 32},         {host.next_Ls, nx * lg * 64},
+                       {host.next_Rs, nx * lg * 64}, {host.next_U, nx * 64},     {host.next_c, nx * 32},
+                       {host.rho, host.rho ? nx * 32 : 0}};
+    ScratchLayout out;
+    const size_t o_chal = out.take(host.chal_out ? k * 5 * 32 : 0), o_sides = out.take(host.sides_out ? k * 2 * 32 : 0),
+                 o_asdl = out.take(host.asdl_out ? k * 2 * 32 : 0), o_v = out.total();
+    HALO_CHECK(st->scratch[1].reserve(o_v + k));  // the last part is not padded
+    std::vector<const void*> dev;
+    HALO_CHECK(upload_parts(st, in, s, dev));
+    uint8_t* dout = st->scratch[1].as<uint8_t>();
+    PlonkCall a{host.curve, host.rows, k,       npi,     dev[0],  dev[1],  dev[2],  dev[3],  dev[4],
+                dev[5],     dev[6],    dev[7],  dev[8],  dev[9],  dev[10], dev[11], dev[12], dev[13],
+                dev[14],    dev[15],   dev[16], dout + o_v, host.chal_out ? dout + o_chal : nullptr,
                 host.sides_out ? dout + o_sides : nullptr, host.asdl_out ? dout + o_asdl : nullptr};
     a.full = host.full;
-    a.next_Ls = dev(17), a.next_Rs = dev(18), a.next_U = dev(19), a.next_c = dev(20), a.rho = dev(21);
+    a.next_Ls = dev[17], a.next_Rs = dev[18], a.next_U = dev[19], a.next_c = dev[20], a.rho = dev[21];
     HALO_CHECK(plonk_device(call, st, a, s, true));
     if (host.chal_out) HALO_CHECK(copy_d2h(host.chal_out, dout + o_chal, k * 5 * 32, s));
     if (host.sides_out) HALO_CHECK(copy_d2h(host.sides_out, dout + o_sides, k * 2 * 32, s));
@@ -829,7 +783,7 @@ static int plonk_dev(const char* call, const PlonkCall& a, void* stream) {
     DeviceState* st = current_state();
     if (!st) return HALO_EDEVICE;
     std::lock_guard<std::mutex> g(st->mu);
-    HALO_CHECK(check_plonk_srs(call, st, a));
+    HALO_CHECK(check_verifier_srs(call, st, a.curve, a.rows - 1, true));
     hipStream_t s = (hipStream_t)stream;
     ScratchUse su(st, s);
     return plonk_device(call, st, a, s);

@@ -76,12 +76,12 @@ __global__ __launch_bounds__(256) void k_point_sum_xyzz(const uint4* pts, size_t
 // host orchestration
 // ---------------------------------------------------------------------------------------------
 int check_curve(halo_curve_t c) {
-    if (c != HALO_PALLAS && c != HALO_VESTA) return set_error(HALO_EINVAL, "unknown curve id %d", (int)c);
+    if (!valid_curve(c)) return set_error(HALO_EINVAL, "unknown curve id %d", (int)c);
     return HALO_OK;
 }
 
 int check_field(halo_field_t f) {
-    if (f != HALO_FP && f != HALO_FQ) return set_error(HALO_EINVAL, "unknown field id %d", (int)f);
+    if (!valid_field(f)) return set_error(HALO_EINVAL, "unknown field id %d", (int)f);
     return HALO_OK;
 }
 

@@ -565,7 +565,7 @@ extern "C" int halo_hpoly_coeffs(halo_field_t field, const halo_fe_t* xis, size_
 extern "C" int halo_pcdl_decider_commit(halo_curve_t curve, const halo_fe_t* xis, size_t n_xis, size_t d,
                                         halo_wrapped_point_t* out) {
     clear_error();
-    if (curve != HALO_PALLAS && curve != HALO_VESTA) return set_error(HALO_EINVAL, "unknown curve id %d", (int)curve);
+    if (!valid_curve(curve)) return set_error(HALO_EINVAL, "unknown curve id %d", (int)curve);
     if (n_xis < 1 || n_xis > 29) return set_error(HALO_EINVAL, "halo_pcdl_decider_commit: n_xis %zu out of range", n_xis);
     if (!xis || !out) return set_error(HALO_EINVAL, "halo_pcdl_decider_commit: null buffer");
     DeviceState* st = current_state();
@@ -626,7 +626,7 @@ __global__ __launch_bounds__(256) void k_row_lengths(const uint4* a, size_t n, u
 extern "C" int halo_trace_commit_batch(halo_curve_t curve, const halo_fe_t* evals, size_t k, unsigned log_n, size_t d,
                                        halo_fe_t* coeffs_out, size_t* lens_out, halo_wrapped_point_t* commits_out) {
     clear_error();
-    if (curve != HALO_PALLAS && curve != HALO_VESTA) return set_error(HALO_EINVAL, "unknown curve id %d", (int)curve);
+    if (!valid_curve(curve)) return set_error(HALO_EINVAL, "unknown curve id %d", (int)curve);
     if (!k) return HALO_OK;
     if (!evals || !commits_out) return set_error(HALO_EINVAL, "halo_trace_commit_batch: null buffer");
     if (log_n > 28) return set_error(HALO_EINVAL, "log_n %u too large", log_n);

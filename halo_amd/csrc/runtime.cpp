@@ -96,6 +96,25 @@ int copy_d2h(void* dst, const void* src, size_t bytes, hipStream_t s) {
     return HALO_OK;
 }
 
+int upload_parts(DeviceState* st, const HostParts& parts, hipStream_t s, std::vector<const void*>& dev) {
+    HALO_CHECK(st->scratch[0].reserve(parts.total()));
+    uint8_t* base = st->scratch[0].as<uint8_t>();
+    dev.assign(parts.rows.size(), nullptr);
+    for (size_t j = 0; j < parts.rows.size(); j++) {
+        if (parts.at(j) == HostParts::ABSENT) continue;
+        dev[j] = base + parts.at(j);
+        HALO_CHECK(copy_h2d(base + parts.at(j), parts.rows[j].src, parts.rows[j].bytes, s));
+    }
+    return HALO_OK;
+}
+
+int check_verifier_srs(const char* call, const DeviceState* st, int curve, size_t d, bool need_sh) {
+    const SrsState& srs = st->srs[curve];
+    if (!srs.n || d > srs.n - 1) return set_error(HALO_ESRSRANGE, "d was larger than D!");
+    if (need_sh && !srs.has_sh) return set_error(HALO_ESRSRANGE, "%s: no (S, H) uploaded", call);
+    return HALO_OK;
+}
+
 // ---- profiling ------------------------------------------------------------------------------
 struct ProfEntry {
     std::string name;

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/halo_gpu.h"
+#include "scratch_layout.hpp"
 
 namespace halo {
 
@@ -153,6 +154,16 @@ DeviceState* current_state();
 // Pinned staging helpers
 int copy_h2d(void* dst, const void* src, size_t bytes, hipStream_t s);
 int copy_d2h(void* dst, const void* src, size_t bytes, hipStream_t s);
+// The arrays of a host call (scratch_layout.hpp) as one buffer, st->scratch[0], copied on `s`; dev[j]: row j on
+// the device, null for a row of no bytes.  st->mu and a ScratchUse of `s` held.
+int upload_parts(DeviceState* st, const HostParts& parts, hipStream_t s, std::vector<const void*>& dev);
+
+// Preconditions the entry points share (each keeps its own message for a bad id).
+inline bool valid_curve(int c) { return c == HALO_PALLAS || c == HALO_VESTA; }
+inline bool valid_field(int f) { return f == HALO_FP || f == HALO_FQ; }
+// The resident SRS of `curve` covers the degree bound d and, where the call needs them, has (S, H).  st->mu held.
+// `call` names the entry point in the (S, H) message only: it may be null when need_sh is false, never otherwise.
+int check_verifier_srs(const char* call, const DeviceState* st, int curve, size_t d, bool need_sh);
 
 // ---- measurement hooks (halo_profile_*) ----------------------------------------------------
 // ProfScope owns a start/stop hipEvent pair for one launch when profiling is enabled; the launch

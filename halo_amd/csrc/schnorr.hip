@@ -11,6 +11,7 @@
 #include "curve.hpp"
 #include "dispatch.hpp"
 #include "glv.hpp"
+#include "host_scalar.hpp"
 #include "poseidon.hpp"
 #include "quad_ladder.hpp"
 #include "runtime.hpp"
@@ -218,31 +219,12 @@ struct PoseidonParams {
 static PoseidonParams g_poseidon;
 static uint64_t g_poseidon_next = 1;
 
-static bool valid_field(int f) { return f == HALO_FP || f == HALO_FQ; }
-static bool valid_curve(int c) { return c == HALO_PALLAS || c == HALO_VESTA; }
-
 // ark Montgomery limbs (a 2^256 mod p, canonical) -> the kernels' form (a 2^261 mod p as nine 29-bit
-// limbs): five modular doublings on the host.  False when the input is not below p.
-static bool ark_to_limbs(const uint64_t (&p)[4], const halo_fe_t& in, uint32_t* out) {
+// limbs): five modular doublings on the host.  False when the input is not below the modulus of M.
+static bool ark_to_limbs(const HostMont& M, const halo_fe_t& in, uint32_t* out) {
+    if (M.geq_p(in.l)) return false;
     uint64_t x[4] = {in.l[0], in.l[1], in.l[2], in.l[3]};
-    auto geq = [&](const uint64_t* a) {
-        for (int i = 3; i >= 0; i--)
-            if (a[i] != p[i]) return a[i] > p[i];
-        return true;
-    };
-    if (geq(x)) return false;
-    for (int d = 0; d < 5; d++) {
-        for (int i = 3; i > 0; i--) x[i] = (x[i] << 1) | (x[i - 1] >> 63);  // p < 2^255: no bit is lost
-        x[0] <<= 1;
-        if (geq(x)) {
-            uint64_t borrow = 0;
-            for (int i = 0; i < 4; i++) {
-                const uint64_t t = x[i] - p[i] - borrow;
-                borrow = (x[i] < p[i] + borrow) || (borrow && p[i] == ~0ull);
-                x[i] = t;
-            }
-        }
-    }
+    for (int d = 0; d < 5; d++) M.dbl(x);
     for (int i = 0; i < NLIMB; i++) {
         const int bit = i * LIMB_BITS, j = bit >> 6, sh = bit & 63;
         uint64_t v = x[j] >> sh;
@@ -291,12 +273,10 @@ static int poseidon_hash_device(DeviceState* st, int field, const void* d_in, si
     const int lanes = poseidon_lanes(st, k);
     const HashGrid g = hash_grid(k, lanes);
     DISPATCH_FIELD(field, F, {
-        if (lanes == 1)
-            hipLaunchKernelGGL((k_poseidon_hash<F, 1>), dim3(g.blocks), dim3(g.threads), 0, s, params, (const uint4*)d_in, len,
+        DISPATCH_LANES(lanes, L, {
+            hipLaunchKernelGGL((k_poseidon_hash<F, L>), dim3(g.blocks), dim3(g.threads), 0, s, params, (const uint4*)d_in, len,
                                k, (uint4*)d_out);
-        else
-            hipLaunchKernelGGL((k_poseidon_hash<F, 3>), dim3(g.blocks), dim3(g.threads), 0, s, params, (const uint4*)d_in, len,
-                               k, (uint4*)d_out);
+        });
     });
     HALO_HIP(hipGetLastError());
     return HALO_OK;
@@ -309,12 +289,10 @@ static int schnorr_hash_device(DeviceState* st, int curve, const void* d_pk, con
     const int lanes = poseidon_lanes(st, k);
     const HashGrid g = hash_grid(k, lanes);
     DISPATCH_CURVE(curve, Cv, {
-        if (lanes == 1)
-            hipLaunchKernelGGL((k_schnorr_hash<Cv, 1>), dim3(g.blocks), dim3(g.threads), 0, s, params, (const uint4*)d_pk,
+        DISPATCH_LANES(lanes, L, {
+            hipLaunchKernelGGL((k_schnorr_hash<Cv, L>), dim3(g.blocks), dim3(g.threads), 0, s, params, (const uint4*)d_pk,
                                (const uint4*)d_R, (const uint4*)d_msgs, msg_len, k, (uint4*)d_e_ark, (uint4*)d_e_words);
-        else
-            hipLaunchKernelGGL((k_schnorr_hash<Cv, 3>), dim3(g.blocks), dim3(g.threads), 0, s, params, (const uint4*)d_pk,
-                               (const uint4*)d_R, (const uint4*)d_msgs, msg_len, k, (uint4*)d_e_ark, (uint4*)d_e_words);
+        });
     });
     HALO_HIP(hipGetLastError());
     return HALO_OK;
@@ -356,10 +334,10 @@ extern "C" int halo_poseidon_set_params(halo_field_t field, const halo_fe_t* mds
     if (!valid_field(field) || !mds || !rc) return set_error(HALO_EINVAL, "halo_poseidon_set_params: invalid argument");
     static uint32_t tmp[poseidon::TABLE_WORDS];
     std::lock_guard<std::mutex> g(g_poseidon.mu);
-    const uint64_t(&p)[4] = field == HALO_FP ? FpCfg::MODULUS64 : FqCfg::MODULUS64;
+    const HostMont& M = scalar_mont(field == HALO_FP ? HALO_PALLAS : HALO_VESTA);  // Fp is Pallas's scalar field
     for (int i = 0; i < poseidon::N_CONST; i++) {
         const halo_fe_t& x = i < 9 ? mds[i] : rc[i - 9];
-        if (!ark_to_limbs(p, x, tmp + i * NLIMB))
+        if (!ark_to_limbs(M, x, tmp + i * NLIMB))
             return set_error(HALO_EINVAL, "halo_poseidon_set_params: constant %d is not a canonical field element", i);
     }
     memcpy(g_poseidon.tab[field], tmp, sizeof(tmp));
@@ -421,10 +399,7 @@ static int check_schnorr_args(const char* call, halo_curve_t curve, const void* 
     }
     if (!pk || !R || (need_s && !s) || !out || (msg_len && !msgs)) return set_error(HALO_EINVAL, "%s: null pointer", call);
     if (msg_len > (SIZE_MAX / 32) / k) return set_error(HALO_EINVAL, "%s: msg_len * k overflows", call);
-    if (!poseidon_params_set(base_field(curve)))
-        return set_error(HALO_EINVAL, "%s: no Poseidon parameters for the curve's base field (halo_poseidon_set_params)",
-                         call);
-    return HALO_OK;
+    return require_poseidon_params(call, curve);
 }
 
 extern "C" int halo_schnorr_hash_batch(halo_curve_t curve, const halo_wrapped_point_t* pk, const halo_wrapped_point_t* R,

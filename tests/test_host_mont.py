@@ -67,12 +67,16 @@ def dump(tmp_path_factory):
     subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", "-I", os.path.join(ROOT, "halo_amd", "csrc"),
                     os.path.join(ROOT, "tests", "host_mont_dump.cpp"), "-o", exe], check=True)
 
-    def run(lines):
+    def raw(lines):
         out = subprocess.run([exe], input="".join(lines), capture_output=True, text=True, check=True)
-        got = [[int(x, 16) for x in l.split()] for l in out.stdout.splitlines()]
+        got = out.stdout.splitlines()
         assert len(got) == len(lines)
         return got
 
+    def run(lines):
+        return [[int(x, 16) for x in l.split()] for l in raw(lines)]
+
+    run.raw = raw
     return run
 
 
@@ -149,3 +153,56 @@ def test_scalar_inverse(dump, f):
     for a, g in zip(ins, got):
         # a = x R: the output is x^-1 R = a^-1 R^2 mod p
         assert g == [1] + words(pow(a, -1, p) * R * R % p), hex(a)
+
+
+# ---- host_scalar.hpp: the one below-the-modulus predicate, check_rho and HostScalar ------------------
+HALO_OK, HALO_EINVAL = 0, 1
+
+
+def edge_values(p):
+    """Where a limb-wise comparison with p can go wrong: the ends of the range, p and its neighbours, the
+    values that equal p in three limbs and differ by one in the lowest (p - 1, p + 1) or in the top one."""
+    top = 1 << 192
+    return [0, 1, p - 1, p, p + 1, (1 << 255) - 1, R - 1, p - top, p + top, p - top + 1, p + top - 1]
+
+
+@pytest.mark.parametrize("f", sorted(FIELDS))
+def test_scalar_below(dump, f):
+    p = FIELDS[f]
+    vals = edge_values(p)
+    got = dump(["below %s 1 %064x\n" % (f, a) for a in vals])
+    for a, g in zip(vals, got):
+        assert g == [int(a < p), int(a < p)], hex(a)
+    # the span form: all of the values, none of them (true), and the ones below p only
+    low = [a for a in vals if a < p]
+    span = lambda xs: "below %s %d %s\n" % (f, len(xs), " ".join("%064x" % a for a in xs))
+    got = dump([span(vals), span([]), span(low), span(low + [p]), span([p] + low)])
+    assert got[0] == [sum(int(a < p) << i for i, a in enumerate(vals)), 0]
+    assert got[1] == [0, 1]
+    assert got[2] == [(1 << len(low)) - 1, 1]
+    assert got[3][1] == 0 and got[4][1] == 0
+
+
+@pytest.mark.parametrize("f", sorted(FIELDS))
+def test_check_rho(dump, f):
+    p = FIELDS[f]
+    rho = lambda xs: "rho %s %d %s\n" % (f, len(xs), " ".join("%064x" % a for a in xs))
+    got = dump.raw([rho([1, p - 1, 5]), "rho %s -1\n" % f, rho([]), rho([1, 0, p]), rho([p - 1, 2, p]), rho([R - 1]),
+                    rho([p + 1, 0])])
+    assert got[0] == "%d|" % HALO_OK and got[1] == "%d|" % HALO_OK and got[2] == "%d|" % HALO_OK
+    assert got[3] == "%d|the_call: rho[1] is zero" % HALO_EINVAL
+    assert got[4] == "%d|the_call: rho[2] is not below the modulus" % HALO_EINVAL
+    assert got[5] == "%d|the_call: rho[0] is not below the modulus" % HALO_EINVAL
+    assert got[6] == "%d|the_call: rho[0] is not below the modulus" % HALO_EINVAL    # the first fault is reported
+
+
+@pytest.mark.parametrize("f", sorted(FIELDS))
+def test_host_scalar_arith(dump, f):
+    """HostScalar takes inputs below the modulus: the edge values that are, in every pair."""
+    p = FIELDS[f]
+    rng = random.Random(0xA517 ^ (p & 0xFFFF))
+    vals = [a for a in edge_values(p) if a < p] + [(p - 1) // 2, (p + 1) // 2] + [rng.randrange(p) for _ in range(6)]
+    pairs = [(a, b) for a in vals for b in vals]
+    got = dump(["arith %s %064x %064x\n" % (f, a, b) for a, b in pairs])
+    for (a, b), g in zip(pairs, got):
+        assert g == words((a + b) % p) + words((a - b) % p) + words(-a % p), (hex(a), hex(b))

@@ -151,6 +151,9 @@ SIGNATURES = {
     "halo_plonk_verify_succinct_batch_dev": [ctypes.c_int, _sz, _sz, _vp, _vp, _sz] + [_vp] * 20,
     "halo_plonk_verify_batch": [ctypes.c_int, _sz, _sz, _vp, _vp, _sz] + [_vp] * 21,
     "halo_plonk_verify_batch_dev": [ctypes.c_int, _sz, _sz, _vp, _vp, _sz] + [_vp] * 23,
+    "halo_acc_verifier_batch": [ctypes.c_int, _sz, _sz, _sz] + [_vp] * 18,
+    "halo_acc_verifier_batch_dev": [ctypes.c_int, _sz, _sz, _sz] + [_vp] * 19,
+    "halo_acc_prover": [ctypes.c_int, _sz, _sz] + [_vp] * 19,
     "halo_field_op": [ctypes.c_int, ctypes.c_int, _vp, _vp, _sz, _vp],
     "halo_curve_op": [ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _sz, _vp],
 }

@@ -24,6 +24,7 @@
 
 #include "dispatch.hpp"
 #include "ipa_session.hpp"
+#include "pcdl_open_fs.hpp"
 #include "pcdl_transcript.hpp"
 #include "runtime.hpp"
 #include "sponge_launch.hpp"
@@ -215,6 +216,44 @@ int check_srs(const char* call, DeviceState* st, int curve, size_t d) {
 }
 
 }  // namespace
+
+// k plain openings over device-resident coefficients, each in its own pooled session: every session's whole chain is
+// enqueued before any is waited for, and every session goes back to the pool on every path.
+int open_fs_dev_chain(const char* call, DeviceState* st, int curve, size_t k, const void* const* d_p, const size_t* lens,
+                      size_t d, const halo_fe_t* z, const halo_wrapped_point_t* C, halo_wrapped_point_t* Ls,
+                      halo_wrapped_point_t* Rs, halo_wrapped_point_t* U, halo_fe_t* c, halo_fe_t* v_out) {
+    const size_t n = d + 1, lg = ilog2(n);
+    HALO_CHECK(check_srs(call, st, curve, d));
+    const uint32_t* params;
+    HALO_CHECK(poseidon_device_params(st, base_field(curve), &params));
+    const int lanes = poseidon_lanes(st, 1);
+    // every session's whole chain is enqueued before any is waited for
+    std::vector<halo_ipa_session*> ses;
+    int rc = HALO_OK;
+    for (size_t i = 0; i < k && !rc; i++) {
+        halo_ipa_session* s = ipa_acquire(st);
+        if (!s) {
+            rc = HALO_EDEVICE;
+            break;
+        }
+        ses.push_back(s);
+        rc = ipa_setup(st, s, curve, n, nullptr, (const halo_fe_t*)d_p[i], lens[i], true, nullptr, &z[i]);
+        s->xi_dev = true;
+        s->solo = k == 1;
+        if (!rc) rc = ipa_eval_cs_enqueue(s, lens[i]);
+        if (!rc) rc = launch_start(s, params, lanes, 0, &C[i], nullptr, nullptr);
+    }
+    if (!rc) rc = enqueue_chains(st, ses.data(), k, params, lanes);
+    for (size_t i = 0; i < ses.size(); i++) {
+        if (rc) continue;
+        rc = finish(call, ses[i], Ls + i * lg, Rs + i * lg, U + i, c + i, v_out ? v_out + i : nullptr);
+    }
+    for (halo_ipa_session* s : ses) ipa_release(s);  // on every path; each waits for its stream
+    return rc;
+}
+
+int open_fs_check_shape(const char* call, int curve, size_t d) { return check_shape(call, (halo_curve_t)curve, d); }
+
 }  // namespace halo
 
 using namespace halo;
@@ -289,7 +328,7 @@ extern "C" int halo_pcdl_open_fs_dev_multi(halo_curve_t curve, size_t k, const v
     if (k == 0) return HALO_OK;
     if (!d_p || !lens || !z || !C || !Ls || !Rs || !U || !c) return set_error(HALO_EINVAL, "%s: null argument", call);
     HALO_CHECK(check_shape(call, curve, d));
-    const size_t n = d + 1, lg = ilog2(n);
+    const size_t n = d + 1;
     for (size_t i = 0; i < k; i++) {
         if (lens[i] && !d_p[i]) return set_error(HALO_EINVAL, "%s: null argument (polynomial %zu)", call, i);
         // (the coefficients are on the device: the length stands for the degree)
@@ -299,31 +338,5 @@ extern "C" int halo_pcdl_open_fs_dev_multi(halo_curve_t curve, size_t k, const v
     DeviceState* st = current_state();
     if (!st) return HALO_EDEVICE;
     std::lock_guard<std::mutex> g(st->mu);
-    HALO_CHECK(check_srs(call, st, curve, d));
-    const uint32_t* params;
-    HALO_CHECK(poseidon_device_params(st, base_field(curve), &params));
-    const int lanes = poseidon_lanes(st, 1);
-    // every session's whole chain is enqueued before any is waited for
-    std::vector<halo_ipa_session*> ses;
-    int rc = HALO_OK;
-    for (size_t i = 0; i < k && !rc; i++) {
-        halo_ipa_session* s = ipa_acquire(st);
-        if (!s) {
-            rc = HALO_EDEVICE;
-            break;
-        }
-        ses.push_back(s);
-        rc = ipa_setup(st, s, curve, n, nullptr, (const halo_fe_t*)d_p[i], lens[i], true, nullptr, &z[i]);
-        s->xi_dev = true;
-        s->solo = k == 1;
-        if (!rc) rc = ipa_eval_cs_enqueue(s, lens[i]);
-        if (!rc) rc = launch_start(s, params, lanes, 0, &C[i], nullptr, nullptr);
-    }
-    if (!rc) rc = enqueue_chains(st, ses.data(), k, params, lanes);
-    for (size_t i = 0; i < ses.size(); i++) {
-        if (rc) continue;
-        rc = finish(call, ses[i], Ls + i * lg, Rs + i * lg, U + i, c + i, v_out ? v_out + i : nullptr);
-    }
-    for (halo_ipa_session* s : ses) ipa_release(s);  // on every path; each waits for its stream
-    return rc;
+    return open_fs_dev_chain(call, st, (int)curve, k, d_p, lens, d, z, C, Ls, Rs, U, c, v_out);
 }

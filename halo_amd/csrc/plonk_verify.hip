@@ -14,10 +14,10 @@
 //   k_plonk_instances   the 3 k instance commitments: acc_prev.C, C_r and C_r_omega made affine (the PCDL
 //                       transcript absorbs affine coordinates)
 //   (fs_device)         pcdl::succinct_check of the 3 k instances, their challenges kept (pcdl_fs.hip)
-//   k_asdl_challenges   one ASDL sponge per proof: label, absorb_fr of the 3 (lg n + 1) xis, absorb_g(U_0, U_1,
-//                       U_2), alpha, z' (acc.rs:157-169)
-//   k_asdl_terms        one lane per proof: the rows of sum alpha^i U_i - acc_next.C, z' == acc_next.z and
-//                       sum alpha^i h_i(z') == acc_next.v (acc.rs:207-210)
+//   (acc_challenges_launch)  one ASDL sponge per proof, m = 3: label, absorb_fr of the 3 (lg n + 1) xis,
+//                       absorb_g(U_0, U_1, U_2), alpha, z' (acc.rs:157-169; k_acc_challenges, acc_fs.hip)
+//   (acc_terms_launch)  the rows of sum alpha^i U_i - acc_next.C, z' == acc_next.z and
+//                       sum alpha^i h_i(z') == acc_next.v (acc.rs:207-210; k_acc_terms, k_acc_finish)
 //   (lincomb_device)    C_bar' - C_bar is the identity
 //   k_plonk_verdict     the stage bits folded into one byte per proof, in the reference's order
 //
@@ -32,6 +32,7 @@
 // As in pcdl_fs.hip no sponge state passes between kernels, and lanes past the batch repeat its last
 // proof because they take part in the shuffles.  Host side: one ScratchLayout, one HostParts table
 // (scratch_layout.hpp), scalar_below / check_rho (host_scalar.hpp), DISPATCH_LANES (sponge_launch.hpp).
+#include "acc_fs.hpp"
 #include "curve.hpp"
 #include "decider.hpp"
 #include "dispatch.hpp"
@@ -45,7 +46,7 @@
 
 namespace halo {
 
-constexpr int ASDL_LABEL = 1, PLONK_LABEL = 2;  // Protocols::{ASDL, PLONK} (outer_sponge.rs:17-22)
+constexpr int PLONK_LABEL = 2;  // Protocols::PLONK (outer_sponge.rs:17-22)
 constexpr int PV_THREADS = 64;                  // the kernels with one lane per proof or per point
 constexpr int N_W = 16, N_R = 15, N_Q = 10, N_T = 16, N_S = 8;  // crates/plonk/src/utils.rs:16-24
 // PlonkProofEvals in struct order (protocol.rs:36-46)
@@ -53,7 +54,7 @@ constexpr int V_WS = 0, V_RS = V_WS + N_W, V_QS = V_RS + N_R, V_TS = V_QS + N_Q,
               V_Z = V_SIGMAS + N_S, V_Z_OMEGA = V_Z + 1, V_W_OMEGAS = V_Z_OMEGA + 1, N_VS = V_W_OMEGAS + 3;
 static_assert(N_VS == HALO_PLONK_EVALS, "halo_gpu.h");
 constexpr int R_TERMS = N_Q + N_W + N_T + 1, RO_TERMS = 4;  // C_r, C_r_omega (protocol.rs:465-475)
-enum { BIT_IDENTITY = 1, BIT_Z = 2, BIT_V = 4 };            // stage bits of a proof: set = the check failed
+enum { BIT_IDENTITY = 1, BIT_Z = ACC_BIT_Z, BIT_V = ACC_BIT_V };  // stage bits of a proof: set = the check failed
 
 // ---------------------------------------------------------------------------------------------
 // points
@@ -386,88 +387,6 @@ __global__ __launch_bounds__(PV_THREADS) void k_plonk_instances(const uint4* __r
         aff_to_wrapped(inst_C + 4 * o, xyzz_to_aff(xyzz_load<F>((j == 1 ? sum_r : sum_ro) + 8 * i)));
 }
 
-// ---------------------------------------------------------------------------------------------
-// acc::verifier
-// ---------------------------------------------------------------------------------------------
-// asdl[2 i ..] = alpha, z' (ark): label, the 3 (lg + 1) challenges of the proof's instances, their three U.
-template <class Cv, int LANES>
-__global__ __launch_bounds__(256) void k_asdl_challenges(const uint32_t* __restrict__ params, const uint4* __restrict__ xis,
-                                                         const uint4* __restrict__ U, size_t lg, size_t k,
-                                                         uint4* __restrict__ asdl) {
-    using Sp = poseidon::OuterSponge<Cv, LANES>;
-    using S = typename Cv::Scalar;
-    constexpr int NS = Sp::FR_ELEMENTS;
-    __shared__ uint32_t tab[poseidon::TABLE_WORDS];
-    poseidon::stage_params(params, tab);
-    bool writer;
-    const size_t i = sponge_index<LANES>(writer);
-    const size_t ic = i < k ? i : k - 1;
-    xis += 2 * 3 * (lg + 1) * ic;
-    U += 4 * 3 * ic;
-    Sp sp;
-    sp.init(tab);
-    const int n_fr = NS * 3 * (int)(lg + 1), total = 1 + n_fr + 6;
-#pragma unroll 1
-    for (int e = 0; e < total; e++) {
-        const int q = e - 1;
-        Fe<typename Cv::Base> x;
-        if (q < 0) {
-            x = Sp::label_element(ASDL_LABEL);
-        } else if (q < n_fr) {
-            uint32_t sw[8];
-            fe_ark_to_canonical_words<S>(xis + 2 * (q / NS), sw);
-            x = Sp::fr_element(sw, q % NS);
-        } else {
-            x = Sp::g_element(U + 4 * ((q - n_fr) >> 1), (q - n_fr) & 1);
-        }
-        sp.absorb(x);
-    }
-#pragma unroll 1
-    for (int c = 0; c < 2; c++) {
-        uint32_t w[8];
-        sp.challenge(w);
-        if (writer && i < k) poseidon::scalar_words_to_ark<S>(asdl + 2 * (2 * i + c), w);
-    }
-}
-
-// One lane per proof: the rows U_0, alpha U_1, alpha^2 U_2 and the addend -acc_next.C; bits[i] gains BIT_Z when
-// z' differs from acc_next.z and BIT_V when sum alpha^j h_j(z') (AccumulatedHPolys::eval, acc.rs:95-101;
-// HPoly::eval, pcdl.rs:222-235) differs from acc_next.v.
-template <class Cv>
-__global__ __launch_bounds__(PV_THREADS) void k_asdl_terms(const uint4* __restrict__ asdl, const uint4* __restrict__ xis,
-                                                           const uint4* __restrict__ U, const uint4* __restrict__ next_C,
-                                                           const uint4* __restrict__ next_z,
-                                                           const uint4* __restrict__ next_v, size_t lg, size_t k,
-                                                           uint4* __restrict__ pts, uint4* __restrict__ sc,
-                                                           uint4* __restrict__ neg_C, uint8_t* __restrict__ bits) {
-    using F = typename Cv::Base;
-    using S = typename Cv::Scalar;
-    const size_t i = (size_t)blockIdx.x * PV_THREADS + threadIdx.x;
-    if (i >= k) return;
-    const Fe<S> one = fe_one<S>(), alpha = fe_from_ark<S>(asdl + 4 * i), z = fe_from_ark<S>(asdl + 4 * i + 2);
-    Fe<S> ap = one, hv = fe_zero<S>();
-#pragma unroll 1
-    for (int j = 0; j < 3; j++) {
-        const uint4* xi = xis + 2 * (3 * i + j) * (lg + 1);
-        Fe<S> zi = z, h = one;
-        if (lg) h = fe_add(one, fe_mul(fe_from_ark<S>(xi + 2 * lg), zi));
-#pragma unroll 1
-        for (size_t q = 1; q < lg; q++) {
-            zi = fe_sqr(zi);
-            h = fe_mul(h, fe_add(one, fe_mul(fe_from_ark<S>(xi + 2 * (lg - q)), zi)));
-        }
-        hv = fe_add(hv, fe_mul(h, ap));
-        fe_to_ark(sc + 2 * (3 * i + j), ap);
-        for (int q = 0; q < 4; q++) pts[4 * (3 * i + j) + q] = U[4 * (3 * i + j) + q];
-        ap = fe_mul(ap, alpha);
-    }
-    Affine<F> C = aff_from_wrapped<F>(next_C + 4 * i);
-    if (!aff_is_id(C)) C.y = fe_neg(C.y);
-    aff_to_wrapped(neg_C + 4 * i, C);
-    const bool z_eq = fe_eq(z, fe_from_ark<S>(next_z + 2 * i)), v_eq = fe_eq(hv, fe_from_ark<S>(next_v + 2 * i));
-    bits[i] |= (z_eq ? 0 : BIT_Z) | (v_eq ? 0 : BIT_V);
-}
-
 // verdict[i]: HALO_PLONK_MALFORMED first (the reference has no value for such a proof), then the reference's
 // checks in its order.
 __global__ __launch_bounds__(PV_THREADS) void k_plonk_verdict(const uint8_t* __restrict__ mal, const uint8_t* __restrict__ bits,
@@ -623,7 +542,7 @@ static int plonk_device(const char* call, DeviceState* st, const PlonkCall& a, h
                  o_os = sl.take(k * RO_TERMS * 32), o_sr = sl.take(k * 128), o_so = sl.take(k * 128),
                  o_ic = sl.take(ipp * k * 64), o_iz = sl.take(ipp * k * 32), o_iv = sl.take(ipp * k * 32),
                  o_xis = sl.take(ipp * k * (lg + 1) * 32), o_den = sl.take(k * m * 32), o_ap = sl.take(3 * k * 64),
-                 o_as = sl.take(3 * k * 32), o_neg = sl.take(k * 64), o_sum = sl.take(k * 128),
+                 o_as = sl.take(3 * k * 32), o_sh = sl.take(3 * k * 32), o_neg = sl.take(k * 64), o_sum = sl.take(k * 128),
                  o_chal = sl.take(a.chal_out ? 0 : k * 5 * 32), o_sides = sl.take(a.sides_out ? 0 : k * 2 * 32),
                  o_asdl = sl.take(a.asdl_out ? 0 : k * 2 * 32), o_mal = sl.take(k), o_bits = sl.take(k),
                  o_ok3 = sl.take(ipp * k), o_cid = sl.take(k), o_l4 = sl.take(4 * nx * lg * 64),
@@ -699,24 +618,10 @@ static int plonk_device(const char* call, DeviceState* st, const PlonkCall& a, h
         HALO_HIP(hipGetLastError());
         xis3 = u4(o_xis3);
     }
-    {
-        ProfScope prof("asdl_challenges", s);
-        DISPATCH_CURVE(a.curve, Cv, {
-            DISPATCH_LANES(lanes, L, {
-                HALO_LAUNCH(prof, (k_asdl_challenges<Cv, L>), dim3(g.blocks), dim3(g.threads), 0, s, params, xis3, cp(a.U),
-                            lg, k, asdl);
-            });
-        });
-        HALO_HIP(hipGetLastError());
-    }
-    {
-        ProfScope prof("asdl_terms", s);
-        DISPATCH_CURVE(a.curve, Cv, {
-            HALO_LAUNCH(prof, k_asdl_terms<Cv>, per_proof, blk, 0, s, (const uint4*)asdl, xis3, cp(a.U),
-                        cp(a.next_C), cp(a.next_z), cp(a.next_v), lg, k, u4(o_ap), u4(o_as), u4(o_neg), bits);
-        });
-        HALO_HIP(hipGetLastError());
-    }
+    // acc::verifier's transcript and terms: the general-m launches of acc_fs.hip with m = 3
+    HALO_CHECK(acc_challenges_launch(st, a.curve, xis3, a.U, lg, k, 3, asdl, s, "asdl_challenges"));
+    HALO_CHECK(acc_terms_launch(a.curve, asdl, xis3, a.U, a.next_C, a.next_z, a.next_v, lg, k, 3, u4(o_ap), u4(o_as), u4(o_sh),
+                                u4(o_neg), bits, nullptr, s, "asdl_terms"));
     HALO_CHECK(lincomb_device(st, a.curve, u4(o_neg), u4(o_ap), u4(o_as), k, 3, u4(o_sum), cid, s));
     hipLaunchKernelGGL(k_plonk_verdict, per_proof, blk, 0, s, (const uint8_t*)mal, (const uint8_t*)bits, (const uint8_t*)ok3,
                        (const uint8_t*)cid, k, ipp, (uint8_t*)a.verdict, a.full ? base + o_live : (uint8_t*)nullptr);

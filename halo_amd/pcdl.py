@@ -636,6 +636,24 @@ def _check_shapes(insts, cid: int) -> None:
             raise ValueError(f"instance {i}: the proof has {len(q.pi['Ls'])} rounds, d = {q.d} needs {lg}")
 
 
+def instance_rows(qs, d: int) -> list:
+    """The arrays of halo_pcdl_succinct_check_fs_batch for a list of instances of one degree bound d, in its
+    argument order: C, z, v, Ls, Rs, U, c, hiding, C_bar, w_prime.  Ls / Rs are None at d = 0; the last three are
+    None when no instance hides, else C_bar / w_prime are zero where the flag is not set."""
+    hid = [q.pi.get("C_bar") is not None for q in qs]
+    zero_pt, zero_fe = np.zeros(8, dtype=np.uint64), np.zeros(4, dtype=np.uint64)
+    rows = [np.stack([H.point_array(q.C).reshape(8) for q in qs]), np.stack([H.fe_array(q.z, 1)[0] for q in qs]),
+            np.stack([H.fe_array(q.v, 1)[0] for q in qs]),
+            np.ascontiguousarray(np.concatenate([H.point_array(q.pi["Ls"]) for q in qs])) if d else None,
+            np.ascontiguousarray(np.concatenate([H.point_array(q.pi["Rs"]) for q in qs])) if d else None,
+            np.stack([H.point_array(q.pi["U"]).reshape(8) for q in qs]), np.stack([H.fe_array(q.pi["c"], 1)[0] for q in qs])]
+    if not any(hid):
+        return rows + [None, None, None]
+    return rows + [np.array(hid, dtype=np.uint8),
+                   np.stack([H.point_array(q.pi["C_bar"]).reshape(8) if h else zero_pt for q, h in zip(qs, hid)]),
+                   np.stack([H.fe_array(q.pi["w_prime"], 1)[0] if h else zero_fe for q, h in zip(qs, hid)])]
+
+
 def succinct_check_device(instances, curve="pallas"):
     """succinct_check_many without transcripts: the device derives every challenge itself
     (halo_pcdl_succinct_check_fs_batch, one call per distinct d).  Returns [(HPoly, U)]; raises CheckFailed
@@ -646,21 +664,11 @@ def succinct_check_device(instances, curve="pallas"):
     _check_shapes(insts, cid)
     ok = np.zeros(len(insts), dtype=np.uint8)
     xis = [None] * len(insts)
-    zero_pt, zero_fe = np.zeros(8, dtype=np.uint64), np.zeros(4, dtype=np.uint64)
     for d in sorted({q.d for q in insts}):
         idx = [i for i, q in enumerate(insts) if q.d == d]
         qs = [insts[i] for i in idx]
-        hid = [q.pi.get("C_bar") is not None for q in qs]
-        ok_d, xis_d, _ = succinct_check_fs_verdicts(
-            np.stack([H.point_array(q.C).reshape(8) for q in qs]), d, np.stack([H.fe_array(q.z, 1)[0] for q in qs]),
-            np.stack([H.fe_array(q.v, 1)[0] for q in qs]),
-            np.concatenate([H.point_array(q.pi["Ls"]) for q in qs]) if d else None,
-            np.concatenate([H.point_array(q.pi["Rs"]) for q in qs]) if d else None,
-            np.stack([H.point_array(q.pi["U"]).reshape(8) for q in qs]),
-            np.stack([H.fe_array(q.pi["c"], 1)[0] for q in qs]),
-            hiding=hid if any(hid) else None,
-            C_bars=np.stack([H.point_array(q.pi["C_bar"]).reshape(8) if h else zero_pt for q, h in zip(qs, hid)]),
-            w_primes=np.stack([H.fe_array(q.pi["w_prime"], 1)[0] if h else zero_fe for q, h in zip(qs, hid)]), curve=cid)
+        C, z, v, Ls, Rs, U, c, hid, cb, wp = instance_rows(qs, d)
+        ok_d, xis_d, _ = succinct_check_fs_verdicts(C, d, z, v, Ls, Rs, U, c, hiding=hid, C_bars=cb, w_primes=wp, curve=cid)
         for j, i in enumerate(idx):
             ok[i], xis[i] = ok_d[j], xis_d[j]
     for i in range(len(insts)):
@@ -737,22 +745,12 @@ def check_batch(instances, rhos=None, curve="pallas", verdicts: bool = False, bi
     rh = H.fe_array(rhos, len(insts)) if rhos is not None else None
     _check_shapes(insts, cid)
     codes = np.zeros(len(insts), dtype=np.uint8)
-    zero_pt, zero_fe = np.zeros(8, dtype=np.uint64), np.zeros(4, dtype=np.uint64)
     for d in sorted({q.d for q in insts}):
         idx = [i for i, q in enumerate(insts) if q.d == d]
         qs = [insts[i] for i in idx]
-        hid = [q.pi.get("C_bar") is not None for q in qs]
-        codes[idx] = check_fs_codes(
-            np.stack([H.point_array(q.C).reshape(8) for q in qs]), d, np.stack([H.fe_array(q.z, 1)[0] for q in qs]),
-            np.stack([H.fe_array(q.v, 1)[0] for q in qs]),
-            np.concatenate([H.point_array(q.pi["Ls"]) for q in qs]) if d else None,
-            np.concatenate([H.point_array(q.pi["Rs"]) for q in qs]) if d else None,
-            np.stack([H.point_array(q.pi["U"]).reshape(8) for q in qs]),
-            np.stack([H.fe_array(q.pi["c"], 1)[0] for q in qs]),
-            hiding=hid if any(hid) else None,
-            C_bars=np.stack([H.point_array(q.pi["C_bar"]).reshape(8) if h else zero_pt for q, h in zip(qs, hid)]),
-            w_primes=np.stack([H.fe_array(q.pi["w_prime"], 1)[0] if h else zero_fe for q, h in zip(qs, hid)]),
-            rhos=rh[idx] if rh is not None else None, curve=cid, bisect=bisect)
+        C, z, v, Ls, Rs, U, c, hid, cb, wp = instance_rows(qs, d)
+        codes[idx] = check_fs_codes(C, d, z, v, Ls, Rs, U, c, hiding=hid, C_bars=cb, w_primes=wp,
+                                    rhos=rh[idx] if rh is not None else None, curve=cid, bisect=bisect)
     if verdicts:
         return codes
     for i, c in enumerate(codes):

@@ -23,7 +23,8 @@ Out of scope (SURVEY §8 "out of scope"): circuit construction and witness gener
 polynomials here are synthetic), the Poseidon Fiat-Shamir transcript on the benchmarked path (challenges
 come from a seeded stand-in, ``Challenges``; ``naive_prover(..., transcript=new_transcript)`` runs the
 reference's sponges instead, so that halo_amd.plonk can verify the proof; on
-``DeviceBackend(curve, device_transcripts=True)`` the PCDL sponges of that mode run on the device), the succinct checks of acc::prover (verifier arithmetic over lg n
+``DeviceBackend(curve, device_transcripts=True)`` the PCDL sponges of that mode run on the device, and with
+``device_acc=True`` acc::prover is one call whose ASDL sponge runs there too), the succinct checks of acc::prover (verifier arithmetic over lg n
 elements) and the hiding terms (``naive_prover`` opens with w = None).  The generic pipeline also
 runs on the CPU restatement backend (oracle/prover_ref.py) at small n: tests/test_gpu_prover.py
 checks every commitment, evaluation and opening bit-exact against it.
@@ -423,7 +424,7 @@ def acc_prover(B, qs, d: int, chal: Challenges):
 class DeviceBackend:
     """Values are torch int64 (len, 4) device tensors of ark words; scalars are canonical ints."""
 
-    def __init__(self, curve: str = "pallas", device_transcripts: bool = False):
+    def __init__(self, curve: str = "pallas", device_transcripts: bool = False, device_acc: bool = False):
         import torch
 
         from . import _lib as H
@@ -433,6 +434,8 @@ class DeviceBackend:
         # round 5 under transcripts: the PCDL sponges run on the device (halo_pcdl_open_fs_dev_multi,
         # pcdl.succinct_check_device) and the opened polynomials stay there
         self.device_transcripts = device_transcripts
+        # acc::prover in one call, its ASDL sponge on the device too (halo_acc_prover, acc.prover_device)
+        self.device_acc = device_acc
         self.curve = H.CURVES[curve]
         self.field = H.SCALAR_FIELD[self.curve]
         self.m = SCALAR_MODULUS[curve]
@@ -799,7 +802,10 @@ class DeviceBackend:
         insts = [pcdl.Instance(np.asarray(q["C"], dtype=np.uint64), d, self.fe(q["z"]), self.fe(q["v"]),
                                {"Ls": np.stack(q["Ls"]), "Rs": np.stack(q["Rs"]), "U": np.asarray(q["U"], dtype=np.uint64),
                                 "c": self.fe(q["c"]), "C_bar": None, "w_prime": None}) for q in qs]
-        a = acc.prover(insts, new_transcript, self.curve, device_transcripts=self.device_transcripts)
+        if self.device_acc:
+            a = acc.prover_device(insts, self.curve)
+        else:
+            a = acc.prover(insts, new_transcript, self.curve, device_transcripts=self.device_transcripts)
         return {"C": a.C, "z": self.to_int(a.z), "v": self.to_int(a.v), "Ls": a.pi["Ls"], "Rs": a.pi["Rs"],
                 "U": a.pi["U"], "c": self.to_int(a.pi["c"])}
 

@@ -682,6 +682,69 @@ int halo_plonk_verify_batch_dev(halo_curve_t curve, size_t rows, size_t k,
         const void* d_acc_next_Ls, const void* d_acc_next_Rs, const void* d_acc_next_U, const void* d_acc_next_c,
         const void* d_mds, const void* d_rho, void* d_verdict, void* d_combined, void* stream);
 
+/* ------------------------------------------------------------------ the accumulation scheme
+ * acc::verifier (crates/accumulation/src/acc.rs:128-176,200-213) for k accumulations of m >= 1 instances each, all of
+ * one degree bound d.  Instance j of accumulation i is row i m + j of C, z, v, Ls, Rs, U, c, hiding, C_bar, w_prime,
+ * in the layouts and with the meaning of halo_pcdl_succinct_check_fs_batch (hiding NULL: no instance hides); its
+ * accumulator is (acc_C[i], d, acc_z[i], acc_v[i]) (acc.pi is not read, acc.rs:201).  Every transcript runs on the
+ * device: the PCDL sponge of each of the k m succinct checks and the ASDL sponge of each accumulation (label,
+ * absorb_fr of the m (lg n + 1) challenges, absorb_g(U_0 .. U_(m-1)), alpha, z').
+ * verdict[i] is HALO_ACC_ACCEPT or the first failing check in the reference's order: the instances in order, then
+ * C_bar, z, v.  first_bad[i] (may be NULL) is the index of the failing instance, or m.  Optional outputs:
+ * asdl_out[2 i ..] = alpha, z'; C_bar_out[i] = C_bar' = sum_j alpha^j U_j; v_out[i] = sum_j alpha^j h_j(z').
+ * acc_C, acc_z, acc_v may be NULL together: the call is then common_subroutine plus the evaluation, the verdicts
+ * are ACCEPT or INSTANCE only, and asdl_out, C_bar_out and v_out are required.
+ * A point of an instance that is neither (0, 0) nor on the curve gives HALO_ACC_INSTANCE for its accumulation alone;
+ * an acc_C that is no point, or differs from C_bar', gives HALO_ACC_C_BAR (C_bar_out[i] is unspecified for an acc_C
+ * that is no point or an accumulation with an invalid U).  lg n = 0 (d = 0) is accepted, Ls / Rs may then be NULL.
+ * Needs the resident SRS with (S, H) and halo_poseidon_set_params for the curve's base field.  Before any device
+ * work: HALO_EINVAL "No instances given" for m = 0, for a null required pointer, for hiding without C_bar and
+ * w_prime, for acc_C / acc_z / acc_v only partly given, for unset Poseidon parameters and for a scalar (z, v, c, a
+ * read w', acc_z, acc_v) that is not below the modulus; HALO_ENOTPOW2 "n ({n}) is not a power of two"; then
+ * HALO_ESRSRANGE "d was larger than D!" or for a missing (S, H).  k = 0: HALO_OK.  No GPU: HALO_EDEVICE. */
+typedef enum {
+    HALO_ACC_ACCEPT = 0,
+    HALO_ACC_INSTANCE = 1, /* a succinct check failed (acc.rs:149); first_bad names the instance */
+    HALO_ACC_C_BAR = 2,    /* "C_bar' != C_bar" (acc.rs:207) */
+    HALO_ACC_Z = 3,        /* "z' = z" (acc.rs:208) */
+    HALO_ACC_V = 4         /* "h(z) = v" (acc.rs:210) */
+} halo_acc_verdict_t;
+int halo_acc_verifier_batch(halo_curve_t curve, size_t d, size_t k, size_t m,
+        const halo_wrapped_point_t* C, const halo_fe_t* z, const halo_fe_t* v,
+        const halo_wrapped_point_t* Ls, const halo_wrapped_point_t* Rs,
+        const halo_wrapped_point_t* U, const halo_fe_t* c,
+        const uint8_t* hiding, const halo_wrapped_point_t* C_bar, const halo_fe_t* w_prime,
+        const halo_wrapped_point_t* acc_C, const halo_fe_t* acc_z, const halo_fe_t* acc_v,
+        uint8_t* verdict, uint32_t* first_bad, halo_fe_t* asdl_out, halo_wrapped_point_t* C_bar_out, halo_fe_t* v_out);
+/* The same over device pointers, asynchronous on `stream`; no host wait, no host arithmetic.  Here a scalar that
+ * is not below the modulus gives its accumulation a failing verdict and leaves the neighbours alone: HALO_ACC_INSTANCE
+ * for an instance's scalar, HALO_ACC_Z / HALO_ACC_V for acc_z / acc_v. */
+int halo_acc_verifier_batch_dev(halo_curve_t curve, size_t d, size_t k, size_t m, const void* d_C, const void* d_z,
+        const void* d_v, const void* d_Ls, const void* d_Rs, const void* d_U, const void* d_c, const void* d_hiding,
+        const void* d_C_bar, const void* d_w_prime, const void* d_acc_C, const void* d_acc_z, const void* d_acc_v,
+        void* d_verdict, void* d_first_bad, void* d_asdl_out, void* d_C_bar_out, void* d_v_out, void* stream);
+/* acc::prover (acc.rs:178-198) of the m instances C[j], z[j], v[j], Ls / Rs[j lg n + ..], U[j], c[j] (hiding, C_bar,
+ * w_prime as above) of degree bound d, n = d + 1 >= 2 a power of two: common_subroutine on the device, h(X) =
+ * sum_j alpha^j h_j(X) formed on the device from the resident challenges (it never visits the host), one copy of
+ * (C_bar, z, v, the verdict) home and one wait, then the plain opening of h at z with commitment C_bar
+ * (halo_pcdl_open_fs_dev_multi's chain for k = 1, its PCDL transcript on the device).  That copy of 168 bytes lands
+ * in ordinary host memory of the call, not in pinned staging: the only pinned buffers belong to pooled sessions, and
+ * none is open before the verdict is known.  The opener's own v = h(z), from the coefficients, is compared with
+ * sum_j alpha^j h_j(z) from the product forms; a difference is HALO_EDEVICE.  The accumulator is
+ * (acc_C, d, acc_z, acc_v) with acc.pi = (acc_Ls, acc_Rs: lg n WrappedPoints each; acc_U, acc_c).
+ * If a succinct check fails the call is still HALO_OK: *verdict = HALO_ACC_INSTANCE, *first_bad (may be NULL) names the
+ * instance, no session is opened and the acc_ outputs are untouched; otherwise *verdict = HALO_ACC_ACCEPT and
+ * *first_bad = m.  The errors of halo_acc_verifier_batch, and the opener's: HALO_EINVAL "assertion failed: n > 1".
+ * The session the opening uses goes back to the pool on every path. */
+int halo_acc_prover(halo_curve_t curve, size_t d, size_t m,
+        const halo_wrapped_point_t* C, const halo_fe_t* z, const halo_fe_t* v,
+        const halo_wrapped_point_t* Ls, const halo_wrapped_point_t* Rs,
+        const halo_wrapped_point_t* U, const halo_fe_t* c,
+        const uint8_t* hiding, const halo_wrapped_point_t* C_bar, const halo_fe_t* w_prime,
+        halo_wrapped_point_t* acc_C, halo_fe_t* acc_z, halo_fe_t* acc_v,
+        halo_wrapped_point_t* acc_Ls, halo_wrapped_point_t* acc_Rs, halo_wrapped_point_t* acc_U, halo_fe_t* acc_c,
+        uint8_t* verdict, uint32_t* first_bad);
+
 /* ------------------------------------------------------------------ measurement hooks
  * When enabled, the library brackets its dominant kernels (MSM bucket accumulation, NTT passes)
  * with hipEvents on the stream they run on; halo_profile_read returns the number of launches and

@@ -15,6 +15,8 @@ reference's names, argument meaning and assertion messages:
                          Poseidon sponge of crates/poseidon, as batches of independent items
     halo_amd.plonk    -- crates/plonk/src/plonk/protocol.rs (PlonkProof, verify_succinct, verify: batches
                          of raw proofs of one circuit, every transcript on the device)
+    halo_amd.sponge   -- crates/poseidon/src/outer_sponge.rs (Sponge: the Fiat-Shamir sponge as an object with
+                         its state on the device; SpongeBatch: k of them in lockstep; new_transcript)
 
 Field elements are numpy uint64 arrays of shape (n, 4) in arkworks Montgomery form; points are
 (n, 8) WrappedPoint arrays (x, y Montgomery limbs; (0, 0) = identity).  There is no CPU fallback:
@@ -22,4 +24,4 @@ without the HIP library or a GPU every call raises.
 """
 from . import _lib  # noqa: F401
 
-__all__ = ["_lib", "group", "poly", "pedersen", "pcdl", "acc", "schnorr", "plonk"]
+__all__ = ["_lib", "group", "poly", "pedersen", "pcdl", "acc", "schnorr", "plonk", "sponge"]

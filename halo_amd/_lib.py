@@ -154,6 +154,17 @@ SIGNATURES = {
     "halo_acc_verifier_batch": [ctypes.c_int, _sz, _sz, _sz] + [_vp] * 18,
     "halo_acc_verifier_batch_dev": [ctypes.c_int, _sz, _sz, _sz] + [_vp] * 19,
     "halo_acc_prover": [ctypes.c_int, _sz, _sz] + [_vp] * 19,
+    "halo_sponge_new": [ctypes.c_int, ctypes.c_int, _sz, _u64p],
+    "halo_sponge_free": [ctypes.c_uint64],
+    "halo_sponge_reset": [ctypes.c_uint64],
+    "halo_sponge_absorb_g": [ctypes.c_uint64, _vp, _sz],
+    "halo_sponge_absorb_fr": [ctypes.c_uint64, _vp, _sz],
+    "halo_sponge_absorb_fq": [ctypes.c_uint64, _vp, _sz],
+    "halo_sponge_challenge": [ctypes.c_uint64, _sz, _vp],
+    "halo_sponge_absorb_g_dev": [ctypes.c_uint64, _vp, _sz, _vp],
+    "halo_sponge_absorb_fr_dev": [ctypes.c_uint64, _vp, _sz, _vp],
+    "halo_sponge_absorb_fq_dev": [ctypes.c_uint64, _vp, _sz, _vp],
+    "halo_sponge_challenge_dev": [ctypes.c_uint64, _sz, _vp, _vp],
     "halo_field_op": [ctypes.c_int, ctypes.c_int, _vp, _vp, _sz, _vp],
     "halo_curve_op": [ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _sz, _vp],
 }

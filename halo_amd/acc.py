@@ -1,8 +1,9 @@
 """Mirror of crates/accumulation/src/acc.rs:128-217 (common_subroutine, prover, verifier, decider) on the
 MI355X backend.
 
-The Fiat-Shamir sponges stay with the caller: ``new_transcript(label)`` returns a fresh sponge with the
-reference's interface (absorb_g, absorb_fr, challenge over WrappedPoints / ark scalars) for the label
+The Fiat-Shamir sponges are the caller's choice: ``new_transcript(label)`` returns a fresh sponge with the
+reference's interface (absorb_g, absorb_fr, challenge over WrappedPoints / ark scalars;
+``halo_amd.sponge.new_transcript(curve)`` is the library's own, on the device) for the label
 "ASDL" (one per common_subroutine, acc.rs:135) or "PCDL" (one per succinct check and per opening,
 pcdl.rs:336,496).  The m succinct checks of common_subroutine run as one batch on the device
 (pcdl.succinct_check_many; with ``device_transcripts=True`` their PCDL sponges run there too,

@@ -150,6 +150,17 @@ ProfScope::~ProfScope() {
     g_prof[slot].pending.emplace_back(a, b);
 }
 
+void prof_count(const char* name, size_t count) {
+    if (!g_prof_on) return;
+    std::lock_guard<std::mutex> g(g_prof_mu);
+    for (auto& e : g_prof)
+        if (e.name == name) {
+            e.launches += count;
+            return;
+        }
+    g_prof.push_back(ProfEntry{name, {}, count, 0.0});
+}
+
 static void prof_drain() {
     for (auto& e : g_prof) {
         for (auto& p : e.pending) {
@@ -245,7 +256,7 @@ int halo_init(int device) {
 
 const char* halo_last_error(void) { return g_last_error.c_str(); }
 
-int halo_abi_version(void) { return 108; }
+int halo_abi_version(void) { return 109; }
 
 // Releases the library's HIP objects while the runtime is alive: pending profiling events, the MSM
 // pipeline's streams and events, the scratch fence events.  Python registers it with atexit

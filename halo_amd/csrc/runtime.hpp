@@ -178,7 +178,11 @@ struct ProfScope {
     ~ProfScope();
 };
 
-#define HALO_LAUNCH(prof, kern, grid, block, shmem, stream, ...)                                       \
+// A count that is no launch (the permutations of the sponge handles, sponge.hip): added to the `launches` that
+// halo_profile_read reports under `name`, while profiling is enabled.
+void prof_count(const char* name, size_t count);
+
+#define HALO_LAUNCH(prof, kern, grid, block, shmem, stream, ...)                                      \
     do {                                                                                              \
         if ((prof).slot >= 0)                                                                         \
             hipExtLaunchKernelGGL(kern, grid, block, shmem, stream, (prof).a, (prof).b, 0, __VA_ARGS__); \

@@ -224,8 +224,8 @@ def open_without_eval(p, C, d: int, z, v, w=None, transcript=None, q=None, w_bar
     p: coefficients (ark scalars, degree <= d); C its commitment; z, v ark scalars; w the commitment
     randomness (None: non-hiding).  ``transcript`` is the caller's Fiat-Shamir sponge with the
     reference's interface (outer_sponge.rs: absorb_g(points), absorb_fr(scalars), challenge()) over
-    WrappedPoints / ark scalars -- a fresh PCDL sponge, as pcdl.rs:336 creates; it is required (the
-    sponge is host logic outside this backend).  q (d coefficients) and w_bar are the random draws the
+    WrappedPoints / ark scalars -- a fresh PCDL sponge, as pcdl.rs:336 creates; it is required
+    (``halo_amd.sponge.Sponge(curve, "PCDL")`` is the library's own).  q (d coefficients) and w_bar are the random draws the
     reference takes from its rng (pcdl.rs:347,352).  p, p_bar and p' stay in the session's device
     buffers from the blind to the rounds (halo_pcdl_open_begin / _blind / _combine / _start).
     Returns the EvalProof: dict(Ls, Rs, U, c, C_bar, w_prime)."""

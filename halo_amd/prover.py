@@ -24,7 +24,8 @@ polynomials here are synthetic), the Poseidon Fiat-Shamir transcript on the benc
 come from a seeded stand-in, ``Challenges``; ``naive_prover(..., transcript=new_transcript)`` runs the
 reference's sponges instead, so that halo_amd.plonk can verify the proof; on
 ``DeviceBackend(curve, device_transcripts=True)`` the PCDL sponges of that mode run on the device, and with
-``device_acc=True`` acc::prover is one call whose ASDL sponge runs there too), the succinct checks of acc::prover (verifier arithmetic over lg n
+``device_acc=True`` acc::prover is one call whose ASDL sponge runs there too, and with ``device_plonk=True`` the
+prover's own PLONK sponge is a halo_amd.sponge.Sponge: no Python sponge is left), the succinct checks of acc::prover (verifier arithmetic over lg n
 elements) and the hiding terms (``naive_prover`` opens with w = None).  The generic pipeline also
 runs on the CPU restatement backend (oracle/prover_ref.py) at small n: tests/test_gpu_prover.py
 checks every commitment, evaluation and opening bit-exact against it.
@@ -204,12 +205,46 @@ class _TranscriptChallenges:
         self.sponge, self.m = sponge, modulus
         self.r_inv = pow(1 << 256, -1, modulus)
 
-    def absorb_g(self, points):
+    def absorb_g(self, points, then: int = 0):
         self.sponge.absorb_g(points)
 
     def __call__(self) -> int:
         x = np.asarray(self.sponge.challenge(), dtype=np.uint64).reshape(4)
         return (int(x[0]) | int(x[1]) << 64 | int(x[2]) << 128 | int(x[3]) << 192) * self.r_inv % self.m
+
+
+class _DevicePlonkChallenges:
+    """The same interface over a device sponge (halo_amd.sponge.Sponge, ``DeviceBackend(device_plonk=True)``): the
+    commitments are absorbed from the buffer the backend's last ``commit_many`` wrote them to, and the ``then``
+    challenges that the protocol draws before it absorbs again are squeezed behind the absorb on the backend's
+    stream and copied to pinned memory, so they are home when the round's own ``B.sync()`` returns."""
+
+    def __init__(self, B):
+        from .sponge import SpongeBatch
+
+        self.B = B
+        self.sponge = SpongeBatch(B.curve, "PLONK", 1)  # Sponge::new(PLONK), several challenges per call
+        self.home = B.torch.empty((2, 4), dtype=B.torch.int64, pin_memory=True)
+        self.ready = B.torch.cuda.Event()
+        self.queue = []
+
+    def absorb_g(self, points, then: int = 0):
+        t = self.B.last_commitments
+        assert t is not None and t.shape[0] == len(points), "absorb_g follows the commit_many of the same points"
+        self.sponge.absorb_g_dev(t)
+        if then:
+            assert not self.queue and then <= self.home.shape[0]
+            self.home[:then].copy_(self.sponge.challenge_dev(then).reshape(then, 4), non_blocking=True)
+            self.ready.record()
+            self.queue = list(range(then))
+
+    def __call__(self) -> int:
+        assert self.queue, "every draw is announced by the absorb before it"
+        self.ready.synchronize()
+        return self.B.to_int(self.home[self.queue.pop(0)].numpy().view(np.uint64))
+
+    def close(self):
+        self.sponge.close()
 
 
 def naive_prover(B, wit, n: int, chal: Challenges, acc_prev=None, keep=None, transcript=None):
@@ -224,13 +259,21 @@ def naive_prover(B, wit, n: int, chal: Challenges, acc_prev=None, keep=None, tra
     sponge absorbs C_ws, C_z and C_ts where protocol.rs:116,163,265 do, and round 5 goes through the
     backend's ``instance_open`` / ``acc_prove`` hooks (Instance::open and acc::prover under their own
     sponges).  ``acc_prev`` is then required, as the dict such a hook returns (C, z, v, Ls, Rs, U, c),
-    and ``chal`` is not read."""
+    and ``chal`` is not read.  On ``DeviceBackend(..., device_plonk=True)`` the PLONK sponge is the library's
+    (halo_amd.sponge) and ``transcript("PLONK")`` is not called; with ``device_transcripts`` and ``device_acc`` set
+    as well the factory is used for nothing but its presence, and ``transcript="device"`` says so."""
     import time
 
     if transcript is not None:
         if acc_prev is None:
             raise ValueError("naive_prover under a transcript needs acc_prev (an accumulator of acc_prove)")
-        chal = _TranscriptChallenges(transcript("PLONK"), B.m)
+        device_plonk = getattr(B, "device_plonk", False)
+        if isinstance(transcript, str) and not (transcript == "device" and device_plonk
+                                                and getattr(B, "device_transcripts", False)
+                                                and getattr(B, "device_acc", False)):
+            raise ValueError('transcript="device" needs DeviceBackend(curve, device_transcripts=True, device_acc=True, '
+                             "device_plonk=True); otherwise pass a new_transcript(label) factory")
+        chal = _DevicePlonkChallenges(B) if device_plonk else _TranscriptChallenges(transcript("PLONK"), B.m)
     real = transcript is not None
     m = B.m
     d = n - 1
@@ -256,7 +299,7 @@ def naive_prover(B, wit, n: int, chal: Challenges, acc_prev=None, keep=None, tra
     t1 = time.perf_counter()
     C_ws = B.commit_many(wit["ws"])
     if real:
-        chal.absorb_g(C_ws)
+        chal.absorb_g(C_ws, then=2)   # beta, gamma
     B.sync()
     times["round1"] = time.perf_counter() - t1
 
@@ -283,7 +326,7 @@ def naive_prover(B, wit, n: int, chal: Challenges, acc_prev=None, keep=None, tra
     z = B.intt(z_evals)
     C_z = B.commit_many([z])[0]
     if real:
-        chal.absorb_g([C_z])
+        chal.absorb_g([C_z], then=1)  # alpha
     B.sync()
     times["round3"] = time.perf_counter() - t3
 
@@ -320,7 +363,7 @@ def naive_prover(B, wit, n: int, chal: Challenges, acc_prev=None, keep=None, tra
     ts = B.split(B.resize(t, T_POLYS * n), n)                  # t_split (protocol.rs:509-517)
     C_ts = B.commit_many(ts)
     if real:
-        chal.absorb_g(C_ts)
+        chal.absorb_g(C_ts, then=2)   # zeta, xi
     B.sync()
     times["round4"] = time.perf_counter() - t4
 
@@ -330,6 +373,8 @@ def naive_prover(B, wit, n: int, chal: Challenges, acc_prev=None, keep=None, tra
     r = geometric_polys(B, zeta, wit["qs"] + wit["ws"] + ts + [z])
     r_omega = geometric_polys(B, zeta, wit["ws"][0:3] + [z])
     xi = chal()
+    if hasattr(chal, "close"):  # the device sponge's state
+        chal.close()
     omega = B.omega(n)
     if keep is not None:
         keep.update(ts=ts, zeta=zeta, xi=xi)
@@ -424,7 +469,8 @@ def acc_prover(B, qs, d: int, chal: Challenges):
 class DeviceBackend:
     """Values are torch int64 (len, 4) device tensors of ark words; scalars are canonical ints."""
 
-    def __init__(self, curve: str = "pallas", device_transcripts: bool = False, device_acc: bool = False):
+    def __init__(self, curve: str = "pallas", device_transcripts: bool = False, device_acc: bool = False,
+                 device_plonk: bool = False):
         import torch
 
         from . import _lib as H
@@ -436,6 +482,10 @@ class DeviceBackend:
         self.device_transcripts = device_transcripts
         # acc::prover in one call, its ASDL sponge on the device too (halo_acc_prover, acc.prover_device)
         self.device_acc = device_acc
+        # the prover's own PLONK sponge on the device (halo_amd.sponge): C_ws, C_z, C_ts are absorbed from the buffer
+        # commit_many wrote them to
+        self.device_plonk = device_plonk
+        self.last_commitments = None
         self.curve = H.CURVES[curve]
         self.field = H.SCALAR_FIELD[self.curve]
         self.m = SCALAR_MODULUS[curve]
@@ -675,6 +725,7 @@ class DeviceBackend:
         lens = (ctypes.c_size_t * k)(*[p.shape[0] for p in polys])
         self.H.check(self.L.halo_msm_batch_dev(self.curve, ptrs, lens, k, ctypes.c_void_p(outs.data_ptr()), self.sp))
         self.H.check(self.L.halo_msm_join(self.sp))
+        self.last_commitments = outs if self.device_plonk else None
         return [o.view(np.uint64) for o in outs.cpu().numpy()]
 
     def eval_many(self, polys, z: int):

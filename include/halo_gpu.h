@@ -745,10 +745,46 @@ int halo_acc_prover(halo_curve_t curve, size_t d, size_t m,
         halo_wrapped_point_t* acc_Ls, halo_wrapped_point_t* acc_Rs, halo_wrapped_point_t* acc_U, halo_fe_t* acc_c,
         uint8_t* verdict, uint32_t* first_bad);
 
+/* ------------------------------------------------------------------ the Fiat-Shamir sponge as an object
+ * Sponge<P> (crates/poseidon/src/outer_sponge.rs:11-100) for the transcripts no fused call walks: a handle owns k
+ * sponges that advance in lockstep (every call applies one operation to all k, on different data; k = 1 is the
+ * ordinary sponge), their states in device memory between calls.  protocol: Protocols::{PCDL = 0, ASDL = 1,
+ * PLONK = 2, SIGNATURE = 3}, absorbed as the first element (Sponge::new).  A handle is an integer id that is never
+ * reused within a process; it belongs to the device that was current when it was made.  Arrays are (k, n)
+ * row-major: row i goes to / comes from sponge i.  Points are WrappedPoints (the identity is (0, 0); a point is
+ * absorbed as its two coordinates and is NOT checked to lie on the curve), scalars and base-field elements ark
+ * Montgomery words.  absorb_g is also the reference's absorb_g_affine.  n = 0 is a no-op, HALO_OK.
+ *
+ * Host forms: copy in, run on the library's stream and wait.  A scalar (absorb_fr) that is not below the scalar
+ * modulus, or a coordinate / element (absorb_g, absorb_fq) that is not below the base modulus, is HALO_EINVAL and
+ * leaves the handle's state as it was.
+ * _dev forms: device pointers, enqueued on `stream`, no host wait.  Their inputs are a precondition: a value that
+ * breaks it is reduced by the Montgomery multiplication, a defined result that is not the reference's.  Calls on
+ * one handle must be ordered by the caller (one stream, or events); halo_sponge_new has completed when it returns,
+ * and halo_sponge_reset / halo_sponge_free first wait for the device.
+ *
+ * halo_sponge_reset: Sponge::reset (outer_sponge.rs:97-99): the zero state, nothing absorbed, NO label.
+ * HALO_EINVAL, with the call's name in halo_last_error: protocol outside 0..3, k = 0, an id that was never made or
+ * has been freed, a null pointer with n > 0, Poseidon parameters not set for the curve's base field
+ * (halo_poseidon_set_params).  No GPU: HALO_EDEVICE. */
+int halo_sponge_new(halo_curve_t curve, int protocol, size_t k, uint64_t* id);
+int halo_sponge_free(uint64_t id);
+int halo_sponge_reset(uint64_t id);
+int halo_sponge_absorb_g(uint64_t id, const halo_wrapped_point_t* pts, size_t n);
+int halo_sponge_absorb_fr(uint64_t id, const halo_fe_t* xs, size_t n);
+int halo_sponge_absorb_fq(uint64_t id, const halo_fe_t* xs, size_t n);
+int halo_sponge_challenge(uint64_t id, size_t n, halo_fe_t* out);
+int halo_sponge_absorb_g_dev(uint64_t id, const void* d_pts, size_t n, void* stream);
+int halo_sponge_absorb_fr_dev(uint64_t id, const void* d_xs, size_t n, void* stream);
+int halo_sponge_absorb_fq_dev(uint64_t id, const void* d_xs, size_t n, void* stream);
+int halo_sponge_challenge_dev(uint64_t id, size_t n, void* d_out, void* stream);
+
 /* ------------------------------------------------------------------ measurement hooks
  * When enabled, the library brackets its dominant kernels (MSM bucket accumulation, NTT passes)
  * with hipEvents on the stream they run on; halo_profile_read returns the number of launches and
- * the summed kernel time in ms for a kernel name ("msm_acc", "ntt_pass") since the last reset. */
+ * the summed kernel time in ms for a kernel name ("msm_acc", "ntt_pass") since the last reset.
+ * One name counts no launches: under "sponge_permutations" `launches` is the number of Poseidon
+ * permutations the sponge handles ran (k per permutation of a handle of k), from the host's plan. */
 int halo_profile_enable(int on);
 int halo_profile_read(const char* name, size_t* launches, double* total_ms);
 int halo_profile_reset(void);

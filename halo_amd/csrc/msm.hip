@@ -29,6 +29,7 @@
 #include <vector>
 #include <cstdlib>
 
+#include "acc_entries.hpp"
 #include "digits.hpp"
 #include "dispatch.hpp"
 #include "glv.hpp"
@@ -121,8 +122,14 @@ __global__ void k_digits_glv(const uint4* scalars, size_t n, int c, int W, uint3
 // first segment's sum goes to first[t], its last segment's (when there are >= 2) to last[t], and the
 // buckets strictly inside the chunk are complete, so they go straight to bucket_sums.  k_merge then
 // completes the buckets that straddle chunk boundaries.
-// k_acc's register budget is sized for 4 workgroups per CU (the compiler's own allocation, 117 VGPRs
-// with the peeled second entry and the three-chain addition; 5 / 6 per CU measured slower).
+// The sorted keys and values come through a cursor (acc_entries.hpp) that loads them four entries at a
+// time, one 16-byte load per array at the chunk's start and at every multiple of four after it: the lanes
+// of a wave are K entries apart, so a 4-byte load per entry asked for a line per lane (per two lanes at
+// K = 16) and asked for it again for each of the line's other entries.  Only keys[beg - 1] is still a load
+// of its own.
+// k_acc's register budget is sized for 4 workgroups per CU (the compiler's own allocation, 124 VGPRs
+// with the peeled second entry, the three-chain addition and the cursor's two groups; 5 / 6 per CU
+// measured slower).
 constexpr int ACC_MIN_BLOCKS = 4;
 // npw_lg: log2 n_per_window when it is a power of two (the window of a shifted entry is a shift,
 // not a division), else 0xff.
@@ -143,7 +150,9 @@ __device__ __forceinline__ void acc_chunk(size_t t, uint32_t cnt, const uint32_t
         return;
     }
     const uint32_t end = (uint32_t)min((size_t)cnt, beg + K);
-    uint32_t cur = keys[beg];
+    AccEntries<> ent(keys, vals);
+    ent.start((uint32_t)beg);
+    uint32_t cur = ent.key((uint32_t)beg);
     // bucket starts (the tail's k_merge): bstart[b] = first sorted position of key b, for every b
     // whose first position (or, for empty buckets, the next bucket's) falls in this chunk
     {
@@ -160,7 +169,8 @@ __device__ __forceinline__ void acc_chunk(size_t t, uint32_t cnt, const uint32_t
     // first), 2 = any later one.
     auto step = [&](uint32_t e, auto pos) {
         constexpr int POS = decltype(pos)::value;
-        const uint32_t k = POS == 0 ? cur : keys[e];
+        if (POS != 0) ent.next(e);
+        const uint32_t k = POS == 0 ? cur : ent.key(e);
         if (POS != 0 && k != cur) {  // bucket boundary inside the chunk
             for (uint32_t b = cur + 1; b <= k; b++) bstart[b] = e;
             if (!first_done) {
@@ -174,7 +184,7 @@ __device__ __forceinline__ void acc_chunk(size_t t, uint32_t cnt, const uint32_t
             sneg = 0;
             cur = k;
         }
-        const uint32_t v = vals[e];
+        const uint32_t v = ent.val(e);
         size_t idx = v & 0x7fffffffu;
         if (stride) {  // window-shifted SRS: entry w * n_per_window + i -> point w * stride + i
             const uint32_t w = npw_lg < 32 ? (uint32_t)idx >> npw_lg : (uint32_t)idx / n_per_window;
@@ -436,6 +446,10 @@ struct AccArgs {
 };
 template <class Cv, class Scratch>
 static int acc_launch(const MsmPlan& p, Scratch& S, const AccArgs& a, hipStream_t s) {
+    // k_acc reads both arrays in 16-byte groups (acc_entries.hpp)
+    if ((((uintptr_t)a.keys | (uintptr_t)a.vals) & 15u) != 0)
+        return set_error(HALO_EINVAL, "k_acc: sorted keys / values not 16-byte aligned (%p, %p)", (const void*)a.keys,
+                         (const void*)a.vals);
     ProfScope prof(a.profiled ? "msm_acc" : nullptr, s);
     uint4* parts = S.partials.template as<uint4>();
     HALO_LAUNCH(prof, k_acc<Cv>, dim3(grid_for(p.nchunks, 256)), dim3(256), 0, s, a.keys, a.vals, a.count, p.K, a.bases,
@@ -985,8 +999,8 @@ static int msm_shared_batch_t(DeviceState* st, const uint4* bases, const uint4* 
     const MsmPlan pl = msm_plan(E, NB, (int)SW, B, c, st->num_cu, W, TS);
     HALO_CHECK(S.digits.reserve((size_t)(shifted ? W_s + W : W) * TS * 4));
     HALO_CHECK(S.lists.reserve((size_t)W * TS * 8 + 16));
-    HALO_CHECK(S.keys.reserve(E * 4));
-    HALO_CHECK(S.vals.reserve(E * 4));
+    HALO_CHECK(S.keys.reserve(acc_entries_bytes(E)));  // whole groups of four: k_acc's 16-byte loads
+    HALO_CHECK(S.vals.reserve(acc_entries_bytes(E)));
     HALO_CHECK(plan_reserve(S, pl, 0));
     uint32_t* ent = S.lists.as<uint32_t>();
     uint32_t* ekey = ent + (size_t)W * TS;

@@ -27,6 +27,7 @@
 #include <type_traits>
 #include <cstdlib>
 
+#include "acc_entries.hpp"
 #include "digits.hpp"
 #include "dispatch.hpp"
 #include "fields.hpp"
@@ -611,10 +612,12 @@ int msm_radix_sort(const uint32_t* digits, size_t E, size_t npw, uint32_t B, uin
                          fused->W, nsc);
     const uint32_t ntiles0 = fused ? (uint32_t)std::max<size_t>(1, (nsc + RS_THREADS - 1) / RS_THREADS) : 0u;
     ntmax = std::max(ntmax, ntiles0);
-    HALO_CHECK(S.keys[0].reserve(std::max<size_t>(E, 1) * 4));
-    HALO_CHECK(S.keys[1].reserve(std::max<size_t>(E, 1) * 4));
-    HALO_CHECK(S.vals[0].reserve(std::max<size_t>(E, 1) * 4));
-    HALO_CHECK(S.vals[1].reserve(std::max<size_t>(E, 1) * 4));
+    // whole groups of four entries: k_acc loads the sorted arrays 16 bytes at a time (acc_entries.hpp), and
+    // either buffer of a pair may end up as the sorted one
+    HALO_CHECK(S.keys[0].reserve(acc_entries_bytes(E)));
+    HALO_CHECK(S.keys[1].reserve(acc_entries_bytes(E)));
+    HALO_CHECK(S.vals[0].reserve(acc_entries_bytes(E)));
+    HALO_CHECK(S.vals[1].reserve(acc_entries_bytes(E)));
     HALO_CHECK(S.hist.reserve((size_t)RS_BINS_MAX * ntmax * 4));
     const size_t nchmax = (ntmax + RS_CH - 1) / RS_CH;
     HALO_CHECK(S.offs.reserve(nchmax * RS_BINS_MAX * 4));

@@ -11,7 +11,8 @@
 //    are device reductions whose results feed the MSM's hiding-term slot (k_final) directly, so a
 //    round never round-trips scalars through the host.
 //  * Here: the fold and weighted-round kernels, the session pool and the session entry points.  The
-//    session's declarations are in ipa_session.hpp, the tail rounds' multiples-table sums in tail.hip,
+//    session's declarations are in ipa_session.hpp, the choice of every round's and fold's path in ipa_plan.hpp
+//    (host-only: this file performs its records), the tail rounds' multiples-table sums in tail.hip,
 //    the dot products and powers in poly.hip, the hiding open's steps in pcdl_open.hip, the opening with its
 //    transcript on the device in pcdl_open_fs.hip.
 #include <algorithm>
@@ -424,7 +425,7 @@ void halo::ipa_release(halo_ipa_session* ses) {
         ses->in_use = false;
     }
     if (ses->s) (void)hipStreamSynchronize(ses->s);
-    ses->table_ref.reset();  // a retired SRS multiples table is freed with its last session
+    ses->op.table_ref.reset();  // a retired SRS multiples table is freed with its last session
     // an idle session keeps at most "ipa_pool_keep_bytes" of device buffers (tuning, default 1 GB: a
     // 2^20 opening's ~0.6 GB stay pooled for the next one): above it the per-size buffers
     // are released here
@@ -460,24 +461,36 @@ void halo::ipa_shutdown() {
 // Session start shared by halo_ipa_begin (G = resident SRS prefix, z powers generated on the
 // device) and halo_ipa_begin_vectors (explicit G, c, z: a shard of a distributed opening or its
 // final collapsed rounds, halo_amd/dist.py).
-static size_t ipa_tail_n() { return IPA_TAIL_N; }
 
-// SRS sessions of n <= this start in the tail rounds over the SRS's table.  A tail round costs ~64 n0
-// table terms: measured per round (hiding open, tools/pcdl_open_time.py) 0.23 ms at n0 = 4096 against
-// 0.29 ms for the weighted path's average (opening 2^12: 5.95 -> 3.86 ms), but 0.33 ms at n0 = 8192,
-// where the weighted rounds are cheaper.
-static size_t ipa_srs_tail_max() {  // tuning "ipa_srs_tail_n" (default 4096; the tests pin the other paths)
-    return std::min((size_t)tuning(TUNE_IPA_SRS_TAIL_N), srs_tab_n());
-}
-
-// Length at which weighted rounds materialise G = sum_u w[u] SRS[i + u len] (one batched MSM with
-// the fold weights as shared scalars, msm_shared_batch) and continue as tail rounds: a weighted
-// round costs two n/2-term MSMs whatever the length (~0.75 ms at 2^16), a tail round ~0.25 ms.
-// Measured (opening 2^12 / 2^16 / 2^20, ms): 1024: 6.2 / 10.4 / 29.3; 2048: 5.6 / 9.3 / 27.6;
-// 4096 (tail 4096): 6.5 / 10.7 / 27.4; 8192: 6.4 / 12.8 / 28.4.
-// (tuning "ipa_mat_n", default 2048)
-static size_t ipa_mat_n() {  // 0 keeps the weighted rounds to the end
-    return (size_t)tuning(TUNE_IPA_MAT_N);
+// What the session's plan (ipa_plan.hpp) is asked with: the constants, the SRS and the tunings as they are now
+// (a round reads "ipa_mat_n", "ipa_tail" and "ipa_pair_max" when it is launched).
+static IpaPlanConsts ipa_plan_consts() { return {IPA_TAIL_N, TAIL_FUSE_N}; }
+static IpaPlanSrs ipa_plan_srs(const SrsState& srs) { return {srs.n, srs.shifted_c != 0, srs_tab_n()}; }
+static IpaPlanTunings ipa_plan_tunings() {
+    IpaPlanTunings t;
+    // tuning "ipa_tail" / "ipa_weighted" (default 1): 0 = no tail rounds / fold G every round
+    t.tail = tuning(TUNE_IPA_TAIL) != 0;
+    t.weighted = tuning(TUNE_IPA_WEIGHTED) != 0;
+    // SRS sessions of n <= this start in the tail rounds over the SRS's table.  A tail round costs ~64 n0
+    // table terms: measured per round (hiding open, tools/pcdl_open_time.py) 0.23 ms at n0 = 4096 against
+    // 0.29 ms for the weighted path's average (opening 2^12: 5.95 -> 3.86 ms), but 0.33 ms at n0 = 8192,
+    // where the weighted rounds are cheaper.
+    // (tuning "ipa_srs_tail_n", default 4096; the tests pin the other paths)
+    t.srs_tail_n = (size_t)tuning(TUNE_IPA_SRS_TAIL_N);
+    // Length at which weighted rounds materialise G = sum_u w[u] SRS[i + u len] (one batched MSM with
+    // the fold weights as shared scalars, msm_shared_batch) and continue as tail rounds: a weighted
+    // round costs two n/2-term MSMs whatever the length (~0.75 ms at 2^16), a tail round ~0.25 ms.
+    // Measured (opening 2^12 / 2^16 / 2^20, ms): 1024: 6.2 / 10.4 / 29.3; 2048: 5.6 / 9.3 / 27.6;
+    // 4096 (tail 4096): 6.5 / 10.7 / 27.4; 8192: 6.4 / 12.8 / 28.4.
+    // (tuning "ipa_mat_n", default 2048; 0 keeps the weighted rounds to the end)
+    t.mat_n = (size_t)tuning(TUNE_IPA_MAT_N);
+    // L and R as one MSM (key = (side, bucket)) while the round is latency-bound; at 2^19 terms per
+    // side two MSMs win (R's front and accumulation overlap L's reduction tail).  Measured, opening
+    // 2^14 / 2^17 / 2^18 / 2^19 / 2^20 ms, two MSMs vs one: 7.5 / 11.3 / 14.4 / 19.3 / 27.2 vs
+    // 6.9 / 10.3 / 13.2 / 17.8 / 29.0 (round 4, after the sort and accumulation changes: 2^20
+    // 21.7 vs 22.7 ms)
+    t.pair_max = (size_t)tuning(TUNE_IPA_PAIR_MAX);
+    return t;
 }
 
 // The 2^i H tables (i < IPA_HTAB, internal affine) of xi-mode sessions, kept per device and curve,
@@ -522,34 +535,20 @@ static int ipa_h_table(DeviceState* st, int curve, const halo_wrapped_point_t* H
 int halo::ipa_setup(DeviceState* st, halo_ipa_session* ses, int curve, size_t n, const halo_wrapped_point_t* gs_host,
                     const halo_fe_t* cs, size_t cs_len, bool cs_on_device, const halo_fe_t* zs_host, const halo_fe_t* z) {
     SrsState& srs = st->srs[curve];
-    ses->curve = curve;
-    {
-        // tuning "ipa_tail" / "ipa_weighted" (default 1): 0 = no tail rounds / fold G every round
-        ses->allow_tail = !gs_host && tuning(TUNE_IPA_TAIL) != 0;
-        ses->tail_from_srs = ses->allow_tail && n <= std::min(ipa_srs_tail_max(), srs.n);
-        ses->weighted = !gs_host && srs.shifted_c != 0 && n > ipa_tail_n() && !ses->tail_from_srs &&
-                        tuning(TUNE_IPA_WEIGHTED) != 0;
-        if (ses->weighted) ses->allow_tail = false;
-        ses->srs_round0 = !gs_host && srs.shifted_c != 0 && !ses->weighted;
-        ses->gs_srs_prefix = !gs_host && !ses->weighted;
-    }
-    ses->n = n;
-    ses->m = n / 2;
+    ses->op.curve = curve;
+    ses->op.n = n;
+    const IpaBegin b = ipa_plan_begin({n, gs_host != nullptr}, ipa_plan_srs(srs), ipa_plan_tunings(), ipa_plan_consts());
+    ses->op.g = b.plan;
     hipStream_t s = ses->s;
-    // an SRS session that starts in the tail rounds never reads G itself (the SRS's table does)
-    const bool need_gs = !ses->weighted && !(ses->gs_srs_prefix && ses->allow_tail && (n <= ipa_tail_n() || ses->tail_from_srs));
-    if (need_gs || gs_host) HALO_CHECK(ses->gs.reserve(n * 64));
-    ses->gs_valid = need_gs || gs_host;
-    if (ses->weighted) {  // w = [1]; scal holds the two n/2-term scalar vectors of a round
+    if (b.copy_gs) HALO_CHECK(ses->gs.reserve(n * 64));
+    if (ses->op.weighted()) {  // w = [1]; scal holds the two n/2-term scalar vectors of a round
         HALO_CHECK(ses->w[0].reserve(n * 32));
         HALO_CHECK(ses->w[1].reserve(n * 32));
         HALO_CHECK(ses->scal.reserve(n * 32));
         DISPATCH_CURVE(curve, Cv, {
             hipLaunchKernelGGL(k_set_one_ark<typename Cv::Scalar>, dim3(1), dim3(64), 0, s, ses->w[0].as<uint4>());
         });
-        ses->n0 = n;
-        ses->wlen = 1;
-        ses->wcur = 0;
+        ses->op.wcur = 0;
     }
     HALO_CHECK(ses->cs.reserve(n * 32));
     HALO_CHECK(ses->zs.reserve(n * 32));
@@ -560,7 +559,7 @@ int halo::ipa_setup(DeviceState* st, halo_ipa_session* ses, int curve, size_t n,
     if (gs_host) {
         HALO_CHECK(copy_h2d(ses->tmp.ptr, gs_host, n * 64, s));
         HALO_CHECK(convert_wrapped_to_internal(curve, ses->tmp.ptr, ses->gs.ptr, n, s));
-    } else if (need_gs) {
+    } else if (b.copy_gs) {
         HALO_HIP(hipMemcpyAsync(ses->gs.ptr, srs.gs.ptr, n * 64, hipMemcpyDeviceToDevice, s));
     }
     if (cs_len < n) HALO_HIP(hipMemsetAsync(ses->cs.as<char>() + cs_len * 32, 0, (n - cs_len) * 32, s));
@@ -585,14 +584,13 @@ int halo::ipa_setup(DeviceState* st, halo_ipa_session* ses, int curve, size_t n,
 }
 
 // G of a session that skipped its copy of the SRS prefix (ipa_setup: it was to start in the tail
-// rounds) but folds G before any round ran (pcdl.rs:627-687 test_u_check drives folds only).
-static int ipa_ensure_gs(DeviceState* st, halo_ipa_session* ses) {
-    if (ses->gs_valid) return HALO_OK;
-    if (!ses->gs_srs_prefix) return set_error(HALO_EINVAL, "ipa: G is not resident");
-    const size_t len = 2 * ses->m;
-    HALO_CHECK(ses->gs.reserve(ses->n * 64));
-    HALO_HIP(hipMemcpyAsync(ses->gs.ptr, st->srs[ses->curve].gs.ptr, len * 64, hipMemcpyDeviceToDevice, ses->s));
-    ses->gs_valid = true;
+// rounds) but folds G before any round ran (pcdl.rs:627-687 test_u_check drives folds only), or builds its
+// own tail table: the plan's fetch_gs.  G is still the prefix of length 2m.
+static int ipa_fetch_gs(DeviceState* st, halo_ipa_session* ses) {
+    const size_t len = 2 * ses->op.g.m;
+    HALO_CHECK(ses->gs.reserve(ses->op.n * 64));
+    HALO_HIP(hipMemcpyAsync(ses->gs.ptr, st->srs[ses->op.curve].gs.ptr, len * 64, hipMemcpyDeviceToDevice, ses->s));
+    ses->op.g.gs_current = true;
     return HALO_OK;
 }
 
@@ -602,32 +600,32 @@ int halo::ipa_start(DeviceState* st, halo_ipa_session* ses, const halo_wrapped_p
                     const halo_wrapped_point_t* Hpt, bool xi0_resident) {
     hipStream_t s = ses->s;
     char* sm = (char*)ses->small.ptr;
-    ses->xi_mode = xi0 != nullptr || xi0_resident;
+    ses->op.xi_mode = xi0 != nullptr || xi0_resident;
     const halo_wrapped_point_t* own = H_prime;  // the point of a per-session table, if one is needed
-    if (ses->xi_mode) {  // xi_0 at [192, 224)
-        HALO_CHECK(ipa_h_table(st, ses->curve, Hpt, &ses->htab_ptr));
+    if (ses->op.xi_mode) {  // xi_0 at [192, 224)
+        HALO_CHECK(ipa_h_table(st, ses->op.curve, Hpt, &ses->op.htab_ptr));
         if (!xi0_resident) HALO_CHECK(copy_h2d(sm + SM_XI0, xi0, 32, s));
-        own = ses->htab_ptr ? nullptr : Hpt;
+        own = ses->op.htab_ptr ? nullptr : Hpt;
     }
-    ses->started = true;
+    ses->op.started = true;
     if (!own) {
-        ses->htab_waited = true;
+        ses->op.htab_waited = true;
         return HALO_OK;
     }
     HALO_CHECK(ses->htab.reserve(IPA_HTAB * (64 + 128)));  // affine table + XYZZ chain scratch
-    ses->htab_ptr = ses->htab.ptr;
+    ses->op.htab_ptr = ses->htab.ptr;
     HALO_CHECK(copy_h2d(sm + SM_HP, own, 64, s));
     // 2^i H' for i < 128 (the hiding terms use the GLV split of their scalar, k_hide_term): a
     // quad-cooperative doubling chain on the session's stream; the hiding-term kernels wait for htab_ready
     const hipStream_t hs = s;
     uint4* chain = ses->htab.as<uint4>() + 4 * IPA_HTAB;  // XYZZ scratch after the affine table
-    DISPATCH_CURVE(ses->curve, Cv, {
+    DISPATCH_CURVE(ses->op.curve, Cv, {
         hipLaunchKernelGGL(k_pow2_xyzz_from_wrapped<Cv>, dim3(1), dim3(64), 0, hs, (const uint4*)(sm + SM_HP), chain, IPA_HTAB);
     });
     HALO_HIP(hipGetLastError());
-    HALO_CHECK(xyzz_to_affine_device(ses->curve, chain, ses->htab.ptr, IPA_HTAB, hs));
+    HALO_CHECK(xyzz_to_affine_device(ses->op.curve, chain, ses->htab.ptr, IPA_HTAB, hs));
     HALO_HIP(hipEventRecord(ses->htab_ready, hs));
-    ses->htab_waited = false;
+    ses->op.htab_waited = false;
     return HALO_OK;
 }
 
@@ -705,7 +703,7 @@ int halo::ipa_eval_cs_enqueue(halo_ipa_session* ses, size_t len) {
         return HALO_OK;
     }
     HALO_CHECK(ses->tmp.reserve(4096 * 32));  // dot_device: at most 1024 block partials
-    const int sf = ses->curve == HALO_PALLAS ? HALO_FP : HALO_FQ;
+    const int sf = ses->op.curve == HALO_PALLAS ? HALO_FP : HALO_FQ;
     return dot_device(sf, ses->cs.ptr, ses->zs.ptr, len, sm + SM_V, ses->tmp.ptr, s);
 }
 
@@ -726,9 +724,9 @@ int halo::ipa_eval_cs(halo_ipa_session* ses, size_t len, halo_fe_t* v_out) {
 // Switch to the tail rounds: G0 = current G (length 2m), w = [1], and the multiples table of G0:
 // the SRS's own table when G0 is still the SRS prefix (a session of n <= IPA_TAIL_N over the SRS:
 // the reference's small pcdl_open shapes, benches/pcdl.rs:35-57), else built for the session.
-static int ipa_enter_tail(DeviceState* st, halo_ipa_session* ses, hipStream_t s) {
-    const size_t n0 = 2 * ses->m;
-    // the largest grid of a later round: one term per lane (+ mode 0's per-side rounding)
+static int ipa_enter_tail(DeviceState* st, halo_ipa_session* ses, const IpaRound& r, hipStream_t s) {
+    const size_t n0 = 2 * ses->op.g.m;
+    // the largest grid of a later round: one term per lane (+ a round's per-side rounding)
     const size_t nblk = tail_blocks_at(TAIL_WIN * n0, 1) + 2;
     HALO_CHECK(ses->w[0].reserve(n0 * 32));
     HALO_CHECK(ses->w[1].reserve(n0 * 32));
@@ -737,120 +735,119 @@ static int ipa_enter_tail(DeviceState* st, halo_ipa_session* ses, hipStream_t s)
     HALO_CHECK(ses->scal.reserve(n0 * 32));
     HALO_CHECK(ses->side.reserve(n0));
     HALO_CHECK(ses->part.reserve(nblk * 2 * 128));
-    SrsState& srs = st->srs[ses->curve];
-    if (ses->gs_srs_prefix && n0 <= std::min(srs_tab_n(), srs.n)) {
-        HALO_CHECK(srs_small_table(st, ses->curve, s));
-        ses->table_ref = srs.small_tab;  // an SRS write rebuilds into a fresh buffer while this is held
-        ses->table = srs.small_tab->as<const uint4>();
-        ses->table_ld = srs.small_n0;
+    SrsState& srs = st->srs[ses->op.curve];
+    if (r.tail_srs_table) {
+        HALO_CHECK(srs_small_table(st, ses->op.curve, s));
+        ses->op.table_ref = srs.small_tab;  // an SRS write rebuilds into a fresh buffer while this is held
+        ses->op.table = srs.small_tab->as<const uint4>();
+        ses->op.table_ld = srs.small_n0;
     } else {
-        // a session that skipped its copy of the SRS prefix (ipa_setup: need_gs) but builds its own
-        // table here (the SRS table is off or shorter than n0) copies the prefix now
-        HALO_CHECK(ipa_ensure_gs(st, ses));
+        // a session that skipped its copy of the SRS prefix at setup but builds its own table here (the SRS
+        // table is off or shorter than n0) copies the prefix now
+        if (r.tail_fetch_gs) HALO_CHECK(ipa_fetch_gs(st, ses));
         HALO_CHECK(ses->own_table.reserve((size_t)TAIL_TBL * TAIL_MUL * n0 * 128));
-        HALO_CHECK(tail_table_build(ses->curve, ses->gs.ptr, ses->gs_xyzz, n0, ses->own_table.ptr, s));
-        ses->table = ses->own_table.as<const uint4>();
-        ses->table_ld = n0;
+        HALO_CHECK(tail_table_build(ses->op.curve, ses->gs.ptr, r.plan.gs_xyzz, n0, ses->own_table.ptr, s));
+        ses->op.table = ses->own_table.as<const uint4>();
+        ses->op.table_ld = n0;
     }
     // w = [1]: the next round's first launch uses 1 and stores it (TailFoldArgs::w_one), no launch here
-    ses->w_one_pending = true;
-    ses->n0 = n0;
-    ses->wlen = 1;
-    ses->wcur = 0;
-    ses->tail = true;
+    ses->op.w_one_pending = true;
+    ses->op.wcur = 0;
     return HALO_OK;
 }
 
-// mode 0: L, R of the current round (with their dot * H' terms) -> small[512..768) as XYZZ; the round's
+// A tail round: L, R of the current round (with their dot * H' terms) -> small[512..768) as XYZZ; the round's
 // scalars and dots come from k_tail_prep (one launch), the hiding terms ride in each side's first
-// k_tail_msm block, and k_tail_final runs only when a side spans several blocks.
-// mode 1: U = sum_u w[u] G0[u] -> small[256..384) as XYZZ (converted on the host).
-static int ipa_tail_sums(const DeviceState* st, halo_ipa_session* ses, int mode, hipStream_t s, const void* copy_src = nullptr,
-                         void* copy_dst = nullptr) {
-    const size_t n0 = ses->n0, m = ses->m;
+// k_tail_msm block, and k_tail_final runs only when a side spans several blocks.  L and R reach `pinned`
+// from the kernels: no copy.
+static int ipa_round_tail(const DeviceState* st, halo_ipa_session* ses, IpaRoundKind kind, hipStream_t s) {
+    const size_t n0 = ses->op.g.n0, m = ses->op.g.m;
     char* sm = (char*)ses->small.ptr;
-    if (mode == 0) {  // one fused launch (k_tail_round) up to TAIL_FUSE_N points, three above
-        TailFoldArgs f{};
-        f.active = ses->fold_pending;
-        if (ses->w_one_pending) {  // (no fold is pending right after the switch to the tail rounds)
-            f.w_one = ses->w[ses->wcur].as<uint4>();
-            ses->w_one_pending = false;
-        }
-        if (f.active) {  // the previous round's fold, applied here (halo_ipa_fold deferred it)
-            memcpy(&f.xi, &ses->pend_xi, 32);
-            memcpy(&f.xinv, &ses->pend_xinv, 32);
-            if (ses->xi_dev) f.xi_dev = (const uint4*)(sm + SM_XI);
-            f.cs_out = ses->cs2.as<uint4>();
-            f.zs_out = ses->zs2.as<uint4>();
-            f.w_out = ses->w[ses->wcur ^ 1].as<uint4>();
-            f.wlen_in = ses->wlen;
-        }
-        TailRoundArgs ra{};
-        ra.table = ses->table;
-        ra.ld = ses->table_ld;
-        ra.n0 = n0;
-        ra.m = m;
-        ra.cs = ses->cs.as<const uint4>();
-        ra.zs = ses->zs.as<const uint4>();
-        ra.w = ses->w[ses->wcur].as<const uint4>();
-        ra.nbs = (uint32_t)((n0 / 2 + TAIL_THREADS / 64 - 1) / (TAIL_THREADS / 64));
-        ra.xi0_ark = ses->xi_mode ? (const uint4*)(sm + SM_XI0) : nullptr;
-        ra.htab = (const uint4*)ses->htab_ptr;
-        ra.dots_ark = (uint4*)(sm + SM_DOT_L);
-        ra.part = ses->part.as<uint4>();
-        ra.ctr = (uint32_t*)(sm + SM_CTR);
-        ra.out_xyzz = (uint4*)(sm + SM_L);
-        ra.host = (uint32_t*)(ses->pinned + PIN_L);
-        ra.seq = ++ses->poll_seq;
-        if (ra.seq == 0) ra.seq = ++ses->poll_seq;  // (0 is the flags' initial value)
-        ses->poll_pending = true;
-        if (n0 <= TAIL_FUSE_N) {
-            HALO_CHECK(tail_round_launch(ses->curve, ra, f, s));
-        } else {  // k_tail_digits (the point scalars and the dots) + k_tail_msm + k_tail_final
-            uint32_t* hkw = (uint32_t*)(sm + SM_HKW);
-            HALO_CHECK(tail_digits_launch(ses->curve, ra, f, ses->scal.as<uint32_t>(), ses->side.as<uint8_t>(), hkw, s));
-            TailSums a;
-            a.table = ses->table;
-            a.ld = ses->table_ld;
-            a.scal = ses->scal.as<const uint32_t>();
-            a.side = ses->side.as<const uint8_t>();
-            a.n0 = n0;
-            a.m = m;
-            a.mode = 0;
-            a.blk = tail_blocks(st, TAIL_WIN * (n0 / 2), 2);  // per side: the grid is 2 blk.nblk blocks
-            a.part = ses->part.as<uint4>();
-            a.htab = ra.htab;
-            a.hide_scalar = ra.dots_ark;
-            a.hkw = hkw;
-            a.out = a.out_direct = ra.out_xyzz;
-            a.host = ra.host;
-            a.seq = ra.seq;
-            HALO_CHECK(tail_sums(ses->curve, a, a.blk.nblk > 1, s));  // a one-block side wrote its sum itself
-        }
-        if (f.active) {
-            std::swap(ses->cs.ptr, ses->cs2.ptr);
-            std::swap(ses->cs.bytes, ses->cs2.bytes);
-            std::swap(ses->zs.ptr, ses->zs2.ptr);
-            std::swap(ses->zs.bytes, ses->zs2.bytes);
-            ses->wcur ^= 1;
-            ses->wlen *= 2;
-            ses->fold_pending = false;
-        }
-        return HALO_OK;
+    TailFoldArgs f{};
+    f.active = ses->op.fold_pending;
+    if (ses->op.w_one_pending) {  // (no fold is pending right after the switch to the tail rounds)
+        f.w_one = ses->w[ses->op.wcur].as<uint4>();
+        ses->op.w_one_pending = false;
     }
-    // mode 1: U = sum_u w[u] G0[u]
-    if (ses->w_one_pending) {
-        DISPATCH_CURVE(ses->curve, Cv, {
-            hipLaunchKernelGGL(k_set_one_ark<typename Cv::Scalar>, dim3(1), dim3(64), 0, s, ses->w[ses->wcur].as<uint4>());
+    if (f.active) {  // the previous round's fold, applied here (halo_ipa_fold deferred it)
+        memcpy(&f.xi, &ses->op.pend_xi, 32);
+        memcpy(&f.xinv, &ses->op.pend_xinv, 32);
+        if (ses->op.xi_dev) f.xi_dev = (const uint4*)(sm + SM_XI);
+        f.cs_out = ses->cs2.as<uint4>();
+        f.zs_out = ses->zs2.as<uint4>();
+        f.w_out = ses->w[ses->op.wcur ^ 1].as<uint4>();
+        f.wlen_in = ses->op.g.wlen / 2;  // (the plan's wlen counts the pending fold)
+    }
+    TailRoundArgs ra{};
+    ra.table = ses->op.table;
+    ra.ld = ses->op.table_ld;
+    ra.n0 = n0;
+    ra.m = m;
+    ra.cs = ses->cs.as<const uint4>();
+    ra.zs = ses->zs.as<const uint4>();
+    ra.w = ses->w[ses->op.wcur].as<const uint4>();
+    ra.nbs = (uint32_t)((n0 / 2 + TAIL_THREADS / 64 - 1) / (TAIL_THREADS / 64));
+    ra.xi0_ark = ses->op.xi_mode ? (const uint4*)(sm + SM_XI0) : nullptr;
+    ra.htab = (const uint4*)ses->op.htab_ptr;
+    ra.dots_ark = (uint4*)(sm + SM_DOT_L);
+    ra.part = ses->part.as<uint4>();
+    ra.ctr = (uint32_t*)(sm + SM_CTR);
+    ra.out_xyzz = (uint4*)(sm + SM_L);
+    ra.host = (uint32_t*)(ses->pinned + PIN_L);
+    ra.seq = ++ses->poll_seq;
+    if (ra.seq == 0) ra.seq = ++ses->poll_seq;  // (0 is the flags' initial value)
+    ses->poll_pending = true;
+    if (kind == IpaRoundKind::TailFused) {  // one fused launch (k_tail_round) up to TAIL_FUSE_N points
+        HALO_CHECK(tail_round_launch(ses->op.curve, ra, f, s));
+    } else {  // k_tail_digits (the point scalars and the dots) + k_tail_msm + k_tail_final
+        uint32_t* hkw = (uint32_t*)(sm + SM_HKW);
+        HALO_CHECK(tail_digits_launch(ses->op.curve, ra, f, ses->scal.as<uint32_t>(), ses->side.as<uint8_t>(), hkw, s));
+        TailSums a;
+        a.table = ses->op.table;
+        a.ld = ses->op.table_ld;
+        a.scal = ses->scal.as<const uint32_t>();
+        a.side = ses->side.as<const uint8_t>();
+        a.n0 = n0;
+        a.m = m;
+        a.mode = 0;
+        a.blk = tail_blocks(st, TAIL_WIN * (n0 / 2), 2);  // per side: the grid is 2 blk.nblk blocks
+        a.part = ses->part.as<uint4>();
+        a.htab = ra.htab;
+        a.hide_scalar = ra.dots_ark;
+        a.hkw = hkw;
+        a.out = a.out_direct = ra.out_xyzz;
+        a.host = ra.host;
+        a.seq = ra.seq;
+        HALO_CHECK(tail_sums(ses->op.curve, a, a.blk.nblk > 1, s));  // a one-block side wrote its sum itself
+    }
+    if (f.active) {
+        std::swap(ses->cs.ptr, ses->cs2.ptr);
+        std::swap(ses->cs.bytes, ses->cs2.bytes);
+        std::swap(ses->zs.ptr, ses->zs2.ptr);
+        std::swap(ses->zs.bytes, ses->zs2.bytes);
+        ses->op.wcur ^= 1;
+        ses->op.fold_pending = false;
+    }
+    return HALO_OK;
+}
+
+// U = sum_u w[u] G0[u] after the last tail round -> small[256..384) as XYZZ (converted on the host)
+static int ipa_tail_u(const DeviceState* st, halo_ipa_session* ses, hipStream_t s, const void* copy_src, void* copy_dst) {
+    const size_t n0 = ses->op.g.n0, m = ses->op.g.m;
+    char* sm = (char*)ses->small.ptr;
+    if (ses->op.w_one_pending) {
+        DISPATCH_CURVE(ses->op.curve, Cv, {
+            hipLaunchKernelGGL(k_set_one_ark<typename Cv::Scalar>, dim3(1), dim3(64), 0, s,
+                               ses->w[ses->op.wcur].as<uint4>());
         });
         HALO_HIP(hipGetLastError());
-        ses->w_one_pending = false;
+        ses->op.w_one_pending = false;
     }
-    HALO_CHECK(tail_scalars_launch(ses->curve, ses->cs.ptr, ses->w[ses->wcur].ptr, n0, 2 * m, m, 1, ses->scal.as<uint32_t>(),
-                                   ses->side.as<uint8_t>(), s));
+    HALO_CHECK(tail_scalars_launch(ses->op.curve, ses->cs.ptr, ses->w[ses->op.wcur].ptr, n0, 2 * m, m, 1,
+                                   ses->scal.as<uint32_t>(), ses->side.as<uint8_t>(), s));
     TailSums a;
-    a.table = ses->table;
-    a.ld = ses->table_ld;
+    a.table = ses->op.table;
+    a.ld = ses->op.table_ld;
     a.scal = ses->scal.as<const uint32_t>();
     a.side = ses->side.as<const uint8_t>();
     a.n0 = n0;
@@ -860,7 +857,7 @@ static int ipa_tail_sums(const DeviceState* st, halo_ipa_session* ses, int mode,
     a.out = a.out_direct = (uint4*)(sm + SM_U);
     a.copy_src = (const uint4*)copy_src;
     a.copy_dst = (uint4*)copy_dst;
-    return tail_sums(ses->curve, a, a.blk.nblk > 1, s);  // one block wrote U itself
+    return tail_sums(ses->op.curve, a, a.blk.nblk > 1, s);  // one block wrote U itself
 }
 
 static int ipa_copy_out(halo_ipa_session* ses) {
@@ -869,218 +866,205 @@ static int ipa_copy_out(halo_ipa_session* ses) {
     return HALO_OK;
 }
 
-// Enqueues one round's L and R (with their H' terms) and their D2H copy into ses->pinned.
-int halo::ipa_round_launch(DeviceState* st, halo_ipa_session* ses) {
-    if (ses->m == 0) return set_error(HALO_EINVAL, "halo_ipa_round_lr: no rounds left");
-    if (!ses->started) return set_error(HALO_EINVAL, "halo_ipa_round_lr: session not started (halo_pcdl_open_start)");
-    hipStream_t s = ses->s;
-    const size_t m = ses->m;
-    const int sf = ses->curve == HALO_PALLAS ? HALO_FP : HALO_FQ;
-    char* sm = (char*)ses->small.ptr;  // [0,32) z, [64,128) H', [128,192) dots, [256,384) U|c, [512,768) L|R XYZZ
+// G (length 2m) = sum_u w[u] SRS[i + u 2m] of a weighted session into gs (XYZZ for the tail table, else affine):
+// from here on an ordinary session
+static int ipa_materialise_g(DeviceState* st, halo_ipa_session* ses, bool xyzz, hipStream_t s) {
+    const size_t len = 2 * ses->op.g.m;
+    HALO_CHECK(ses->gs.reserve(len * 128));
+    // over the window-shifted copies (three-window Horner) when they are resident
+    const SrsState& srs = st->srs[ses->op.curve];
+    const bool sh = srs.shifted_c != 0;
+    return msm_shared_batch(st, ses->op.curve, sh ? srs.shifted.ptr : srs.gs.ptr, ses->w[ses->op.wcur].ptr, ses->op.g.wlen,
+                            len, ses->gs.ptr, xyzz, ses->mat, s, sh ? srs.n : 0, sh ? srs.shifted_c : 0);
+}
+
+// A weighted round: the round's weighted scalars (k_weighted_prep without its dot blocks) on s, and in the pair
+// path its two dots (scaled by xi_0) on the MSM's tail stream just before the hiding terms that read them
+// (MsmPreHide), beside the digit / sort / accumulation phase
+static int ipa_round_weighted(DeviceState* st, halo_ipa_session* ses, IpaRoundKind kind, hipEvent_t hr, hipStream_t s) {
+    const size_t m = ses->op.g.m, wlen = ses->op.g.wlen;
+    const int curve = ses->op.curve;
+    const void* htab = ses->op.htab_ptr;
+    char* sm = (char*)ses->small.ptr;
     const char* cs = ses->cs.as<const char>();
     const char* zs = ses->zs.as<const char>();
-    if (ses->weighted && 2 * m <= ipa_mat_n()) {
-        // G (length 2m) = sum_u w[u] SRS[i + u 2m]: from here on an ordinary (tail) session
-        ses->allow_tail = tuning(TUNE_IPA_TAIL) != 0;
-        const bool to_tail = ses->allow_tail && 2 * m <= ipa_tail_n();  // the tail table reads XYZZ directly
-        HALO_CHECK(ses->gs.reserve(2 * m * 128));
-        // over the window-shifted copies (three-window Horner) when they are resident
-        const SrsState& srs = st->srs[ses->curve];
-        const bool sh = srs.shifted_c != 0;
-        HALO_CHECK(msm_shared_batch(st, ses->curve, sh ? srs.shifted.ptr : srs.gs.ptr, ses->w[ses->wcur].ptr,
-                                    ses->wlen, 2 * m, ses->gs.ptr, to_tail, ses->mat, s, sh ? srs.n : 0,
-                                    sh ? srs.shifted_c : 0));
-        ses->gs_xyzz = to_tail;
-        ses->gs_valid = true;
-        ses->gs_srs_prefix = false;
-        ses->weighted = false;
+    const size_t half = ses->op.g.n0 / 2;  // = wlen * m terms per side
+    const uint32_t lgm = ilog2(m);
+    const char* sl = cs + m * 32;  // round 0 (w = [1]): the scalars are c_r, c_l themselves
+    const char* sr = cs;
+    char* sb = (char*)ses->scal.ptr;
+    const unsigned nbk = grid_for(half, 256), ndot = std::min(nbk, 256u);
+    HALO_CHECK(ses->tmp.reserve((size_t)ndot * 64));
+    const bool pair = kind == IpaRoundKind::WeightedPair;
+    WeightedDots wd{(const uint4*)cs, (const uint4*)zs, m, ses->tmp.as<uint4>(), (uint32_t*)(sm + SM_CTR + 8),
+                    ses->op.xi_mode ? (const uint4*)(sm + SM_XI0) : nullptr, (uint4*)(sm + SM_DOT_L), ndot, curve};
+    if (wlen > 1 || !pair) {
+        DISPATCH_CURVE(curve, Cv, {
+            hipLaunchKernelGGL(k_weighted_prep<typename Cv::Scalar>, dim3(wlen > 1 ? nbk : ndot), dim3(256), 0, s,
+                               (const uint4*)cs, (const uint4*)zs, ses->w[ses->op.wcur].as<const uint4>(), m, (int)lgm,
+                               half, wlen > 1 ? (uint4*)sb : nullptr, (uint4*)(sb + half * 32), wd.part, wd.ctr, wd.xi0,
+                               wd.dots, pair ? 0u : ndot);
+        });
+        HALO_HIP(hipGetLastError());
     }
-    if (!ses->tail && ses->allow_tail && (2 * m <= ipa_tail_n() || ses->tail_from_srs)) HALO_CHECK(ipa_enter_tail(st, ses, s));
-    const char* gs = ses->gs.as<const char>();  // (materialised above in a weighted session)
-    // only round 1 orders its hiding terms after the side-stream table: every later round starts after
-    // the host has synchronised on round 1's results, which needed the table (a cross-stream wait in
-    // every round cost ~0.3 ms per 2^16 round)
-    hipEvent_t hr = ses->htab_waited ? nullptr : ses->htab_ready;
-    ses->htab_waited = true;
-    if (ses->tail) {  // k_tail_prep forms the dots (scaled by xi_0) with the round's scalars
-        if (hr) HALO_HIP(hipStreamWaitEvent(s, hr, 0));
-        HALO_CHECK(ipa_tail_sums(st, ses, 0, s));  // (L and R reach `pinned` from the kernels: no copy)
+    if (wlen > 1) {
+        sl = sb;
+        sr = sb + half * 32;
+    }
+    // (the two-MSM form: the even half-blocks of 2^lgm points, dot H' from the GLV table, L / R as XYZZ)
+    const MsmOpts blocks = MsmOpts::Async().blocks(lgm).glv_hide().xyzz().after(hr);
+    if (pair) {
+        // L and R reach `pinned` from k_bitcombine itself (polled, as the tail rounds): no copy
+        const MsmPairIO io{sl, sr, sm + SM_DOT_L, sm + SM_DOT_R, sm + SM_L, sm + SM_R};
+        const MsmPreHide pre{weighted_dots_launch, &wd};
+        uint32_t seq = ++ses->poll_seq;
+        if (seq == 0) seq = ++ses->poll_seq;  // (0 is the flags' initial value)
+        HALO_CHECK(msm_srs_pairs_device(st, curve, 1, &io, half, lgm, htab, s, hr, &pre,
+                                        (uint32_t*)(ses->pinned + PIN_L), seq));
+        HALO_CHECK(msm_join(st, s));
+        ses->poll_pending = true;
         return HALO_OK;
     }
-    if (ses->weighted) {
-        // the round's weighted scalars (k_weighted_prep without its dot blocks) on s, and in the pair path
-        // its two dots (scaled by xi_0) on the MSM's tail stream just before the hiding terms that read
-        // them (MsmPreHide), beside the digit / sort / accumulation phase
-        const size_t half = ses->n0 / 2;  // = wlen * m terms per side
-        const uint32_t lgm = ilog2(m);
-        const char* sl = cs + m * 32;     // round 0 (w = [1]): the scalars are c_r, c_l themselves
-        const char* sr = cs;
-        char* sb = (char*)ses->scal.ptr;
-        const unsigned nbk = grid_for(half, 256), ndot = std::min(nbk, 256u);
-        HALO_CHECK(ses->tmp.reserve((size_t)ndot * 64));
-        const bool pair = half <= (size_t)tuning(TUNE_IPA_PAIR_MAX);
-        WeightedDots wd{(const uint4*)cs, (const uint4*)zs, m, ses->tmp.as<uint4>(), (uint32_t*)(sm + SM_CTR + 8),
-                        ses->xi_mode ? (const uint4*)(sm + SM_XI0) : nullptr, (uint4*)(sm + SM_DOT_L), ndot, ses->curve};
-        if (ses->wlen > 1 || !pair) {
-            DISPATCH_CURVE(ses->curve, Cv, {
-                hipLaunchKernelGGL(k_weighted_prep<typename Cv::Scalar>, dim3(ses->wlen > 1 ? nbk : ndot), dim3(256), 0,
-                                   s, (const uint4*)cs, (const uint4*)zs, ses->w[ses->wcur].as<const uint4>(), m,
-                                   (int)lgm, half, ses->wlen > 1 ? (uint4*)sb : nullptr, (uint4*)(sb + half * 32),
-                                   wd.part, wd.ctr, wd.xi0, wd.dots, pair ? 0u : ndot);
-            });
-            HALO_HIP(hipGetLastError());
+    if (kind == IpaRoundKind::WeightedTwoStreams) {
+        // L on the session stream and R on its second stream: the two MSMs' fronts, accumulations and
+        // reduction tails overlap, instead of R's front waiting for L's accumulation (measured, 2^20
+        // opening 20.5-20.8 -> 19.7-19.9 ms; with k sessions in lockstep their streams already overlap,
+        // and 2k streams over the default 4 hardware queues made the prover's three openings ~2 ms
+        // slower, so lockstep rounds keep one stream per session)
+        if (!ses->s2) {
+            HALO_HIP(hipStreamCreateWithFlags(&ses->s2, hipStreamNonBlocking));
+            HALO_HIP(hipEventCreateWithFlags(&ses->ev_fork, hipEventDisableTiming));
+            HALO_HIP(hipEventCreateWithFlags(&ses->ev_join, hipEventDisableTiming));
         }
-        if (ses->wlen > 1) {
-            sl = sb;
-            sr = sb + half * 32;
+        if (!ses->op.slots_reset) {
+            msm_slots_reset(st);
+            ses->op.slots_reset = true;
         }
-        // L and R as one MSM (key = (side, bucket)) while the round is latency-bound; at 2^19 terms per
-        // side two MSMs win (R's front and accumulation overlap L's reduction tail).  Measured, opening
-        // 2^14 / 2^17 / 2^18 / 2^19 / 2^20 ms, two MSMs vs one: 7.5 / 11.3 / 14.4 / 19.3 / 27.2 vs
-        // 6.9 / 10.3 / 13.2 / 17.8 / 29.0 (round 4, after the sort and accumulation changes: 2^20
-        // 21.7 vs 22.7 ms)
-        // (the two-MSM form: the even half-blocks of 2^lgm points, dot H' from the GLV table, L / R as XYZZ)
-        const MsmOpts blocks = MsmOpts::Async().blocks(lgm).glv_hide().xyzz().after(hr);
-        if (pair) {
-            // L and R reach `pinned` from k_bitcombine itself (polled, as the tail rounds): no copy
-            const MsmPairIO io{sl, sr, sm + SM_DOT_L, sm + SM_DOT_R, sm + SM_L, sm + SM_R};
-            const MsmPreHide pre{weighted_dots_launch, &wd};
-            uint32_t seq = ++ses->poll_seq;
-            if (seq == 0) seq = ++ses->poll_seq;  // (0 is the flags' initial value)
-            HALO_CHECK(msm_srs_pairs_device(st, ses->curve, 1, &io, half, lgm, ses->htab_ptr, s, hr, &pre,
-                                            (uint32_t*)(ses->pinned + PIN_L), seq));
-            HALO_CHECK(msm_join(st, s));
-            ses->poll_pending = true;
-            return HALO_OK;
-        } else if (ses->solo) {
-            // L on the session stream and R on its second stream: the two MSMs' fronts, accumulations and
-            // reduction tails overlap, instead of R's front waiting for L's accumulation (measured, 2^20
-            // opening 20.5-20.8 -> 19.7-19.9 ms; with k sessions in lockstep their streams already overlap,
-            // and 2k streams over the default 4 hardware queues made the prover's three openings ~2 ms
-            // slower, so lockstep rounds keep one stream per session)
-            if (!ses->s2) {
-                HALO_HIP(hipStreamCreateWithFlags(&ses->s2, hipStreamNonBlocking));
-                HALO_HIP(hipEventCreateWithFlags(&ses->ev_fork, hipEventDisableTiming));
-                HALO_HIP(hipEventCreateWithFlags(&ses->ev_join, hipEventDisableTiming));
-            }
-            if (!ses->slots_reset) {
-                msm_slots_reset(st);
-                ses->slots_reset = true;
-            }
-            HALO_HIP(hipEventRecord(ses->ev_fork, s));
-            HALO_HIP(hipStreamWaitEvent(ses->s2, ses->ev_fork, 0));
-            HALO_CHECK(msm_srs_range_device(st, ses->curve, 0, sl, half, ses->htab_ptr, sm + SM_DOT_L, sm + SM_L, s, blocks));
-            HALO_CHECK(msm_srs_range_device(st, ses->curve, m, sr, half, ses->htab_ptr, sm + SM_DOT_R, sm + SM_R, ses->s2,
-                                            blocks));
-            HALO_CHECK(msm_join(st, ses->s2));
-            HALO_HIP(hipEventRecord(ses->ev_join, ses->s2));
-            HALO_HIP(hipStreamWaitEvent(s, ses->ev_join, 0));
-        } else {
-            HALO_CHECK(msm_srs_range_device(st, ses->curve, 0, sl, half, ses->htab_ptr, sm + SM_DOT_L, sm + SM_L, s, blocks));
-            HALO_CHECK(msm_srs_range_device(st, ses->curve, m, sr, half, ses->htab_ptr, sm + SM_DOT_R, sm + SM_R, s, blocks));
-        }
-        HALO_CHECK(msm_join(st, s));
-        return ipa_copy_out(ses);
+        HALO_HIP(hipEventRecord(ses->ev_fork, s));
+        HALO_HIP(hipStreamWaitEvent(ses->s2, ses->ev_fork, 0));
+        HALO_CHECK(msm_srs_range_device(st, curve, 0, sl, half, htab, sm + SM_DOT_L, sm + SM_L, s, blocks));
+        HALO_CHECK(msm_srs_range_device(st, curve, m, sr, half, htab, sm + SM_DOT_R, sm + SM_R, ses->s2, blocks));
+        HALO_CHECK(msm_join(st, ses->s2));
+        HALO_HIP(hipEventRecord(ses->ev_join, ses->s2));
+        HALO_HIP(hipStreamWaitEvent(s, ses->ev_join, 0));
+    } else {
+        HALO_CHECK(msm_srs_range_device(st, curve, 0, sl, half, htab, sm + SM_DOT_L, sm + SM_L, s, blocks));
+        HALO_CHECK(msm_srs_range_device(st, curve, m, sr, half, htab, sm + SM_DOT_R, sm + SM_R, s, blocks));
     }
+    HALO_CHECK(msm_join(st, s));
+    return ipa_copy_out(ses);
+}
+
+// A round over G itself: the two dots, then L and R as two MSMs over the SRS ranges or over gs
+static int ipa_round_lr_g(DeviceState* st, halo_ipa_session* ses, IpaRoundKind kind, hipEvent_t hr, hipStream_t s) {
+    const size_t m = ses->op.g.m;
+    const int curve = ses->op.curve;
+    const void* htab = ses->op.htab_ptr;
+    const int sf = curve == HALO_PALLAS ? HALO_FP : HALO_FQ;
+    char* sm = (char*)ses->small.ptr;
+    const char* cs = ses->cs.as<const char>();
+    const char* zs = ses->zs.as<const char>();
+    const char* gs = ses->gs.as<const char>();
     HALO_CHECK(dot_device(sf, cs + m * 32, zs, m, sm + SM_DOT_L, ses->tmp.ptr, s));        // <c_r, z_l>
     HALO_CHECK(dot_device(sf, cs, zs + m * 32, m, sm + SM_DOT_R, ses->tmp.ptr, s));        // <c_l, z_r>
-    if (ses->xi_mode) {  // dot H' = (dot xi_0) H
-        DISPATCH_CURVE(ses->curve, Cv, {
+    if (ses->op.xi_mode) {  // dot H' = (dot xi_0) H
+        DISPATCH_CURVE(curve, Cv, {
             hipLaunchKernelGGL(k_scale_ark<typename Cv::Scalar>, dim3(1), dim3(64), 0, s, (uint4*)(sm + SM_DOT_L), 2,
                                (const uint4*)(sm + SM_XI0));
         });
         HALO_HIP(hipGetLastError());
     }
-    {
-        // L and R are independent: the second MSM's accumulation overlaps the first one's tail
-        const MsmOpts lr = MsmOpts::Async().glv_hide().xyzz().after(hr);
-        if (ses->srs_round0) {  // G_l = SRS[0, m), G_r = SRS[m, 2m): resident window-shifted copies, no Horner
-            HALO_CHECK(msm_srs_range_device(st, ses->curve, 0, cs + m * 32, m, ses->htab_ptr, sm + SM_DOT_L, sm + SM_L, s, lr));
-            HALO_CHECK(msm_srs_range_device(st, ses->curve, m, cs, m, ses->htab_ptr, sm + SM_DOT_R, sm + SM_R, s, lr));
-        } else {
-            HALO_CHECK(msm_device(st, ses->curve, gs, cs + m * 32, m, ses->htab_ptr, sm + SM_DOT_L, sm + SM_L, s, lr));
-            HALO_CHECK(msm_device(st, ses->curve, gs + m * 64, cs, m, ses->htab_ptr, sm + SM_DOT_R, sm + SM_R, s, lr));
-        }
-        HALO_CHECK(msm_join(st, s));
+    // L and R are independent: the second MSM's accumulation overlaps the first one's tail
+    const MsmOpts lr = MsmOpts::Async().glv_hide().xyzz().after(hr);
+    if (kind == IpaRoundKind::LrSrsRanges) {  // G_l = SRS[0, m), G_r = SRS[m, 2m): resident shifted copies, no Horner
+        HALO_CHECK(msm_srs_range_device(st, curve, 0, cs + m * 32, m, htab, sm + SM_DOT_L, sm + SM_L, s, lr));
+        HALO_CHECK(msm_srs_range_device(st, curve, m, cs, m, htab, sm + SM_DOT_R, sm + SM_R, s, lr));
+    } else {
+        HALO_CHECK(msm_device(st, curve, gs, cs + m * 32, m, htab, sm + SM_DOT_L, sm + SM_L, s, lr));
+        HALO_CHECK(msm_device(st, curve, gs + m * 64, cs, m, htab, sm + SM_DOT_R, sm + SM_R, s, lr));
     }
+    HALO_CHECK(msm_join(st, s));
     return ipa_copy_out(ses);
 }
 
-// Enqueues one fold with challenge xi (pcdl.rs:427-435); the session advances to the next round.
-static int ipa_fold_now(DeviceState* st, halo_ipa_session* ses, const halo_fe_t* xi, const halo_fe_t* xi_inv);
-
-// A deferred tail-round fold applied on its own (before U at the end, a state read, or a second fold).
-static int ipa_apply_pending_fold(DeviceState* st, halo_ipa_session* ses) {
-    if (!ses->fold_pending) return HALO_OK;
-    ses->fold_pending = false;
-    ses->m = ses->pend_m;  // ipa_fold_now halves it again
-    return ipa_fold_now(st, ses, &ses->pend_xi, &ses->pend_xinv);
+// A round may run: rounds are left and the session was started
+static int ipa_round_ready(const halo_ipa_session* ses) {
+    if (ses->op.g.m == 0) return set_error(HALO_EINVAL, "halo_ipa_round_lr: no rounds left");
+    if (!ses->op.started) return set_error(HALO_EINVAL, "halo_ipa_round_lr: session not started (halo_pcdl_open_start)");
+    return HALO_OK;
 }
 
-int halo::ipa_fold_launch(DeviceState* st, halo_ipa_session* ses, const halo_fe_t* xi, const halo_fe_t* xi_inv) {
-    if (ses->m == 0) return set_error(HALO_EINVAL, "halo_ipa_fold: no rounds left");
-    if (!ses->started) return set_error(HALO_EINVAL, "halo_ipa_fold: session not started (halo_pcdl_open_start)");
-    if (!ses->xi_dev && (!xi || !xi_inv)) return set_error(HALO_EINVAL, "halo_ipa_fold: null argument");
-    if (ses->tail) {  // applied by the next round's k_tail_prep (no launch, no copy now)
-        HALO_CHECK(ipa_apply_pending_fold(st, ses));
-        if (!ses->xi_dev) {  // (a device transcript's challenge stays at SM_XI until the round that applies it)
-            ses->pend_xi = *xi;
-            ses->pend_xinv = *xi_inv;
-        }
-        ses->pend_m = ses->m;
-        ses->fold_pending = true;
-        ses->srs_round0 = false;
-        ses->m /= 2;
-        return HALO_OK;
+// Enqueues one round's L and R (with their H' terms) and their D2H copy into ses->pinned: what the plan's
+// record of the round says, in its order.
+int halo::ipa_round_launch(DeviceState* st, halo_ipa_session* ses) {
+    HALO_CHECK(ipa_round_ready(ses));
+    hipStream_t s = ses->s;
+    const IpaRound r = ipa_plan_round(ses->op.g, ipa_plan_srs(st->srs[ses->op.curve]), ipa_plan_tunings(),
+                                      ipa_plan_consts(), ses->solo);
+    if (r.materialise) HALO_CHECK(ipa_materialise_g(st, ses, r.mat_xyzz, s));
+    if (r.enter_tail) HALO_CHECK(ipa_enter_tail(st, ses, r, s));
+    ses->op.g = r.plan;
+    // only round 1 orders its hiding terms after the side-stream table: every later round starts after
+    // the host has synchronised on round 1's results, which needed the table (a cross-stream wait in
+    // every round cost ~0.3 ms per 2^16 round)
+    hipEvent_t hr = ses->op.htab_waited ? nullptr : ses->htab_ready;
+    ses->op.htab_waited = true;
+    switch (r.kind) {
+        case IpaRoundKind::TailFused:
+        case IpaRoundKind::TailSplit:  // k_tail_prep forms the dots (scaled by xi_0) with the round's scalars
+            if (hr) HALO_HIP(hipStreamWaitEvent(s, hr, 0));
+            return ipa_round_tail(st, ses, r.kind, s);
+        case IpaRoundKind::WeightedPair:
+        case IpaRoundKind::WeightedTwoStreams:
+        case IpaRoundKind::WeightedOneStream: return ipa_round_weighted(st, ses, r.kind, hr, s);
+        case IpaRoundKind::LrSrsRanges:
+        case IpaRoundKind::LrMsm: return ipa_round_lr_g(st, ses, r.kind, hr, s);
     }
-    return ipa_fold_now(st, ses, xi, xi_inv);
+    return HALO_OK;
 }
 
-static int ipa_fold_now(DeviceState* st, halo_ipa_session* ses, const halo_fe_t* xi, const halo_fe_t* xi_inv) {
+// Enqueues the launches of one fold of half-length m with challenge xi (pcdl.rs:427-435): the weight fold of
+// wlen weights (c, z and w), or the G fold (c, z and gs).
+static int ipa_fold_enqueue(DeviceState* st, halo_ipa_session* ses, IpaFoldKind kind, bool fetch_gs, size_t m, size_t wlen,
+                            const halo_fe_t* xi, const halo_fe_t* xi_inv) {
     hipStream_t s = ses->s;
     char* sm = (char*)ses->small.ptr;
     // the previous fold's H2D copy from the pinned staging must have completed (a round in between
     // synchronises the stream; two folds in a row wait here)
-    if (ses->fold_inflight) HALO_HIP(hipStreamSynchronize(s));
-    const size_t m = ses->m;
+    if (ses->op.fold_inflight) HALO_HIP(hipStreamSynchronize(s));
     // a device transcript's xi | xi^-1 are already at SM_XI (no by-value pair, no staging copy)
-    const uint4* x_dev = ses->xi_dev ? (const uint4*)(sm + SM_XI) : nullptr;
-    if (ses->tail || ses->weighted) {
+    const uint4* x_dev = ses->op.xi_dev ? (const uint4*)(sm + SM_XI) : nullptr;
+    if (kind == IpaFoldKind::Weights) {
         // xi, xi^-1 as kernel arguments: no staging copy, so nothing for a later fold to wait on
         ArkScalarPair x{};
         if (!x_dev) {
             memcpy(&x.v[0], xi, 32);
             memcpy(&x.v[2], xi_inv, 32);
         }
-        ses->srs_round0 = false;
-        const dim3 grid(grid_for(std::max(m, ses->wlen), 256));
-        DISPATCH_CURVE(ses->curve, Cv, {
+        const dim3 grid(grid_for(std::max(m, wlen), 256));
+        const uint4* w_in = ses->w[ses->op.wcur].as<const uint4>();
+        uint4* w_out = ses->w[ses->op.wcur ^ 1].as<uint4>();
+        DISPATCH_CURVE(ses->op.curve, Cv, {
             if (x_dev)
                 hipLaunchKernelGGL(k_tail_fold_dev<Cv>, grid, dim3(256), 0, s, ses->cs.as<uint4>(), ses->zs.as<uint4>(), m,
-                                   x_dev, ses->w[ses->wcur].as<const uint4>(), ses->w[ses->wcur ^ 1].as<uint4>(), ses->wlen);
+                                   x_dev, w_in, w_out, wlen);
             else
                 hipLaunchKernelGGL(k_tail_fold<Cv>, grid, dim3(256), 0, s, ses->cs.as<uint4>(), ses->zs.as<uint4>(), m, x,
-                                   ses->w[ses->wcur].as<const uint4>(), ses->w[ses->wcur ^ 1].as<uint4>(), ses->wlen);
+                                   w_in, w_out, wlen);
         });
         HALO_HIP(hipGetLastError());
-        ses->wcur ^= 1;
-        ses->wlen *= 2;
-        ses->m /= 2;
+        ses->op.wcur ^= 1;
         return HALO_OK;
     }
     if (!x_dev) {
-        ses->fold_inflight = true;
+        ses->op.fold_inflight = true;
         memcpy(ses->pinned + PIN_XI, xi, 32);
         memcpy(ses->pinned + PIN_XINV, xi_inv, 32);
         HALO_HIP(hipMemcpyAsync(sm + SM_XI, ses->pinned + PIN_XI, 64, hipMemcpyHostToDevice, s));
     }
-    ses->srs_round0 = false;
-    if (!ses->tail && !ses->weighted) {  // G itself is folded below
-        HALO_CHECK(ipa_ensure_gs(st, ses));
-        ses->gs_srs_prefix = false;
-    }
+    if (fetch_gs) HALO_CHECK(ipa_fetch_gs(st, ses));
     {
-        DISPATCH_CURVE(ses->curve, Cv, {
+        DISPATCH_CURVE(ses->op.curve, Cv, {
             ProfScope prof("ipa_fold", s);
             HALO_LAUNCH(prof, k_ipa_fold<Cv>, dim3(grid_for(m, FOLD_THREADS)), dim3(FOLD_THREADS), 0, s, ses->gs.as<uint4>(),
                         ses->cs.as<uint4>(), ses->zs.as<uint4>(), m, (const uint4*)(sm + SM_XI),
@@ -1088,7 +1072,36 @@ static int ipa_fold_now(DeviceState* st, halo_ipa_session* ses, const halo_fe_t*
         });
         HALO_HIP(hipGetLastError());
     }
-    ses->m /= 2;
+    return HALO_OK;
+}
+
+// A deferred tail-round fold applied on its own (before U at the end, a state read, or a second fold); the
+// plan advanced when it was deferred.
+static int ipa_apply_pending_fold(DeviceState* st, halo_ipa_session* ses) {
+    if (!ses->op.fold_pending) return HALO_OK;
+    ses->op.fold_pending = false;
+    return ipa_fold_enqueue(st, ses, IpaFoldKind::Weights, false, ses->op.pend_m, ses->op.g.wlen / 2, &ses->op.pend_xi,
+                            &ses->op.pend_xinv);
+}
+
+// Enqueues one fold with challenge xi; the session advances to the next round.
+int halo::ipa_fold_launch(DeviceState* st, halo_ipa_session* ses, const halo_fe_t* xi, const halo_fe_t* xi_inv) {
+    if (ses->op.g.m == 0) return set_error(HALO_EINVAL, "halo_ipa_fold: no rounds left");
+    if (!ses->op.started) return set_error(HALO_EINVAL, "halo_ipa_fold: session not started (halo_pcdl_open_start)");
+    if (!ses->op.xi_dev && (!xi || !xi_inv)) return set_error(HALO_EINVAL, "halo_ipa_fold: null argument");
+    const IpaFold f = ipa_plan_fold(ses->op.g);
+    if (f.kind == IpaFoldKind::Deferred) {  // applied by the next round's k_tail_prep (no launch, no copy now)
+        HALO_CHECK(ipa_apply_pending_fold(st, ses));
+        if (!ses->op.xi_dev) {  // (a device transcript's challenge stays at SM_XI until the round that applies it)
+            ses->op.pend_xi = *xi;
+            ses->op.pend_xinv = *xi_inv;
+        }
+        ses->op.pend_m = ses->op.g.m;
+        ses->op.fold_pending = true;
+    } else {
+        HALO_CHECK(ipa_fold_enqueue(st, ses, f.kind, f.fetch_gs, ses->op.g.m, ses->op.g.wlen, xi, xi_inv));
+    }
+    ses->op.g = f.plan;
     return HALO_OK;
 }
 
@@ -1103,7 +1116,7 @@ static int ipa_poll_lr(halo_ipa_session* ses) {
     for (uint32_t spin = 0;; spin++) {
         if (__atomic_load_n(&fl[0], __ATOMIC_ACQUIRE) == seq && __atomic_load_n(&fl[1], __ATOMIC_ACQUIRE) == seq) {
             // the flags are the round's last stores, stream-ordered after any fold it followed
-            ses->fold_inflight = false;
+            ses->op.fold_inflight = false;
             return HALO_OK;
         }
         // spin politely: a pause per probe, and past ~1 ms (a round is 0.1-2 ms) give the core up between
@@ -1114,6 +1127,20 @@ static int ipa_poll_lr(halo_ipa_session* ses) {
     }
     HALO_HIP(hipStreamSynchronize(ses->s));
     HALO_HIP(hipMemcpy(ses->pinned + PIN_L, (char*)ses->small.ptr + SM_L, 256, hipMemcpyDeviceToHost));
+    return HALO_OK;
+}
+
+// The session list of a _multi call: every entry an open session, none listed twice.  Checked before the call
+// touches any session, so a refused call leaves all k where they were (lockstep openings stay in step; ADVICE
+// r05).  not_open_note: what the call's "is not open" text adds.
+static int ipa_check_sessions(const char* call, halo_ipa_session* const* ses, size_t k, const char* not_open_note = "") {
+    if (k && !ses) return set_error(HALO_EINVAL, "%s: null session list", call);
+    for (size_t i = 0; i < k; i++) {
+        if (!ses[i]) return set_error(HALO_EINVAL, "%s: null session %zu", call, i);
+        if (!ipa_is_open(ses[i])) return set_error(HALO_EINVAL, "%s: session %zu is not open%s", call, i, not_open_note);
+        for (size_t j = 0; j < i; j++)
+            if (ses[j] == ses[i]) return set_error(HALO_EINVAL, "%s: session %zu listed twice", call, i);
+    }
     return HALO_OK;
 }
 
@@ -1132,9 +1159,11 @@ extern "C" int halo_ipa_round_lr_multi(halo_ipa_session* const* ses, size_t k, h
     DeviceState* st = current_state();
     if (!st) return HALO_EDEVICE;
     std::lock_guard<std::mutex> g(st->mu);
+    // every session checked before the first round is enqueued (a session listed twice would run two rounds
+    // on one state and return the second one's L, R for both)
+    HALO_CHECK(ipa_check_sessions("halo_ipa_round_lr_multi", ses, k));
+    for (size_t i = 0; i < k; i++) HALO_CHECK(ipa_round_ready(ses[i]));
     for (size_t i = 0; i < k; i++) {
-        if (!ses[i]) return set_error(HALO_EINVAL, "halo_ipa_round_lr_multi: null session %zu", i);
-        if (!ipa_is_open(ses[i])) return set_error(HALO_EINVAL, "halo_ipa_round_lr_multi: session %zu is not open", i);
         ses[i]->solo = k == 1;
         HALO_CHECK(ipa_round_launch(st, ses[i]));
     }
@@ -1143,11 +1172,11 @@ extern "C" int halo_ipa_round_lr_multi(halo_ipa_session* const* ses, size_t k, h
             HALO_CHECK(ipa_poll_lr(ses[i]));
         } else {
             HALO_HIP(hipStreamSynchronize(ses[i]->s));
-            ses[i]->fold_inflight = false;
+            ses[i]->op.fold_inflight = false;
         }
         const void* src[2] = {ses[i]->pinned + PIN_L, ses[i]->pinned + PIN_R};
         void* dst[2] = {&L[i], &R[i]};
-        host_xyzz_to_wrapped2(ses[i]->curve, src, dst, 2);
+        host_xyzz_to_wrapped2(ses[i]->op.curve, src, dst, 2);
     }
     return HALO_OK;
 }
@@ -1187,15 +1216,12 @@ extern "C" int halo_ipa_fold_multi(halo_ipa_session* const* ses, size_t k, const
     if (!st) return HALO_EDEVICE;
     std::lock_guard<std::mutex> g(st->mu);
     // every session checked and every inverse formed before the first fold is enqueued: an argument
-    // error leaves all k sessions where they were (lockstep openings stay in step)
+    // error leaves all k sessions where they were
+    HALO_CHECK(ipa_check_sessions("halo_ipa_fold_multi", ses, k));
     std::vector<halo_fe_t> inv(xi_inv ? 0 : k);
     for (size_t i = 0; i < k; i++) {
-        if (!ses[i]) return set_error(HALO_EINVAL, "halo_ipa_fold_multi: null session %zu", i);
-        if (!ipa_is_open(ses[i])) return set_error(HALO_EINVAL, "halo_ipa_fold_multi: session %zu is not open", i);
-        for (size_t j = 0; j < i; j++)
-            if (ses[j] == ses[i]) return set_error(HALO_EINVAL, "halo_ipa_fold_multi: session %zu listed twice", i);
         // xi_inv == NULL: xi^-1 formed here, as the reference's fold does (pcdl.rs:430)
-        if (!xi_inv && !host_scalar_inverse(ses[i]->curve, &xi[i], &inv[i]))
+        if (!xi_inv && !host_scalar_inverse(ses[i]->op.curve, &xi[i], &inv[i]))
             return set_error(HALO_EINVAL, "halo_ipa_fold_multi: xi %zu is zero (no inverse)", i);
     }
     for (size_t i = 0; i < k; i++) HALO_CHECK(ipa_fold_launch(st, ses[i], &xi[i], xi_inv ? &xi_inv[i] : &inv[i]));
@@ -1213,15 +1239,15 @@ extern "C" int halo_ipa_state(halo_ipa_session* ses, size_t* m, halo_wrapped_poi
     std::lock_guard<std::mutex> g(st->mu);
     hipStream_t s = ses->s;
     HALO_CHECK(ipa_apply_pending_fold(st, ses));
-    const size_t len = std::max<size_t>(2 * ses->m, 1);
-    if (m) *m = ses->m;
-    if (gs && (ses->tail || ses->weighted || !ses->gs_valid))
+    const size_t len = std::max<size_t>(2 * ses->op.g.m, 1);
+    if (m) *m = ses->op.g.m;
+    if (gs && (ses->op.tail() || ses->op.weighted() || !ses->op.g.gs_current))
         return set_error(HALO_EINVAL,
                          "halo_ipa_state: G is not materialised in the weighted / tail rounds (HALO_IPA_WEIGHTED=0, "
                          "HALO_IPA_TAIL=0)");
     if (gs) {
         HALO_CHECK(ses->tmp.reserve(std::max<size_t>(len * 64, 4096 * 32)));
-        HALO_CHECK(convert_internal_to_wrapped(ses->curve, ses->gs.ptr, ses->tmp.ptr, len, s));
+        HALO_CHECK(convert_internal_to_wrapped(ses->op.curve, ses->gs.ptr, ses->tmp.ptr, len, s));
         HALO_CHECK(copy_d2h(gs, ses->tmp.ptr, len * 64, s));
     }
     if (cs) HALO_CHECK(copy_d2h(cs, ses->cs.ptr, len * 32, s));
@@ -1236,41 +1262,42 @@ int halo::ipa_end_enqueue(DeviceState* st, halo_ipa_session* ses) {
     hipStream_t s = ses->s;
     char* sm = (char*)ses->small.ptr;
     int rc = HALO_OK;
-    if (!ses->started) {
+    if (!ses->op.started) {
         rc = set_error(HALO_EINVAL, "halo_ipa_end: session not started");
     } else if ((rc = ipa_apply_pending_fold(st, ses))) {
-    } else if (ses->tail || ses->weighted) {
+    } else if (ses->op.tail() || ses->op.weighted()) {
         // U = G_0 = sum_u w[u] G0[u] (len = 1 once every round ran)
-        if (ses->m != 0)
+        if (ses->op.g.m != 0)
             rc = set_error(HALO_EINVAL, "halo_ipa_end: U needs every round in the weighted / tail rounds (m = %zu)",
-                           ses->m);
-        else if (ses->tail)  // XYZZ at [256, 384), converted below; c = cs[0] copied to [384, 416) by its last block
-            rc = ipa_tail_sums(st, ses, 1, s, ses->cs.ptr, sm + SM_U_C_XYZZ);
+                           ses->op.g.m);
+        else if (ses->op.tail())  // XYZZ at [256, 384), converted below; c = cs[0] copied to [384, 416) by its last block
+            rc = ipa_tail_u(st, ses, s, ses->cs.ptr, sm + SM_U_C_XYZZ);
         else
-            rc = msm_srs_range_device(st, ses->curve, 0, ses->w[ses->wcur].ptr, ses->n0, nullptr, nullptr, sm + SM_U, s,
-                                      MsmOpts::Sync());
-        if (!rc && !ses->tail && hipMemcpyAsync(sm + SM_U_C, ses->cs.ptr, 32, hipMemcpyDeviceToDevice, s) != hipSuccess)
+            rc = msm_srs_range_device(st, ses->op.curve, 0, ses->w[ses->op.wcur].ptr, ses->op.g.n0, nullptr, nullptr,
+                                      sm + SM_U, s, MsmOpts::Sync());
+        if (!rc && !ses->op.tail() && hipMemcpyAsync(sm + SM_U_C, ses->cs.ptr, 32, hipMemcpyDeviceToDevice, s) != hipSuccess)
             rc = set_error(HALO_EDEVICE, "ipa end copy failed");
-    } else if ((rc = ipa_ensure_gs(st, ses))) {
+    } else if (!ses->op.g.gs_current && (rc = ipa_fetch_gs(st, ses))) {  // (no round and no fold ran: G is the SRS prefix)
     } else {
-        DISPATCH_CURVE(ses->curve, Cv, {
+        DISPATCH_CURVE(ses->op.curve, Cv, {
             hipLaunchKernelGGL(k_copy_first_wrapped<Cv>, dim3(1), dim3(64), 0, s, ses->gs.as<const uint4>(),
                                ses->cs.as<const uint4>(), (uint4*)(sm + SM_U), (uint4*)(sm + SM_U_C));
         });
         if (hipGetLastError() != hipSuccess) rc = set_error(HALO_EDEVICE, "ipa end launch failed");
     }
     // one copy through the pinned staging: U (wrapped, or XYZZ [256, 384) after tail rounds), c
-    if (!rc && hipMemcpyAsync(ses->pinned + PIN_U, sm + SM_U, ses->tail ? 160 : 96, hipMemcpyDeviceToHost, s) != hipSuccess)
+    const size_t u_bytes = ses->op.tail() ? 160 : 96;
+    if (!rc && hipMemcpyAsync(ses->pinned + PIN_U, sm + SM_U, u_bytes, hipMemcpyDeviceToHost, s) != hipSuccess)
         rc = set_error(HALO_EDEVICE, "ipa end copy failed");
     return rc;
 }
 
 int halo::ipa_end_finish(halo_ipa_session* ses, halo_wrapped_point_t* U, halo_fe_t* c) {
-    const bool u_xyzz = ses->tail;
+    const bool u_xyzz = ses->op.tail();
     if (hipStreamSynchronize(ses->s) != hipSuccess) return set_error(HALO_EDEVICE, "ipa end synchronisation failed");
     if (U) {
         if (u_xyzz)
-            host_xyzz_to_wrapped(ses->curve, ses->pinned + PIN_U, U);
+            host_xyzz_to_wrapped(ses->op.curve, ses->pinned + PIN_U, U);
         else
             memcpy(U, ses->pinned + PIN_U, 64);
     }
@@ -1299,14 +1326,7 @@ extern "C" int halo_ipa_end(halo_ipa_session* ses, halo_wrapped_point_t* U, halo
 
 extern "C" int halo_ipa_end_multi(halo_ipa_session* const* ses, size_t k, halo_wrapped_point_t* U, halo_fe_t* c) {
     clear_error();
-    if (k && !ses) return set_error(HALO_EINVAL, "halo_ipa_end_multi: null session list");
-    for (size_t i = 0; i < k; i++) {
-        if (!ses[i]) return set_error(HALO_EINVAL, "halo_ipa_end_multi: null session %zu", i);
-        if (!ipa_is_open(ses[i]))
-            return set_error(HALO_EINVAL, "halo_ipa_end_multi: session %zu is not open (already ended)", i);
-        for (size_t j = 0; j < i; j++)
-            if (ses[j] == ses[i]) return set_error(HALO_EINVAL, "halo_ipa_end_multi: session %zu listed twice", i);
-    }
+    HALO_CHECK(ipa_check_sessions("halo_ipa_end_multi", ses, k, " (already ended)"));
     int rc = HALO_OK;
     if (k && (U || c)) {
         DeviceState* st = current_state();

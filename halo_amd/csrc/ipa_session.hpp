@@ -4,11 +4,49 @@
 #pragma once
 #include <memory>
 
+#include "ipa_plan.hpp"
 #include "msm.hpp"
 #include "runtime.hpp"
 
 using halo::BatchScratch;
 using halo::DevBuf;
+using halo::GForm;
+using halo::IpaPlan;
+
+// The per-opening half of a session: value-initialised by ipa_acquire (halo_ipa_session::reset_state is one
+// assignment, so a field added here cannot survive into the next pooled opening).
+struct IpaOpening {
+    int curve = 0;
+    size_t n = 0;
+    // The form of G, the half-length m of the next round and, in the weighted and tail rounds, n0 and the length
+    // of the fold weights: ipa_plan.hpp, which also decides what every round and fold launches.
+    IpaPlan g;
+    int wcur = 0;                  // w[wcur] holds the fold weights
+    const uint4* table = nullptr;  // tail multiples table: own_table, or the SRS's small table
+    size_t table_ld = 0;
+    std::shared_ptr<DevBuf> table_ref;  // keeps the SRS's table alive while the session reads it
+    bool slots_reset = false;         // this opening restarted the MSM slot assignment (msm_slots_reset)
+    bool fold_inflight = false;       // a fold's H2D copy of xi may still read `pinned`
+    bool fold_pending = false;        // tail rounds: the last fold is applied by the next launch (k_tail_prep)
+    bool w_one_pending = false;       // entered the tail rounds: w = [1] is written by the next tail launch
+    halo_fe_t pend_xi{}, pend_xinv{};
+    size_t pend_m = 0;                // the half-length m the pending fold folds (g.m is half of it already)
+    bool htab_waited = false;         // round 1 waited for it (later rounds follow a host sync of round 1)
+    // xi mode (halo_ipa_begin_xi / _dev_xi / halo_pcdl_open_start): the hiding terms use the resident
+    // 2^i H table and the dots scaled by xi_0 (dot H' = (dot xi_0) H), so there is neither H' nor a
+    // per-session table
+    bool xi_mode = false;
+    const void* htab_ptr = nullptr;  // 2^i H' (own table) or 2^i H (SrsState::h_tables)
+    bool started = false;            // rounds may run (a pcdl open session starts at halo_pcdl_open_start)
+    bool blinded = false;            // halo_pcdl_open_blind ran (pbar holds p_bar)
+    bool combined = false;           // halo_pcdl_open_combine ran
+    // the transcript runs on the device (pcdl_open_fs.hip): the folds read xi | xi^-1 at SM_XI, which the
+    // round's transcript kernel wrote, and no round or fold waits for the host
+    bool xi_dev = false;
+
+    bool tail() const { return g.form == GForm::Tail; }
+    bool weighted() const { return g.form == GForm::Weighted; }
+};
 
 // One opening.  Sessions are pooled per device (ipa_acquire / ipa_release): the streams, events,
 // pinned staging and every device buffer survive halo_ipa_end and are reused by the next opening,
@@ -20,7 +58,6 @@ struct halo_ipa_session {
     hipStream_t s = nullptr;
     hipStream_t s2 = nullptr;           // weighted rounds above ipa_pair_max: R's MSM (created on first use)
     bool solo = true;                   // the round call advances this session alone (s2 is used then)
-    bool slots_reset = false;           // this opening restarted the MSM slot assignment (msm_slots_reset)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     hipEvent_t htab_ready = nullptr;  // recorded after the session's own 2^i H' table
     hipEvent_t lr_ready = nullptr;    // halo_ipa_round_lr_dev: L, R copied out (created on first use)
@@ -35,64 +72,28 @@ struct halo_ipa_session {
     // session entry point refuses a handle that is not open, and a second end cannot pool it twice
     bool in_use = false;
     // ---- per-opening state (reset by ipa_acquire)
-    int curve = 0;
-    size_t n = 0, m = 0;
-    // tail rounds (length <= IPA_TAIL_N, sessions over the SRS only): see k_tail_table
-    bool allow_tail = false, tail = false;
-    bool srs_round0 = false;  // G is still the SRS prefix (no fold yet): L/R on the resident shifted SRS
-    bool gs_srs_prefix = false;  // G (length 2m) = Gs[0..2m): the tail can use the SRS's multiples table
-    bool tail_from_srs = false;  // n <= ipa_srs_tail_max(): tail rounds from round 1 over the SRS's table
-    bool gs_xyzz = false;     // gs holds XYZZ points (materialised for the tail table only)
-    bool gs_valid = false;    // gs holds the current G (halo_ipa_state may read it)
-    bool weighted = false;    // G is never folded: L/R over the resident shifted SRS (k_weighted_scalars)
-    size_t n0 = 0, wlen = 0;
-    int wcur = 0;
-    const uint4* table = nullptr;  // tail multiples table: own_table, or the SRS's small table
-    size_t table_ld = 0;
-    std::shared_ptr<DevBuf> table_ref;  // keeps the SRS's table alive while the session reads it
-    bool fold_inflight = false;       // a fold's H2D copy of xi may still read `pinned`
-    bool fold_pending = false;        // tail rounds: the last fold is applied by the next launch (k_tail_prep)
-    bool w_one_pending = false;       // entered the tail rounds: w = [1] is written by the next tail launch
-    halo_fe_t pend_xi{}, pend_xinv{};
-    size_t pend_m = 0;                // the half-length m the pending fold folds (before its m /= 2)
-    bool htab_waited = false;         // round 1 waited for it (later rounds follow a host sync of round 1)
-    // xi mode (halo_ipa_begin_xi / _dev_xi / halo_pcdl_open_start): the hiding terms use the resident
-    // 2^i H table and the dots scaled by xi_0 (dot H' = (dot xi_0) H), so there is neither H' nor a
-    // per-session table
-    bool xi_mode = false;
-    const void* htab_ptr = nullptr;  // 2^i H' (own table) or 2^i H (SrsState::h_tables)
-    bool started = false;            // rounds may run (a pcdl open session starts at halo_pcdl_open_start)
-    bool blinded = false;            // halo_pcdl_open_blind ran (pbar holds p_bar)
-    bool combined = false;           // halo_pcdl_open_combine ran
-    // the transcript runs on the device (pcdl_open_fs.hip): the folds read xi | xi^-1 at SM_XI, which the
-    // round's transcript kernel wrote, and no round or fold waits for the host
-    bool xi_dev = false;
+    IpaOpening op;
 
-    void reset_state() {
-        curve = 0;
-        n = m = 0;
-        allow_tail = tail = srs_round0 = gs_srs_prefix = tail_from_srs = gs_xyzz = gs_valid = weighted = false;
-        n0 = wlen = 0;
-        wcur = 0;
-        table = nullptr;
-        table_ld = 0;
-        fold_inflight = htab_waited = xi_mode = fold_pending = slots_reset = w_one_pending = false;
-        htab_ptr = nullptr;
-        started = blinded = combined = xi_dev = false;
-    }
-    size_t buffer_bytes() const {
-        size_t b = 0;
-        for (const DevBuf* d : {&gs, &cs, &zs, &cs2, &zs2, &htab, &small, &tmp, &pbar, &own_table, &w[0], &w[1], &scal,
-                                &side, &part, &mat.digits, &mat.lists, &mat.keys, &mat.vals, &mat.bstart, &mat.partials,
-                                &mat.bucket_sums, &mat.window_sums})
-            b += d->bytes;
-        return b;
-    }
-    void release_large() {  // everything sized by n (the small staging and the H' table stay)
+    void reset_state() { op = IpaOpening{}; }
+
+    // every device buffer; sized_by_n: all but the small staging and the H' table
+    template <class F>
+    void each_buffer(F&& f) {
+        for (DevBuf* d : {&htab, &small}) f(*d, false);
         for (DevBuf* d : {&gs, &cs, &zs, &cs2, &zs2, &tmp, &pbar, &own_table, &w[0], &w[1], &scal, &side, &part,
                           &mat.digits, &mat.lists, &mat.keys, &mat.vals, &mat.bstart, &mat.partials, &mat.bucket_sums,
                           &mat.window_sums})
-            d->release();
+            f(*d, true);
+    }
+    size_t buffer_bytes() {
+        size_t b = 0;
+        each_buffer([&](DevBuf& d, bool) { b += d.bytes; });
+        return b;
+    }
+    void release_large() {  // everything sized by n (the small staging and the H' table stay)
+        each_buffer([](DevBuf& d, bool sized_by_n) {
+            if (sized_by_n) d.release();
+        });
     }
     void destroy() {
         if (s) (void)hipStreamSynchronize(s);
@@ -110,12 +111,7 @@ struct halo_ipa_session {
         s = nullptr;
         htab_ready = nullptr;
         pinned = nullptr;
-        for (DevBuf* b : {&gs, &cs, &zs, &cs2, &zs2, &htab, &small, &tmp, &pbar, &own_table, &w[0], &w[1], &scal, &side,
-                          &part})
-            b->release();
-        for (DevBuf* b : {&mat.digits, &mat.lists, &mat.keys, &mat.vals, &mat.bstart, &mat.partials, &mat.bucket_sums,
-                          &mat.window_sums})
-            b->release();
+        each_buffer([](DevBuf& d, bool) { d.release(); });
     }
 };
 

@@ -128,14 +128,15 @@ extern "C" int halo_pcdl_open_blind(halo_ipa_session* ses, const halo_fe_t* q, c
                                     halo_wrapped_point_t* C_bar) {
     clear_error();
     if (!ses || !q || !w_bar || !C_bar) return set_error(HALO_EINVAL, "halo_pcdl_open_blind: null argument");
-    if (ses->started || ses->blinded) return set_error(HALO_EINVAL, "halo_pcdl_open_blind: session already blinded or started");
+    if (ses->op.started || ses->op.blinded)
+        return set_error(HALO_EINVAL, "halo_pcdl_open_blind: session already blinded or started");
     DeviceState* st = current_state();
     if (!st) return HALO_EDEVICE;
     std::lock_guard<std::mutex> g(st->mu);
-    SrsState& srs = st->srs[ses->curve];
+    SrsState& srs = st->srs[ses->op.curve];
     if (!srs.has_sh) return set_error(HALO_ESRSRANGE, "hiding commitment needs S: upload the SRS (S, H) first");
     hipStream_t s = ses->s;
-    const size_t n = ses->n, d = n - 1;
+    const size_t n = ses->op.n, d = n - 1;
     char* sm = ses->small.as<char>();
     HALO_CHECK(ses->pbar.reserve(n * 32));
     HALO_CHECK(ses->tmp.reserve(std::max<size_t>(4096 * 32, d * 32)));
@@ -144,29 +145,29 @@ extern "C" int halo_pcdl_open_blind(halo_ipa_session* ses, const halo_fe_t* q, c
     // of dependent multiplications at the end of the blind)
     if (n <= std::min(srs_small_max(), srs.n)) {  // p_bar, its GLV words and w_bar in one launch (k_pbar_small)
         SmallMsmScratch scr;
-        HALO_CHECK(small_msm_scratch(st, ses->curve, n, s, &scr));
+        HALO_CHECK(small_msm_scratch(st, ses->op.curve, n, s, &scr));
         ArkScalarPair wb;
         memcpy(&wb.v[0], w_bar, 32);
-        DISPATCH_CURVE(ses->curve, Cv, {
+        DISPATCH_CURVE(ses->op.curve, Cv, {
             hipLaunchKernelGGL(k_pbar_small<Cv>, dim3(grid_for(n, 256)), dim3(256), 0, s, ses->tmp.as<const uint4>(), d,
                                (const uint4*)(sm + SM_Z), wb, (uint4*)(sm + SM_WBAR), ses->pbar.as<uint4>(), scr.scal,
                                scr.side);
         });
         HALO_HIP(hipGetLastError());
-        HALO_CHECK(small_msm_sums(st, ses->curve, scr, n, sm + SM_WBAR, sm + SM_T, s, true, nullptr, nullptr, nullptr));
+        HALO_CHECK(small_msm_sums(st, ses->op.curve, scr, n, sm + SM_WBAR, sm + SM_T, s, true, nullptr, nullptr, nullptr));
     } else {
         HALO_CHECK(copy_h2d(sm + SM_WBAR, w_bar, 32, s));
-        HALO_CHECK(pcdl_pbar_device(ses->curve, ses->tmp.ptr, d, sm + SM_Z, ses->pbar.ptr, s));
-        HALO_CHECK(msm_srs_device(st, ses->curve, ses->pbar.ptr, n, sm + SM_WBAR, sm + SM_T, s, MsmOpts::Sync().xyzz()));
+        HALO_CHECK(pcdl_pbar_device(ses->op.curve, ses->tmp.ptr, d, sm + SM_Z, ses->pbar.ptr, s));
+        HALO_CHECK(msm_srs_device(st, ses->op.curve, ses->pbar.ptr, n, sm + SM_WBAR, sm + SM_T, s, MsmOpts::Sync().xyzz()));
     }
     HALO_HIP(hipMemcpyAsync(ses->pinned + PIN_T, sm + SM_T, 128, hipMemcpyDeviceToHost, s));
     HALO_HIP(hipStreamSynchronize(s));
-    host_xyzz_to_wrapped(ses->curve, ses->pinned + PIN_T, C_bar);
+    host_xyzz_to_wrapped(ses->op.curve, ses->pinned + PIN_T, C_bar);
     if (n > COMBINE_MSM_MAX) {  // pcdl_combine_device reads C_bar on the device
         memcpy(ses->pinned + PIN_T, C_bar, 64);
         HALO_HIP(hipMemcpyAsync(sm + SM_CBAR, ses->pinned + PIN_T, 64, hipMemcpyHostToDevice, s));
     }
-    ses->blinded = true;
+    ses->op.blinded = true;
     return HALO_OK;
 }
 
@@ -175,17 +176,17 @@ extern "C" int halo_pcdl_open_combine(halo_ipa_session* ses, const halo_fe_t* al
     clear_error();
     if (!ses || !alpha || !C || !w || !w_prime || !C_prime)
         return set_error(HALO_EINVAL, "halo_pcdl_open_combine: null argument");
-    if (!ses->blinded || ses->combined || ses->started)
+    if (!ses->op.blinded || ses->op.combined || ses->op.started)
         return set_error(HALO_EINVAL, "halo_pcdl_open_combine: needs exactly one halo_pcdl_open_blind before it");
     DeviceState* st = current_state();
     if (!st) return HALO_EDEVICE;
     std::lock_guard<std::mutex> g(st->mu);
     hipStream_t s = ses->s;
     char* sm = ses->small.as<char>();
-    const bool small = ses->n <= std::min(srs_small_max(), st->srs[ses->curve].n);  // (k_combine_small takes them by value)
+    const bool small = ses->op.n <= std::min(srs_small_max(), st->srs[ses->op.curve].n);  // (k_combine_small takes them by value)
     if (!small) {  // alpha, w, C and S (internal) in one launch
         PutArgs a{};
-        const void* src[4] = {alpha, w, C, st->srs[ses->curve].S};
+        const void* src[4] = {alpha, w, C, st->srs[ses->op.curve].S};
         const size_t off[4] = {SM_ALPHA, SM_W, SM_C, SM_S};
         const int cnt[4] = {2, 2, 4, 4};
         int k = 0;
@@ -202,45 +203,45 @@ extern "C" int halo_pcdl_open_combine(halo_ipa_session* ses, const halo_fe_t* al
     // Up to COMBINE_MSM_MAX coefficients C' is formed as C + MSM(G, alpha p_bar) - w S (= C + alpha C_bar - w' S,
     // since C_bar = MSM(G, p_bar) + w_bar S): an MSM (the table path, or the bucket pipeline) instead of
     // the lone-lane scalar multiplications of k_hiding_point (~1.3 ms of dependent curve operations).
-    if (ses->n <= COMBINE_MSM_MAX) {
+    if (ses->op.n <= COMBINE_MSM_MAX) {
         // the MSM as packed XYZZ (no inversion on the device), + C, converted on the host below
         if (small) {
             // one launch for every scalar (k_combine_small), then the small MSM whose final block adds C and
             // puts w' beside the sum: one device-to-host copy of both
             SmallMsmScratch scr;
-            HALO_CHECK(small_msm_scratch(st, ses->curve, ses->n, s, &scr));
+            HALO_CHECK(small_msm_scratch(st, ses->op.curve, ses->op.n, s, &scr));
             CombineSmallArgs a;
             memcpy(a.alpha, alpha, 32);
             memcpy(a.w, w, 32);
             memcpy(a.C, C, 64);
-            DISPATCH_CURVE(ses->curve, Cv, {
-                hipLaunchKernelGGL(k_combine_small<Cv>, dim3(grid_for(ses->n, 256)), dim3(256), 0, s, a, ses->cs.as<uint4>(),
-                                   ses->pbar.as<uint4>(), ses->n, (const uint4*)(sm + SM_WBAR), (uint4*)(sm + SM_WP),
+            DISPATCH_CURVE(ses->op.curve, Cv, {
+                hipLaunchKernelGGL(k_combine_small<Cv>, dim3(grid_for(ses->op.n, 256)), dim3(256), 0, s, a, ses->cs.as<uint4>(),
+                                   ses->pbar.as<uint4>(), ses->op.n, (const uint4*)(sm + SM_WBAR), (uint4*)(sm + SM_WP),
                                    (uint4*)(sm + SM_NEGW), (uint4*)(sm + SM_C), scr.scal, scr.side);
             });
             HALO_HIP(hipGetLastError());
-            HALO_CHECK(small_msm_sums(st, ses->curve, scr, ses->n, sm + SM_NEGW, sm + SM_T, s, true, sm + SM_C, sm + SM_WP,
+            HALO_CHECK(small_msm_sums(st, ses->op.curve, scr, ses->op.n, sm + SM_NEGW, sm + SM_T, s, true, sm + SM_C, sm + SM_WP,
                                       sm + SM_T + 128));
             HALO_HIP(hipMemcpyAsync(ses->pinned + PIN_T, sm + SM_T, 160, hipMemcpyDeviceToHost, s));
             HALO_HIP(hipStreamSynchronize(s));
             memcpy(w_prime, ses->pinned + PIN_T_WP, 32);
-            host_xyzz_to_wrapped(ses->curve, ses->pinned + PIN_T, C_prime);
-            ses->combined = true;
+            host_xyzz_to_wrapped(ses->op.curve, ses->pinned + PIN_T, C_prime);
+            ses->op.combined = true;
             return HALO_OK;
         } else {
-            HALO_CHECK(pcdl_combine_scalars_device(ses->curve, ses->cs.ptr, ses->pbar.ptr, ses->n, sm + SM_ALPHA,
+            HALO_CHECK(pcdl_combine_scalars_device(ses->op.curve, ses->cs.ptr, ses->pbar.ptr, ses->op.n, sm + SM_ALPHA,
                                                    sm + SM_W, sm + SM_WBAR, sm + SM_WP, sm + SM_NEGW, s));
-            HALO_CHECK(msm_srs_device(st, ses->curve, ses->pbar.ptr, ses->n, sm + SM_NEGW, sm + SM_T, s,
+            HALO_CHECK(msm_srs_device(st, ses->op.curve, ses->pbar.ptr, ses->op.n, sm + SM_NEGW, sm + SM_T, s,
                                       MsmOpts::Sync().xyzz()));
-            HALO_CHECK(xyzz_add_wrapped_device(ses->curve, sm + SM_T, sm + SM_C, s, false));
+            HALO_CHECK(xyzz_add_wrapped_device(ses->op.curve, sm + SM_T, sm + SM_C, s, false));
         }
         HALO_HIP(hipMemcpyAsync(ses->pinned + PIN_FE, sm + SM_WP, 32, hipMemcpyDeviceToHost, s));
         HALO_HIP(hipMemcpyAsync(ses->pinned + PIN_T, sm + SM_T, 128, hipMemcpyDeviceToHost, s));
         HALO_HIP(hipStreamSynchronize(s));
         memcpy(w_prime, ses->pinned + PIN_FE, 32);
-        host_xyzz_to_wrapped(ses->curve, ses->pinned + PIN_T, C_prime);
+        host_xyzz_to_wrapped(ses->op.curve, ses->pinned + PIN_T, C_prime);
     } else {
-        HALO_CHECK(pcdl_combine_device(ses->curve, ses->cs.ptr, ses->n, ses->pbar.ptr, ses->n, sm + SM_ALPHA, sm + SM_W,
+        HALO_CHECK(pcdl_combine_device(ses->op.curve, ses->cs.ptr, ses->op.n, ses->pbar.ptr, ses->op.n, sm + SM_ALPHA, sm + SM_W,
                                        sm + SM_WBAR, sm + SM_C, sm + SM_CBAR, sm + SM_S, ses->cs.ptr, sm + SM_CP,
                                        sm + SM_WP, s));
         HALO_HIP(hipMemcpyAsync(ses->pinned + PIN_FE, sm + SM_WP, 32, hipMemcpyDeviceToHost, s));
@@ -249,21 +250,21 @@ extern "C" int halo_pcdl_open_combine(halo_ipa_session* ses, const halo_fe_t* al
         memcpy(w_prime, ses->pinned + PIN_FE, 32);
         memcpy(C_prime, ses->pinned + PIN_CP, 64);
     }
-    ses->combined = true;
+    ses->op.combined = true;
     return HALO_OK;
 }
 
 extern "C" int halo_pcdl_open_start(halo_ipa_session* ses, const halo_wrapped_point_t* H, const halo_fe_t* xi0) {
     clear_error();
     if (!ses || !xi0) return set_error(HALO_EINVAL, "halo_pcdl_open_start: null argument");
-    if (ses->started) return set_error(HALO_EINVAL, "halo_pcdl_open_start: session already started");
-    if (ses->blinded && !ses->combined)
+    if (ses->op.started) return set_error(HALO_EINVAL, "halo_pcdl_open_start: session already started");
+    if (ses->op.blinded && !ses->op.combined)
         return set_error(HALO_EINVAL, "halo_pcdl_open_start: a blinded opening needs halo_pcdl_open_combine first");
     DeviceState* st = current_state();
     if (!st) return HALO_EDEVICE;
     std::lock_guard<std::mutex> g(st->mu);
     if (!H) {  // the resident SRS's H (pp.H, pcdl.rs:390)
-        const SrsState& srs = st->srs[ses->curve];
+        const SrsState& srs = st->srs[ses->op.curve];
         if (!srs.has_sh) return set_error(HALO_ESRSRANGE, "no (S, H) uploaded");
         H = &srs.H_wrapped;
     }

@@ -128,7 +128,7 @@ int launch_start(halo_ipa_session* ses, const uint32_t* params, int lanes, int m
     if (v) memcpy(a.v, v, 32);
     a.mode = mode;
     a.has_v = v != nullptr;
-    DISPATCH_CURVE(ses->curve, Cv, {
+    DISPATCH_CURVE(ses->op.curve, Cv, {
         DISPATCH_LANES(lanes, L, {
             hipLaunchKernelGGL((k_open_fs_start<Cv, L>), dim3(1), dim3(64), 0, ses->s, params, ses->small.as<uint4>(), a);
         });
@@ -148,7 +148,7 @@ int enqueue_round(DeviceState* st, halo_ipa_session* ses, const uint32_t* params
     uint4* row = (uint4*)(sm + SM_PROOF + 128 * j);
     {
         ProfScope prof("open_fs_round", s);
-        DISPATCH_CURVE(ses->curve, Cv, {
+        DISPATCH_CURVE(ses->op.curve, Cv, {
             DISPATCH_LANES(lanes, L, {
                 HALO_LAUNCH(prof, (k_open_fs_round<Cv, L>), dim3(1), dim3(64), 0, s, params, (uint4*)sm, xi_prev, row);
             });
@@ -163,7 +163,7 @@ int enqueue_end(DeviceState* st, halo_ipa_session* ses) {
     hipStream_t s = ses->s;
     char* sm = ses->small.as<char>();
     HALO_CHECK(ipa_end_enqueue(st, ses));
-    HALO_HIP(hipMemcpyAsync(ses->pinned + PIN_PROOF, sm + SM_PROOF, ilog2(ses->n) * 128, hipMemcpyDeviceToHost, s));
+    HALO_HIP(hipMemcpyAsync(ses->pinned + PIN_PROOF, sm + SM_PROOF, ilog2(ses->op.n) * 128, hipMemcpyDeviceToHost, s));
     HALO_HIP(hipMemcpyAsync(ses->pinned + PIN_STATUS, sm + SM_STATUS, 4, hipMemcpyDeviceToHost, s));
     HALO_HIP(hipMemcpyAsync(ses->pinned + PIN_V, sm + SM_V, 32, hipMemcpyDeviceToHost, s));
     return HALO_OK;
@@ -174,8 +174,8 @@ int enqueue_end(DeviceState* st, halo_ipa_session* ses) {
 // session enqueued whole would take every slot and its neighbours would queue behind it), then the ends.
 int enqueue_chains(DeviceState* st, halo_ipa_session* const* ses, size_t k, const uint32_t* params, int lanes) {
     for (size_t i = 0; i < k; i++)
-        HALO_CHECK(ipa_start(st, ses[i], nullptr, nullptr, &st->srs[ses[i]->curve].H_wrapped, true));
-    const size_t lg = ilog2(ses[0]->n);
+        HALO_CHECK(ipa_start(st, ses[i], nullptr, nullptr, &st->srs[ses[i]->op.curve].H_wrapped, true));
+    const size_t lg = ilog2(ses[0]->op.n);
     for (size_t j = 0; j < lg; j++)
         for (size_t i = 0; i < k; i++) HALO_CHECK(enqueue_round(st, ses[i], params, lanes, j));
     for (size_t i = 0; i < k; i++) HALO_CHECK(enqueue_end(st, ses[i]));
@@ -186,7 +186,7 @@ int enqueue_chains(DeviceState* st, halo_ipa_session* const* ses, size_t k, cons
 int finish(const char* call, halo_ipa_session* ses, halo_wrapped_point_t* Ls, halo_wrapped_point_t* Rs, halo_wrapped_point_t* U,
            halo_fe_t* c, halo_fe_t* v_out) {
     HALO_CHECK(ipa_end_finish(ses, U, c));
-    const size_t lg = ilog2(ses->n);
+    const size_t lg = ilog2(ses->op.n);
     for (size_t j = 0; j < lg; j++) {
         memcpy(&Ls[j], ses->pinned + PIN_PROOF + 128 * j, 64);
         memcpy(&Rs[j], ses->pinned + PIN_PROOF + 128 * j + 64, 64);
@@ -238,7 +238,7 @@ int open_fs_dev_chain(const char* call, DeviceState* st, int curve, size_t k, co
         }
         ses.push_back(s);
         rc = ipa_setup(st, s, curve, n, nullptr, (const halo_fe_t*)d_p[i], lens[i], true, nullptr, &z[i]);
-        s->xi_dev = true;
+        s->op.xi_dev = true;
         s->solo = k == 1;
         if (!rc) rc = ipa_eval_cs_enqueue(s, lens[i]);
         if (!rc) rc = launch_start(s, params, lanes, 0, &C[i], nullptr, nullptr);
@@ -288,7 +288,7 @@ extern "C" int halo_pcdl_open_fs(halo_curve_t curve, const halo_fe_t* p, size_t 
         ses = ipa_acquire(st);
         if (!ses) return HALO_EDEVICE;
         rc = ipa_setup(st, ses, curve, n, nullptr, p, deg_len, false, nullptr, z);
-        ses->xi_dev = true;
+        ses->op.xi_dev = true;
         ses->solo = true;
         if (!rc && !v) rc = ipa_eval_cs_enqueue(ses, deg_len);  // pcdl::open: v = p(z) (pcdl.rs:471)
     }

@@ -17,6 +17,8 @@ reference's names, argument meaning and assertion messages:
                          of raw proofs of one circuit, every transcript on the device)
     halo_amd.sponge   -- crates/poseidon/src/outer_sponge.rs (Sponge: the Fiat-Shamir sponge as an object with
                          its state on the device; SpongeBatch: k of them in lockstep; new_transcript)
+    halo_amd.wire     -- ark-serialize compressed bytes of Instance / EvalProof / Accumulator (pcdl.rs:26,159,
+                         acc.rs:22) <-> the arrays above, decoded and encoded on the device
 
 Field elements are numpy uint64 arrays of shape (n, 4) in arkworks Montgomery form; points are
 (n, 8) WrappedPoint arrays (x, y Montgomery limbs; (0, 0) = identity).  There is no CPU fallback:
@@ -24,4 +26,4 @@ without the HIP library or a GPU every call raises.
 """
 from . import _lib  # noqa: F401
 
-__all__ = ["_lib", "group", "poly", "pedersen", "pcdl", "acc", "schnorr", "plonk", "sponge"]
+__all__ = ["_lib", "group", "poly", "pedersen", "pcdl", "acc", "schnorr", "plonk", "sponge", "wire"]

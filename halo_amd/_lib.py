@@ -165,6 +165,20 @@ SIGNATURES = {
     "halo_sponge_absorb_fr_dev": [ctypes.c_uint64, _vp, _sz, _vp],
     "halo_sponge_absorb_fq_dev": [ctypes.c_uint64, _vp, _sz, _vp],
     "halo_sponge_challenge_dev": [ctypes.c_uint64, _sz, _vp, _vp],
+    "halo_fe_sqrt_batch": [ctypes.c_int, _vp, _sz, _vp, _vp],
+    "halo_fe_sqrt_batch_dev": [ctypes.c_int, _vp, _sz, _vp, _vp, _vp],
+    "halo_points_decompress": [ctypes.c_int, _vp, _sz, _vp, _vp],
+    "halo_points_decompress_dev": [ctypes.c_int, _vp, _sz, _vp, _vp, _vp],
+    "halo_points_compress": [ctypes.c_int, _vp, _sz, _vp],
+    "halo_points_compress_dev": [ctypes.c_int, _vp, _sz, _vp, _vp, _vp],
+    "halo_scalars_from_bytes": [ctypes.c_int, _vp, _sz, _vp, _vp],
+    "halo_scalars_from_bytes_dev": [ctypes.c_int, _vp, _sz, _vp, _vp, _vp],
+    "halo_scalars_to_bytes": [ctypes.c_int, _vp, _sz, _vp],
+    "halo_scalars_to_bytes_dev": [ctypes.c_int, _vp, _sz, _vp, _vp],
+    "halo_pcdl_instances_walk": [_vp, _sz, ctypes.c_int, _sz, _vp, _vp, _vp, ctypes.POINTER(_sz)],
+    "halo_pcdl_instances_decode": [ctypes.c_int, _sz, _sz, _vp, _sz] + [_vp] * 12,
+    "halo_pcdl_instances_decode_dev": [ctypes.c_int, _sz, _sz, _vp, _sz] + [_vp] * 13,
+    "halo_pcdl_instances_encode": [ctypes.c_int, _sz, _sz] + [_vp] * 11 + [ctypes.POINTER(_sz)],
     "halo_field_op": [ctypes.c_int, ctypes.c_int, _vp, _vp, _sz, _vp],
     "halo_curve_op": [ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _sz, _vp],
 }

@@ -45,6 +45,12 @@ def field_block(struct: str, p: int) -> str:
     out.append(arr("ARK_MUL_FIX", (1 << 266) % p))         # ark x ark through R' = 2^261 -> ark
     out.append(arr("ARK2CANON", 32))                        # ark Montgomery -> canonical integer
     out.append(arr("INV_FIX", pow(RP, 3, p)))              # fe_inv: (x R')^-1 -> x^-1 R'
+    # fe_sqrt (field_sqrt.hpp): p - 1 = 2^32 t, t odd; the chain's exponent (t - 1) / 2 in 2-bit windows.  The
+    # generator of the order-2^32 subgroup is 5^t = OMEGA[32] and g^(-2^i) = OMEGA_INV[32 - i] below.
+    t = (p - 1) >> MAXLOG
+    assert t & 1 and (p - 1) == t << MAXLOG and pow(5, (p - 1) // 2, p) == p - 1
+    out.append(f"    static constexpr uint64_t SQRT_EXP64[4] = {{{u64s((t - 1) // 2)}}};\n")
+    out.append(f"    static constexpr int SQRT_EXP_WINDOWS = {(((t - 1) // 2).bit_length() + 1) // 2};\n")
     # NTT domain constants: omega_N = 5^((p-1)/N) for N = 2^k, internal Montgomery form
     om = [pow(5, (p - 1) >> k, p) for k in range(MAXLOG + 1)]
     omi = [pow(w, -1, p) for w in om]

@@ -759,6 +759,30 @@ def check_batch(instances, rhos=None, curve="pallas", verdicts: bool = False, bi
     return None
 
 
+WIRE_MSG = "the bytes do not deserialize"
+
+
+def check_bytes(buf, rhos=None, vec: bool = False, curve="pallas", verdicts: bool = False, bisect: bool = False):
+    """pcdl::check for the instances of a serialized buffer (ark-serialize compressed bytes: concatenated Instances,
+    or with vec=True a Vec<Instance>): the layout is walked on the host, the points and scalars are decoded on the
+    device (halo_pcdl_instances_decode_dev) and checked there (halo_pcdl_check_fs_batch_dev), one pair of calls per
+    distinct d, the decoded arrays staying on the device.  rhos and bisect as in check_batch.  Codes: those of
+    check_batch, plus 3: the bytes of that instance do not deserialize (a point or scalar the format refuses), where
+    the reference's deserialize_compressed returns Err.  A buffer whose structure is broken (truncated, a bad length
+    or tag) raises HaloError with the walk's message before any launch.  Without verdicts: raises CheckFailed with
+    the reference's messages for 1 / 2 and ValueError naming the instance for 3."""
+    from . import wire
+    codes = wire.check_codes(buf, rhos=rhos, vec=vec, curve=curve, bisect=bisect)
+    if verdicts:
+        return codes
+    for i, c in enumerate(codes):
+        if c == 3:
+            raise ValueError(f"instance {i}: {WIRE_MSG}")
+        if c:
+            raise CheckFailed(SUCCINCT_MSG if c == 1 else DECIDER_MSG, i)
+    return None
+
+
 def trace_commit_batch(evals, d: int, curve="pallas", want_coeffs: bool = False):
     """Trace::new's interpolate + commit (crates/plonk/src/circuit/trace.rs:165-192) for k evaluation
     vectors at once: Evals::from_vec_and_domain -> interpolate_by_ref -> pcdl::commit(poly, d, None).

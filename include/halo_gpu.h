@@ -779,6 +779,76 @@ int halo_sponge_absorb_fr_dev(uint64_t id, const void* d_xs, size_t n, void* str
 int halo_sponge_absorb_fq_dev(uint64_t id, const void* d_xs, size_t n, void* stream);
 int halo_sponge_challenge_dev(uint64_t id, size_t n, void* d_out, void* stream);
 
+/* ------------------------------------------------------------------ the wire format (ABI 110)
+ * The reference's proof objects travel as ark-serialize 0.5 compressed bytes, little endian, concatenation the only
+ * framing (pcdl.rs:26,159, acc.rs:22; written by accumulation/src/main.rs:80-81):
+ *   usize u64 | Vec<T> u64 length, items | Option<T> one byte 0 / 1, then the item if 1
+ *   scalar  32 bytes, the canonical value (not Montgomery), below the modulus
+ *   point   33 bytes: canonical x in bytes 0..31; byte 32: 0x80 y is the larger root (y > p - y), 0x40 infinity
+ *           with x = 0, both set invalid, bits 0..5 zero
+ *   Instance C, d, z, v, pi;  EvalProof (pi) Ls, Rs, U, c, C_bar: Option, w_prime: Option;  Accumulator = its Instance
+ * A point record is REFUSED when x is not below the modulus, x^3 + 5 is not a square (x = 0 among them), a flag
+ * bit is bad, or it is an infinity whose x is not 0 (only the canonical encoding is accepted; arkworks may be more
+ * lenient there).  A refused record decodes to the off-curve sentinel (0, 1) with validity 0, so by the rule of
+ * every batch verifier ("neither (0, 0) nor on the curve: that instance alone is rejected") it fails exactly the
+ * instance that holds it.  Host forms run on the null stream and return when the outputs are written; _dev forms
+ * take device pointers, are asynchronous on `stream` and wait for nothing.  k = 0: HALO_OK. */
+
+/* Square roots in either Pasta field, one lane per element: out[i] the SMALLER root of in[i] as a canonical
+ * integer (ark Montgomery limbs like every field element here) and is_square[i] = 1; zero and 0 for a
+ * non-residue; sqrt(0) = 0 with flag 1.  is_square may be NULL. */
+int halo_fe_sqrt_batch(halo_field_t field, const halo_fe_t* in, size_t k, halo_fe_t* out, uint8_t* is_square);
+int halo_fe_sqrt_batch_dev(halo_field_t field, const void* d_in, size_t k, void* d_out, void* d_is_square, void* stream);
+/* k consecutive 33-byte records -> WrappedPoints and validity bytes (ok may be NULL). */
+int halo_points_decompress(halo_curve_t curve, const uint8_t* bytes, size_t k, halo_wrapped_point_t* out_pts, uint8_t* ok);
+int halo_points_decompress_dev(halo_curve_t curve, const void* d_bytes, size_t k, void* d_out_pts, void* d_ok, void* stream);
+/* The inverse; (0, 0) gives the infinity record.  A point that is neither (0, 0) nor on the curve has no encoding:
+ * HALO_EINVAL naming it in the host form; in the _dev form d_ok[i] = 0 (d_ok may be NULL) and the record written
+ * carries both flags, which no decoder accepts. */
+int halo_points_compress(halo_curve_t curve, const halo_wrapped_point_t* pts, size_t k, uint8_t* out_bytes);
+int halo_points_compress_dev(halo_curve_t curve, const void* d_pts, size_t k, void* d_out_bytes, void* d_ok, void* stream);
+/* 32 canonical bytes <-> ark Montgomery limbs.  From bytes: ok[i] = 0 and a zero scalar where the value is not
+ * below the modulus (ok may be NULL).  To bytes: the value is reduced first. */
+int halo_scalars_from_bytes(halo_field_t field, const uint8_t* bytes, size_t k, halo_fe_t* out, uint8_t* ok);
+int halo_scalars_from_bytes_dev(halo_field_t field, const void* d_bytes, size_t k, void* d_out, void* d_ok, void* stream);
+int halo_scalars_to_bytes(halo_field_t field, const halo_fe_t* in, size_t k, uint8_t* out_bytes);
+int halo_scalars_to_bytes_dev(halo_field_t field, const void* d_in, size_t k, void* d_out_bytes, void* stream);
+/* The layout of a buffer of concatenated Instances, on the host alone (no device work, no GPU needed): with
+ * vec_prefix a Vec<Instance> (u64 count first, no byte after the last instance), else instances up to the last
+ * byte.  Reads only lengths, d and option tags.  offsets holds max_k + 1 entries: offsets[i] the first byte of
+ * instance i, offsets[i + 1] its end (instances are contiguous), so offsets[*k_out] is where the walk ended;
+ * ds[i], hiding[i] its degree bound and option tag.  Refused before anything is written, with a message of its own
+ * naming the instance: a buffer that ends inside an instance; a length prefix whose items the remaining bytes
+ * could not hold; Ls / Rs lengths that differ from each other or from lg(d + 1); d + 1 not a power of two
+ * (HALO_ENOTPOW2; the others HALO_EINVAL); a tag other than 0 / 1; one of C_bar / w_prime without the other;
+ * more than max_k instances; bytes after the last instance of a Vec. */
+int halo_pcdl_instances_walk(const uint8_t* bytes, size_t len, int vec_prefix, size_t max_k, uint64_t* offsets,
+                             uint64_t* ds, uint8_t* hiding, size_t* k_out);
+/* k instances of ONE degree bound d at offsets[0..k) of bytes[0, len) -> the argument arrays of
+ * halo_pcdl_check_fs_batch, in its order (Ls / Rs: k lg n rows; hiding, C_bar, w_prime always written: zero rows
+ * where the flag is 0).  The structure of every instance is checked first, on the host, with the refusals of
+ * halo_pcdl_instances_walk; an instance of another d is HALO_EINVAL.  ok[i] = 0 if any point or scalar of instance i
+ * does not decode: ALL its points are then the sentinel and all its scalars zero, so the verifier that follows
+ * rejects that instance alone and meets no scalar it would answer HALO_EINVAL for. */
+int halo_pcdl_instances_decode(halo_curve_t curve, size_t d, size_t k, const uint8_t* bytes, size_t len,
+        const uint64_t* offsets, halo_wrapped_point_t* C, halo_fe_t* z, halo_fe_t* v, halo_wrapped_point_t* Ls,
+        halo_wrapped_point_t* Rs, halo_wrapped_point_t* U, halo_fe_t* c, uint8_t* hiding, halo_wrapped_point_t* C_bar,
+        halo_fe_t* w_prime, uint8_t* ok);
+/* The same over device pointers.  Nothing is checked on the host: the device checks again that every instance lies
+ * inside [0, len), that its d is the call's, that Ls and Rs hold lg n points and that the tags are 0 / 1 and equal,
+ * reading nothing at or past len; a mismatch is a failed decode (ok 0, sentinels, zeros, hiding 0), so
+ * halo_pcdl_check_fs_batch_dev can consume the arrays on the same stream without a trip home. */
+int halo_pcdl_instances_decode_dev(halo_curve_t curve, size_t d, size_t k, const void* d_bytes, size_t len,
+        const void* d_offsets, void* d_C, void* d_z, void* d_v, void* d_Ls, void* d_Rs, void* d_U, void* d_c, void* d_hiding,
+        void* d_C_bar, void* d_w_prime, void* d_ok, void* stream);
+/* The inverse of halo_pcdl_instances_decode: the k instances, concatenated, with no Vec prefix.  hiding NULL: none
+ * hides.  *out_len: in, the capacity of out_bytes; out, the length.  Size query: out_bytes NULL returns the length
+ * alone.  HALO_EINVAL naming the instance for a point that is neither (0, 0) nor on the curve. */
+int halo_pcdl_instances_encode(halo_curve_t curve, size_t d, size_t k, const halo_wrapped_point_t* C,
+        const halo_fe_t* z, const halo_fe_t* v, const halo_wrapped_point_t* Ls, const halo_wrapped_point_t* Rs,
+        const halo_wrapped_point_t* U, const halo_fe_t* c, const uint8_t* hiding, const halo_wrapped_point_t* C_bar,
+        const halo_fe_t* w_prime, uint8_t* out_bytes, size_t* out_len);
+
 /* ------------------------------------------------------------------ measurement hooks
  * When enabled, the library brackets its dominant kernels (MSM bucket accumulation, NTT passes)
  * with hipEvents on the stream they run on; halo_profile_read returns the number of launches and

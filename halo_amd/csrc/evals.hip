@@ -432,6 +432,7 @@ extern "C" int halo_evals_op_dev(halo_field_t field, int op, const void* d_a, co
                                  uint32_t exponent, void* d_out, size_t n, void* stream) {
     clear_error();
     HALO_CHECK(check_evals_args(field, op, d_a, d_b, scalar, d_out, n));
+    if (!n) return HALO_OK;
     DeviceState* st = current_state();
     if (!st) return HALO_EDEVICE;
     return evals_launch(field, op, d_a, d_b, scalar, exponent, d_out, n, (hipStream_t)stream);
@@ -503,10 +504,10 @@ extern "C" int halo_evals_scan_dev(halo_field_t field, int reverse, const void* 
     if (field != HALO_FP && field != HALO_FQ) return set_error(HALO_EINVAL, "unknown field id %d", (int)field);
     if (n && (!d_in || !d_out)) return set_error(HALO_EINVAL, "halo_evals_scan_dev: null buffer");
     if (!n) return HALO_OK;
+    const size_t nb = n / SCAN_BLOCK + (n % SCAN_BLOCK != 0);
+    if (nb > (size_t)SCAN_THREADS * 4096) return set_error(HALO_EINVAL, "halo_evals_scan_dev: n too large");
     DeviceState* st = current_state();
     if (!st) return HALO_EDEVICE;
-    const size_t nb = (n + SCAN_BLOCK - 1) / SCAN_BLOCK;
-    if (nb > (size_t)SCAN_THREADS * 4096) return set_error(HALO_EINVAL, "halo_evals_scan_dev: n too large");
     hipStream_t s = (hipStream_t)stream;
     ScratchUse su(st, s);
     DevBuf* tot;

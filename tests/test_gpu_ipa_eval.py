@@ -627,3 +627,72 @@ def test_ipa_end_multi_arguments(hal, corc):
         s_._s = None
     hal.check(L.halo_ipa_end_multi(both, 2, None, None))
     assert L.halo_ipa_end_multi(both, 2, None, None) == 1  # HALO_EINVAL  # both closed now
+
+
+# ---- edges of the poly.hip reductions: block and run boundaries, words from the whole of [0, p) -----------------
+def _edge_z(tag):
+    """evaluation points as canonical values: 0, 1, -1, the values whose ark words are 1 and p - 1, a full-range one"""
+    import evals_ref as E
+    m = P.FIELDS[tag]
+    return [0, 1, m - 1] + E.unark([1, m - 1], m) + [random.Random(len(tag)).randrange(m)]
+
+
+@pytest.mark.parametrize("tag", ["fp", "fq"])
+@pytest.mark.parametrize("n", [0, 1, 2, 4095, 4096, 4097, 4113])
+def test_construct_powers_edges(hal, tag, n):
+    """halo_construct_powers at the lengths where a thread's run of powers is whole, ragged (4097 = 256 runs of 16 and
+    one power, 4113 = 257 and one) or absent, at z = 0 ([1, 0, 0, ...]), 1, -1 and full-range points."""
+    m = P.FIELDS[tag]
+    for z in _edge_z(tag):
+        got = group.construct_powers(fe([z], m), n, tag)
+        assert got.shape == (n, 4)
+        assert unfe(got, m) == P.construct_powers(z, n, m), (n, hex(z))
+    if n > 1:
+        assert unfe(group.construct_powers(fe([0], m), n, tag), m) == [1] + [0] * (n - 1)
+
+
+@pytest.mark.parametrize("tag", ["fp", "fq"])
+@pytest.mark.parametrize("n", [1, 2047, 2048, 2049, 6145])
+def test_scalar_dot_edges(hal, tag, n):
+    """halo_scalar_dot at the lengths around its 2048-element block (6145 = three blocks and one element) with operands
+    over the whole of [0, p) and the edge words, and x = y = all p - 1."""
+    import evals_ref as E
+    m = P.FIELDS[tag]
+    rng = random.Random(n)
+    pool = E.EDGE(m) + E.full_range(rng, 400, m)
+    xw, yw = [rng.choice(pool) for _ in range(n)], [rng.choice(pool) for _ in range(n)]
+    for xs, ys in ((xw, yw), ([m - 1] * n, [m - 1] * n), (xw, [m - 1] * n), ([0] * n, yw)):
+        got = group.scalar_dot(E.to_array(xs), E.to_array(ys), tag)
+        assert unfe(got, m) == [P.scalar_dot(E.unark(xs, m), E.unark(ys, m), m)], n
+
+
+@pytest.mark.parametrize("tag,fid", [("fp", 0), ("fq", 1)])
+def test_poly_eval_batch_edges(hal, tag, fid):
+    """halo_poly_eval_batch and _dev over one batch whose lengths sit around a thread's chunk of 32 coefficients and a
+    block's 8192 (and an empty polynomial), full-range coefficients, at z = 0, 1, -1 and full-range points."""
+    import ctypes
+
+    import evals_ref as E
+    import torch
+    m = P.FIELDS[tag]
+    rng = random.Random(fid)
+    lens = [0, 1, 31, 32, 33, 8191, 8192, 8193]
+    words = [E.full_range(rng, ln, m) for ln in lens]
+    words[-1][-1] = m - 1
+    vals = [E.unark(w, m) for w in words]
+    polys = [E.to_array(w) for w in words]
+    ts = [torch.from_numpy(p.view(np.int64)).cuda() if len(p) else None for p in polys]
+    ptrs = (ctypes.c_void_p * len(lens))(*[t.data_ptr() if t is not None else None for t in ts])
+    clens = (ctypes.c_size_t * len(lens))(*lens)
+    for z in _edge_z(tag):
+        exp = [P.horner(v, z, m) for v in vals]
+        assert exp[0] == 0 and (z or exp[1:] == [v[0] for v in vals[1:]])
+        zz = fe([z], m)
+        assert unfe(poly.evaluate_batch(polys, zz[0], tag), m) == exp, hex(z)
+        out = torch.full((len(lens) + 1, 4), 0x5A5A5A5A5A5A5A5A, dtype=torch.int64, device="cuda")
+        hal.check(hal.load().halo_poly_eval_batch_dev(fid, ptrs, clens, len(lens), hal.ptr(zz),
+                                                      ctypes.c_void_p(out.data_ptr()), None))
+        torch.cuda.synchronize()
+        h = out.cpu().numpy().view(np.uint64)
+        assert (h[-1] == np.uint64(0x5A5A5A5A5A5A5A5A)).all(), "the row past the results was written"
+        assert unfe(h[:-1], m) == exp, hex(z)

@@ -145,6 +145,8 @@ SIGNATURES = {
     "halo_pcdl_decide_batch": [ctypes.c_int, _sz, _sz] + [_vp] * 5,
     "halo_pcdl_decide_batch_dev": [ctypes.c_int, _sz, _sz] + [_vp] * 7,
     "halo_pcdl_decide_bisect_dev": [ctypes.c_int, _sz, _sz] + [_vp] * 6,
+    "halo_pcdl_decide_rho": [ctypes.c_int, _sz, _sz] + [_vp] * 4,
+    "halo_pcdl_decide_rho_dev": [ctypes.c_int, _sz, _sz] + [_vp] * 5,
     "halo_pcdl_check_fs_batch": [ctypes.c_int, _sz, _sz] + [_vp] * 12,
     "halo_pcdl_check_fs_batch_dev": [ctypes.c_int, _sz, _sz] + [_vp] * 14,
     "halo_plonk_verify_succinct_batch": [ctypes.c_int, _sz, _sz, _vp, _vp, _sz] + [_vp] * 19,
@@ -317,3 +319,20 @@ def bisecting(on: bool) -> tuning:
     """``with bisecting(bisect):`` around a batched decider call: decide_bisect = 1 when asked for, else no key is
     touched (a rejected combined batch is then bisected on the device instead of rerun in exact mode)."""
     return tuning(decide_bisect=1) if on else tuning()
+
+
+def deriving(on: bool) -> tuning:
+    """``with deriving(rhos == "fs"):`` around a batched decider call that passes no weights: decide_rho_fs = 1 when
+    asked for, else no key is touched (a NULL rho then means combined mode under the weights the device derives from
+    the batch, halo_pcdl_decide_rho, instead of exact mode)."""
+    return tuning(decide_rho_fs=1) if on else tuning()
+
+
+def fs_rhos(rhos, k: int):
+    """The two readings of a ``rhos`` argument: (the caller's weights as a (k, 4) array or None, derive).  "fs":
+    no array, and the call runs under ``deriving(True)``."""
+    if isinstance(rhos, str):
+        if rhos != "fs":
+            raise ValueError(f"rhos is an array of weights, None or 'fs', not {rhos!r}")
+        return None, True
+    return (fe_array(rhos, k) if rhos is not None else None), False

@@ -225,6 +225,6 @@ def decider(acc, new_transcript, curve="pallas") -> None:
 
 def decider_batch(accs, rhos=None, curve="pallas", bisect: bool = False) -> None:
     """acc.rs:215-217 for many accumulators at once: pcdl.check_batch of their instances, the transcripts and
-    the deciders on the device (rhos and bisect as in pcdl.decide_batch).  Raises CheckFailed naming the first
+    the deciders on the device (rhos -- None, "fs" or the caller's weights -- and bisect as in pcdl.decide_batch).  Raises CheckFailed naming the first
     failing one."""
     pcdl.check_batch([Instance(*a) for a in accs], rhos=rhos, curve=curve, bisect=bisect)

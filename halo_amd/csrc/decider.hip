@@ -7,7 +7,8 @@
 //   (msm_batch_device)   U'_i of the group: one (polynomial, bucket)-keyed MSM up to msm_multi_max, pipelined above
 //   k_decide_compare     one lane per instance: ok[i] = live[i] && U_i is (0, 0) or on the curve && U'_i == U_i
 // Combined mode, sum_i rho_i (U_i - Commit(h_i)) = sum_i rho_i U_i - Commit(sum_i rho_i h_i) with the caller's
-// random rho: one MSM whatever k.
+// random rho, or with DecideCall::derive the weights that decide_rho.hip derives from the batch (decide_rho_weights,
+// first thing in each of the three cores below): one MSM whatever k.
 //   k_decide_mask        rho_i = 0 and U_i = (0, 0) where the instance is not live: it contributes nothing
 //   (hpoly_combine_device)  sum_i rho_i h_i(X) as one coefficient vector (k_hpoly_tables with weights, k_hpoly_coeffs)
 //   (msm_srs_device)     its commitment P
@@ -38,6 +39,7 @@
 #include "poly.hpp"
 #include "quad_ladder.hpp"
 #include "runtime.hpp"
+#include "sponge_launch.hpp"
 
 namespace halo {
 
@@ -191,18 +193,6 @@ __global__ __launch_bounds__(DEC_THREADS) void k_check_codes(const uint8_t* __re
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-// A stage that is more than one kernel (an MSM): its halo_profile_read time is the span on `s` between begin
-// and end, its launch count the number of stages.
-struct StageScope {
-    ProfScope p;
-    StageScope(const char* name, hipStream_t s) : p(name, s) {
-        if (p.slot >= 0) (void)hipEventRecord(p.a, s);
-    }
-    void end() {
-        if (p.slot >= 0) (void)hipEventRecord(p.b, p.s);
-    }
-};
-
 static int decide_exact(DeviceState* st, const DecideCall& a, hipStream_t s) {
     const SrsState& srs = st->srs[a.curve];
     const size_t k = a.k, n = a.d + 1;
@@ -286,10 +276,12 @@ static int decide_combined(DeviceState* st, const DecideCall& a, hipStream_t s, 
     return HALO_OK;
 }
 
-int decide_device(DeviceState* st, const DecideCall& a, hipStream_t s) {
+int decide_device(DeviceState* st, const DecideCall& call, hipStream_t s) {
     // (n = d + 1 here, so the SRS prefix Gs[0..d] is never shorter than the coefficients: pedersen::commit's
     // "ms must be larger than Gs", halo_pcdl_decider_commit's HALO_ELENGTH, cannot arise once d <= D)
-    HALO_CHECK(check_verifier_srs(nullptr, st, a.curve, a.d, false));
+    HALO_CHECK(check_verifier_srs(nullptr, st, call.curve, call.d, false));
+    DecideCall a = call;
+    HALO_CHECK(decide_rho_weights(st, a, s));
     if (a.rho && a.k > 1) return decide_combined(st, a, s);
     HALO_CHECK(decide_exact(st, a, s));
     if (a.rho && a.combined) {  // k = 1 costs the same either way
@@ -353,9 +345,11 @@ struct BisectDevice {
 };
 static_assert(sizeof(BisectNode) == sizeof(uint4), "the kernels read a node as one uint4");
 
-int decide_bisect_device(DeviceState* st, const DecideCall& a, hipStream_t s) {
+int decide_bisect_device(DeviceState* st, const DecideCall& call, hipStream_t s) {
+    HALO_CHECK(check_verifier_srs(nullptr, st, call.curve, call.d, false));
+    DecideCall a = call;
+    HALO_CHECK(decide_rho_weights(st, a, s));
     if (!a.rho || a.k < 2) return decide_device(st, a, s);
-    HALO_CHECK(check_verifier_srs(nullptr, st, a.curve, a.d, false));
     const SrsState& srs = st->srs[a.curve];
     const size_t k = a.k, n = a.d + 1;
     CombinedOut root;
@@ -381,10 +375,12 @@ int decide_bisect_device(DeviceState* st, const DecideCall& a, hipStream_t s) {
     return bisect_descend(k, n, (size_t)std::max<long long>(tuning(TUNE_DECIDE_GROUP_SCALARS), 1), W, ev, host_ok.data());
 }
 
-int decide_resolved(DeviceState* st, const DecideCall& a, hipStream_t s) {
+int decide_resolved(DeviceState* st, const DecideCall& call, hipStream_t s) {
+    HALO_CHECK(check_verifier_srs(nullptr, st, call.curve, call.d, false));
+    DecideCall a = call;
+    HALO_CHECK(decide_rho_weights(st, a, s));
     if (!a.rho || a.k < 2) return decide_device(st, a, s);
     if (tuning(TUNE_DECIDE_BISECT) > 0) return decide_bisect_device(st, a, s);
-    HALO_CHECK(check_verifier_srs(nullptr, st, a.curve, a.d, false));
     CombinedOut root;
     HALO_CHECK(decide_combined(st, a, s, false, &root));
     uint8_t combined = 0;
@@ -392,6 +388,7 @@ int decide_resolved(DeviceState* st, const DecideCall& a, hipStream_t s) {
     if (combined) return HALO_OK;
     DecideCall exact = a;  // some instance fails: the exact verdicts
     exact.rho = nullptr;
+    exact.derive = false;
     return decide_device(st, exact, s);
 }
 
@@ -423,12 +420,14 @@ extern "C" int halo_pcdl_decide_batch_dev(halo_curve_t curve, size_t d, size_t k
     bool done;
     HALO_CHECK(check_decide_args(call, curve, d, k, d_xis, d_U, d_ok, done));
     if (done) return HALO_OK;
+    const bool derive = decide_derives(d_rho);
+    if (derive) HALO_CHECK(require_poseidon_params(call, curve));
     DeviceState* st = current_state();
     if (!st) return HALO_EDEVICE;
     std::lock_guard<std::mutex> g(st->mu);
     hipStream_t s = (hipStream_t)stream;
     ScratchUse su(st, s);
-    return decide_device(st, DecideCall{(int)curve, d, k, d_xis, d_U, d_live, d_rho, d_ok, d_combined}, s);
+    return decide_device(st, DecideCall{(int)curve, d, k, d_xis, d_U, d_live, d_rho, d_ok, d_combined, derive}, s);
 }
 
 extern "C" int halo_pcdl_decide_bisect_dev(halo_curve_t curve, size_t d, size_t k, const void* d_xis, const void* d_U,
@@ -438,13 +437,15 @@ extern "C" int halo_pcdl_decide_bisect_dev(halo_curve_t curve, size_t d, size_t 
     bool done;
     HALO_CHECK(check_decide_args(call, curve, d, k, d_xis, d_U, d_ok, done));
     if (done) return HALO_OK;
-    if (!d_rho) return set_error(HALO_EINVAL, "%s: null d_rho", call);
+    const bool derive = decide_derives(d_rho);
+    if (!d_rho && !derive) return set_error(HALO_EINVAL, "%s: null d_rho", call);
+    if (derive) HALO_CHECK(require_poseidon_params(call, curve));
     DeviceState* st = current_state();
     if (!st) return HALO_EDEVICE;
     std::lock_guard<std::mutex> g(st->mu);
     hipStream_t s = (hipStream_t)stream;
     ScratchUse su(st, s);
-    return decide_bisect_device(st, DecideCall{(int)curve, d, k, d_xis, d_U, d_live, d_rho, d_ok, nullptr}, s);
+    return decide_bisect_device(st, DecideCall{(int)curve, d, k, d_xis, d_U, d_live, d_rho, d_ok, nullptr, derive}, s);
 }
 
 extern "C" int halo_pcdl_decide_batch(halo_curve_t curve, size_t d, size_t k, const halo_fe_t* xis,
@@ -460,11 +461,13 @@ extern "C" int halo_pcdl_decide_batch(halo_curve_t curve, size_t d, size_t k, co
         if (!scalar_below(curve, xis[j]))
             return set_error(HALO_EINVAL, "%s: xi_%zu of instance %zu is not below the modulus", call, j % row, j / row);
     HALO_CHECK(check_rho(call, curve, rho, k));
+    const bool derive = decide_derives(rho);
+    if (derive) HALO_CHECK(require_poseidon_params(call, curve));
     DeviceState* st = current_state();
     if (!st) return HALO_EDEVICE;
     std::lock_guard<std::mutex> g(st->mu);
     HALO_CHECK(check_verifier_srs(call, st, curve, d, false));
-    // only the live instances travel
+    // only the live instances travel (derived weights are those of the batch that travels: its m instances, all live)
     std::vector<size_t> idx;
     for (size_t i = 0; i < k; i++) {
         ok_out[i] = 0;
@@ -490,7 +493,7 @@ extern "C" int halo_pcdl_decide_batch(halo_curve_t curve, size_t d, size_t k, co
     std::vector<const void*> at;
     HALO_CHECK(upload_parts(st, HostParts{{xis, m * row * 32}, {U, m * 64}, {rho, rho ? m * 32 : 0}}, s, at));
     if (m != k) HALO_HIP(hipStreamSynchronize(s));  // pageable sources: each copy returns once the source has been read
-    DecideCall a{(int)curve, d, m, at[0], at[1], nullptr, at[2], dout, dout + align256(m)};
+    DecideCall a{(int)curve, d, m, at[0], at[1], nullptr, at[2], dout, dout + align256(m), derive};
     HALO_CHECK(decide_resolved(st, a, s));
     std::vector<uint8_t> got(m);
     HALO_CHECK(copy_d2h(got.data(), dout, m, s));
@@ -500,8 +503,8 @@ extern "C" int halo_pcdl_decide_batch(halo_curve_t curve, size_t d, size_t k, co
 
 // pcdl::check over device pointers: fs_device, then the decider over the xis it leaves in st->decider[3].
 // host_fallback: a rejected combined batch is resolved to per-instance verdicts (decide_resolved).
-static int check_fs_run(const char* call, DeviceState* st, FsCall a, const void* d_rho, void* d_code, void* d_combined,
-                        bool host_fallback, hipStream_t s) {
+static int check_fs_run(const char* call, DeviceState* st, FsCall a, const void* d_rho, bool derive, void* d_code,
+                        void* d_combined, bool host_fallback, hipStream_t s) {
     const size_t k = a.k, lg = ilog2(a.d + 1);
     HALO_CHECK(check_verifier_srs(call, st, a.curve, a.d, false));
     ScratchLayout lay;
@@ -513,7 +516,7 @@ static int check_fs_run(const char* call, DeviceState* st, FsCall a, const void*
     a.ok = base + o_succ;
     HALO_CHECK(fs_device(call, st, a, s));
     uint8_t* comb = d_combined ? (uint8_t*)d_combined : base + o_comb;
-    DecideCall dc{a.curve, a.d, k, base + o_xis, a.U, base + o_succ, d_rho, base + o_dec, comb};
+    DecideCall dc{a.curve, a.d, k, base + o_xis, a.U, base + o_succ, d_rho, base + o_dec, comb, derive};
     HALO_CHECK(host_fallback ? decide_resolved(st, dc, s) : decide_device(st, dc, s));
     hipLaunchKernelGGL(k_check_codes, dim3(grid_for(k, DEC_THREADS)), dim3(DEC_THREADS), 0, s, (const uint8_t*)(base + o_succ),
                        (const uint8_t*)(base + o_dec), k, (uint8_t*)d_code);
@@ -531,12 +534,13 @@ extern "C" int halo_pcdl_check_fs_batch_dev(halo_curve_t curve, size_t d, size_t
     bool done;
     HALO_CHECK(check_fs_args(call, a, done));
     if (done) return HALO_OK;
+    const bool derive = decide_derives(d_rho);  // (check_fs_args has required the Poseidon parameters)
     DeviceState* st = current_state();
     if (!st) return HALO_EDEVICE;
     std::lock_guard<std::mutex> g(st->mu);
     hipStream_t s = (hipStream_t)stream;
     ScratchUse su(st, s);
-    return check_fs_run(call, st, a, d_rho, d_ok, d_combined, false, s);
+    return check_fs_run(call, st, a, d_rho, derive, d_ok, d_combined, false, s);
 }
 
 extern "C" int halo_pcdl_check_fs_batch(halo_curve_t curve, size_t d, size_t k, const halo_wrapped_point_t* C,
@@ -552,6 +556,7 @@ extern "C" int halo_pcdl_check_fs_batch(halo_curve_t curve, size_t d, size_t k, 
     if (done) return HALO_OK;
     HALO_CHECK(fs_host_scalars(call, host));
     HALO_CHECK(check_rho(call, curve, rho, k));
+    const bool derive = decide_derives(rho);
     DeviceState* st = current_state();
     if (!st) return HALO_EDEVICE;
     std::lock_guard<std::mutex> g(st->mu);
@@ -564,6 +569,6 @@ extern "C" int halo_pcdl_check_fs_batch(halo_curve_t curve, size_t d, size_t k, 
     HALO_CHECK(upload_parts(st, in, s, at));
     HALO_CHECK(st->scratch[1].reserve(k));
     uint8_t* dout = st->scratch[1].as<uint8_t>();
-    HALO_CHECK(check_fs_run(call, st, fs_dev_call(host, at), at.back(), dout, nullptr, true, s));
+    HALO_CHECK(check_fs_run(call, st, fs_dev_call(host, at), at.back(), derive, dout, nullptr, true, s));
     return copy_d2h(ok_out, dout, k, s);
 }

@@ -78,8 +78,10 @@ struct OuterSponge {
     HALO_DEV void absorb(const Fe<F>& x) { inner.absorb(x); }
 
     // The next challenge as the scalar's canonical integer (below the scalar modulus in both directions).
-    HALO_DEV void challenge(uint32_t (&w)[8]) {
-        fe_to_canonical_words(inner.squeeze(), w);
+    HALO_DEV void challenge(uint32_t (&w)[8]) { challenge_words(inner.squeeze(), w); }
+    // ... of an element that the inner sponge squeezed (a kernel whose one squeeze call serves several sponges)
+    static HALO_DEV void challenge_words(const Fe<F>& squeezed, uint32_t (&w)[8]) {
+        fe_to_canonical_words(squeezed, w);
         if (SCALAR_BELOW_BASE) {
 #pragma unroll
             for (int q = 0; q < 8; q++) w[q] = (w[q] >> 1) | (q < 7 ? w[q + 1] << 31 : 0u);

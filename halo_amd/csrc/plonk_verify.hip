@@ -488,6 +488,7 @@ struct PlonkCall {  // the arguments of either entry point
     bool full = false;
     const void *next_Ls = nullptr, *next_Rs = nullptr, *next_U = nullptr, *next_c = nullptr, *rho = nullptr;
     void* combined = nullptr;
+    bool derive = false;  // a null rho means derived weights (decider.hpp decide_derives, resolved at the entry point)
 };
 
 // What the decider of a full call reads, left in scratch by plonk_device (plonk_decide runs it).
@@ -520,7 +521,7 @@ static int check_plonk_args(const char* call, const PlonkCall& a, bool& done) {
 // host form, which waits for a rejected combined batch's per-proof verdicts (decide_resolved).
 static int plonk_decide(DeviceState* st, const PlonkCall& a, const PlonkDecide& pd, const void* rho, bool resolve,
                         hipStream_t s) {
-    const DecideCall dc{a.curve, a.rows - 1, a.k, pd.xis, a.next_U, pd.live, rho, pd.decided, pd.combined};
+    const DecideCall dc{a.curve, a.rows - 1, a.k, pd.xis, a.next_U, pd.live, rho, pd.decided, pd.combined, a.derive};
     HALO_CHECK(resolve ? decide_resolved(st, dc, s) : decide_device(st, dc, s));
     hipLaunchKernelGGL(k_plonk_decided, dim3(grid_for(a.k, PV_THREADS)), dim3(PV_THREADS), 0, s, (const uint8_t*)pd.live,
                        (const uint8_t*)pd.decided, a.k, (uint8_t*)a.verdict);
@@ -674,6 +675,7 @@ static int plonk_host(const char* call, const PlonkCall& host) {
                 host.sides_out ? dout + o_sides : nullptr, host.asdl_out ? dout + o_asdl : nullptr};
     a.full = host.full;
     a.next_Ls = dev[17], a.next_Rs = dev[18], a.next_U = dev[19], a.next_c = dev[20], a.rho = dev[21];
+    a.derive = host.derive;
     HALO_CHECK(plonk_device(call, st, a, s, true));
     if (host.chal_out) HALO_CHECK(copy_d2h(host.chal_out, dout + o_chal, k * 5 * 32, s));
     if (host.sides_out) HALO_CHECK(copy_d2h(host.sides_out, dout + o_sides, k * 2 * 32, s));
@@ -739,6 +741,7 @@ extern "C" int halo_plonk_verify_batch_dev(
     a.full = true;
     a.next_Ls = d_acc_next_Ls, a.next_Rs = d_acc_next_Rs, a.next_U = d_acc_next_U, a.next_c = d_acc_next_c;
     a.rho = d_rho, a.combined = d_combined;
+    a.derive = decide_derives(d_rho);
     return plonk_dev("halo_plonk_verify_batch_dev", a, stream);
 }
 
@@ -756,5 +759,6 @@ extern "C" int halo_plonk_verify_batch(
     host.full = true;
     host.next_Ls = acc_next_Ls, host.next_Rs = acc_next_Rs, host.next_U = acc_next_U, host.next_c = acc_next_c;
     host.rho = rho;
+    host.derive = decide_derives(rho);
     return plonk_host("halo_plonk_verify_batch", host);
 }

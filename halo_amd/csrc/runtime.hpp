@@ -39,7 +39,7 @@ void clear_error();
 // ---- tuning (halo_set_tuning): path selections the parity tests pin; read on every use
 enum TuneKey { TUNE_IPA_WEIGHTED, TUNE_IPA_TAIL, TUNE_IPA_SRS_TAIL_N, TUNE_IPA_MAT_N, TUNE_MSM_MULTI_MAX, TUNE_IPA_POOL_KEEP,
                TUNE_NTT_BIG_MAX_LOG, TUNE_NTT_EVEN_SPLIT, TUNE_IPA_PAIR_MAX, TUNE_POSEIDON_LANES, TUNE_DECIDE_GROUP_SCALARS,
-               TUNE_DECIDE_BISECT, TUNE_COUNT };
+               TUNE_DECIDE_BISECT, TUNE_DECIDE_RHO_FS, TUNE_COUNT };
 long long tuning(TuneKey k);
 
 // ---- device buffers ---------------------------------------------------------------------------
@@ -128,6 +128,7 @@ struct DeviceState {
     DevBuf lincomb_terms;    // the terms of a batch of linear combinations (lincomb.hip): packed XYZZ, then a byte each
     DevBuf decider[4];       // decider.hip: h rows / coefficients, half-tables, U' and masks, the xis of a check
     DevBuf bisect[3];        // decider.hip's descent: segment rows, the root's terms, node tables / commitments / defects
+    DevBuf decide_rho[2];    // decide_rho.hip: the derived weights (no reserve of decider[] or bisect[] moves them), the hash tree
     // ScratchUse state: completion event of the last scratch user and its stream
     hipEvent_t scratch_ev = nullptr;
     hipStream_t scratch_last = nullptr;

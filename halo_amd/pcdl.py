@@ -688,21 +688,40 @@ def check_device(C, d: int, z, v, pi: dict, curve="pallas") -> None:
         raise CheckFailed(DECIDER_MSG)
 
 
+def decide_rho(xis, Us, d: int, live=None, curve="pallas") -> np.ndarray:
+    """halo_pcdl_decide_rho: the weights that rhos="fs" stands for, derived on the device from the batch itself
+    (d, k, the live flags and every live instance's U and xi_1 .. xi_lg n) by Fiat-Shamir over the curve's sponge;
+    include/halo_gpu.h states the derivation and its soundness bound.  xis, Us, live as in decide_batch.  Returns
+    (k, 4) ark scalars: nonzero where the instance is live, zero where it is not.  Needs the Poseidon parameters
+    (schnorr.set_poseidon_params) and no SRS."""
+    H.ensure_device()
+    U = H.point_array(Us)
+    k = len(U)
+    lg = (d + 1).bit_length() - 1
+    out = np.zeros((k, 4), dtype=np.uint64)
+    lv = np.ascontiguousarray(np.asarray(live, dtype=np.uint8).reshape(k)) if live is not None else None
+    H.check(H.load().halo_pcdl_decide_rho(_curve(curve), d, k, H.ptr(H.fe_array(xis, k * (lg + 1))), H.ptr(U), H.ptr(lv),
+                                          H.ptr(out)))
+    return out
+
+
 def decide_batch(xis, Us, d: int, rhos=None, live=None, curve="pallas", bisect: bool = False) -> np.ndarray:
     """halo_pcdl_decide_batch: acc::decider for k instances of degree bound d.  xis (k, lg n + 1, 4) challenges
     (the layout succinct_check_fs_verdicts returns), Us (k, 8).  rhos None: one commitment per instance (exact
-    mode); rhos (k, 4) nonzero scalars drawn by the caller AFTER the proofs were fixed: one random linear
-    combination and one MSM, with an exact rerun if it fails, or with bisect=True a descent through the halves
-    that fail (one MSM per failing node; tuning key decide_bisect).  live: k flags, 0 skips the instance
-    (verdict 0).  Returns k bytes, 1 where U == CM.Commit(ck, h_vec)."""
+    mode); rhos "fs": one random linear combination and one MSM under weights that the device derives from the
+    batch itself by Fiat-Shamir (decide_rho; no random number generator is needed, and two runs agree), with an
+    exact rerun if it fails, or with bisect=True a descent through the halves that fail (one MSM per failing node;
+    tuning key decide_bisect); rhos (k, 4): the same under the caller's own weights, nonzero scalars drawn
+    uniformly AFTER the proofs were fixed.  live: k flags, 0 skips the instance (verdict 0).  Returns k bytes, 1
+    where U == CM.Commit(ck, h_vec)."""
     H.ensure_device()
     U = H.point_array(Us)
     k = len(U)
     lg = (d + 1).bit_length() - 1
     ok = np.zeros(k, dtype=np.uint8)
     lv = np.ascontiguousarray(np.asarray(live, dtype=np.uint8).reshape(k)) if live is not None else None
-    rh = H.fe_array(rhos, k) if rhos is not None else None
-    with H.bisecting(bisect):
+    rh, derive = H.fs_rhos(rhos, k)
+    with H.bisecting(bisect), H.deriving(derive):
         H.check(H.load().halo_pcdl_decide_batch(_curve(curve), d, k, H.ptr(H.fe_array(xis, k * (lg + 1))), H.ptr(U),
                                                 H.ptr(lv), H.ptr(rh), H.ptr(ok)))
     return ok
@@ -723,8 +742,8 @@ def check_fs_codes(Cs, d: int, zs, vs, Ls, Rs, Us, cs, hiding=None, C_bars=None,
         hid = np.ascontiguousarray(np.asarray(hiding, dtype=np.uint8).reshape(k))
         cb, wp = H.point_array(C_bars), H.fe_array(w_primes, k)
         assert len(cb) == k
-    rh = H.fe_array(rhos, k) if rhos is not None else None
-    with H.bisecting(bisect):
+    rh, derive = H.fs_rhos(rhos, k)
+    with H.bisecting(bisect), H.deriving(derive):
         H.check(H.load().halo_pcdl_check_fs_batch(
             _curve(curve), d, k, H.ptr(C), H.ptr(H.fe_array(zs, k)), H.ptr(H.fe_array(vs, k)),
             H.ptr(H.point_array(Ls)) if lg else None, H.ptr(H.point_array(Rs)) if lg else None, H.ptr(H.point_array(Us)),
@@ -734,15 +753,15 @@ def check_fs_codes(Cs, d: int, zs, vs, Ls, Rs, Us, cs, hiding=None, C_bars=None,
 
 def check_batch(instances, rhos=None, curve="pallas", verdicts: bool = False, bisect: bool = False):
     """pcdl::check (pcdl.rs:563-583) for many instances (C, d, z, v, pi), every transcript and every decider on
-    the device: one halo_pcdl_check_fs_batch call per distinct d.  rhos: one nonzero scalar per instance, drawn
-    by the caller after the proofs were fixed (decide_batch), or None for exact deciders; bisect as in
-    decide_batch.  Raises
+    the device: one halo_pcdl_check_fs_batch call per distinct d.  rhos: None for exact deciders, "fs" for
+    weights derived on the device (each call, i.e. each d, derives its own), or one nonzero scalar per instance
+    drawn by the caller after the proofs were fixed (decide_batch); bisect as in decide_batch.  Raises
     CheckFailed(msg, index) for the first failing instance; with verdicts=True returns the codes instead
     (0 accept, 1 succinct check, 2 decider) and raises only for a d beyond the SRS."""
     H.ensure_device()
     cid = _curve(curve)
     insts = [Instance(*q) for q in instances]
-    rh = H.fe_array(rhos, len(insts)) if rhos is not None else None
+    rh, derive = H.fs_rhos(rhos, len(insts))
     _check_shapes(insts, cid)
     codes = np.zeros(len(insts), dtype=np.uint8)
     for d in sorted({q.d for q in insts}):
@@ -750,7 +769,8 @@ def check_batch(instances, rhos=None, curve="pallas", verdicts: bool = False, bi
         qs = [insts[i] for i in idx]
         C, z, v, Ls, Rs, U, c, hid, cb, wp = instance_rows(qs, d)
         codes[idx] = check_fs_codes(C, d, z, v, Ls, Rs, U, c, hiding=hid, C_bars=cb, w_primes=wp,
-                                    rhos=rh[idx] if rh is not None else None, curve=cid, bisect=bisect)
+                                    rhos="fs" if derive else rh[idx] if rh is not None else None, curve=cid,
+                                    bisect=bisect)
     if verdicts:
         return codes
     for i, c in enumerate(codes):

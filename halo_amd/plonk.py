@@ -182,10 +182,11 @@ def verify_batch(circuit: PlonkCircuit, public_inputs, acc_prevs, proofs, rhos=N
                  bisect: bool = False) -> np.ndarray:
     """PlonkProof::verify (protocol.rs:493-502) of k proofs of one circuit in one device call
     (halo_plonk_verify_batch): verify_succinct, then acc::decider of every acc_next, whose PCDL transcript runs
-    beside the proof's three instances.  rhos None: one commitment per decider; rhos (k, 4) nonzero scalars
-    drawn by the caller AFTER the proofs were fixed: one random linear combination of the deciders and one MSM,
-    with an exact rerun if it fails, or with bisect=True a bisection of the batch (pcdl.decide_batch).  Returns the k verdict bytes: the verify_succinct code
-    if nonzero, else DECIDER_SUCCINCT, DECIDER or ACCEPT."""
+    beside the proof's three instances.  rhos None: one commitment per decider; rhos "fs": one random linear
+    combination of the deciders and one MSM under weights derived on the device from the batch (pcdl.decide_rho),
+    with an exact rerun if it fails, or with bisect=True a bisection of the batch (pcdl.decide_batch); rhos (k, 4):
+    the same under the caller's nonzero scalars, drawn AFTER the proofs were fixed.  Returns the k verdict bytes:
+    the verify_succinct code if nonzero, else DECIDER_SUCCINCT, DECIDER or ACCEPT."""
     a = pack_batch(circuit, public_inputs, acc_prevs, proofs)
     k = len(proofs)
     verdict = np.zeros(k, dtype=np.uint8)
@@ -200,10 +201,10 @@ def verify_batch(circuit: PlonkCircuit, public_inputs, acc_prevs, proofs, rhos=N
     nRs = np.ascontiguousarray(np.stack([H.point_array(pi["Rs"]).reshape(lg, 8) for pi in pis]))
     nU = np.ascontiguousarray(np.stack([H.point_array(pi["U"]).reshape(8) for pi in pis]))
     nc = np.ascontiguousarray(np.stack([H.fe_array(pi["c"], 1)[0] for pi in pis]))
-    rh = H.fe_array(rhos, k) if rhos is not None else None
+    rh, derive = H.fs_rhos(rhos, k)
     H.ensure_device()
     names = ARG_ORDER[:-1]  # mds comes after acc_next's evaluation proof
-    with H.bisecting(bisect):
+    with H.bisecting(bisect), H.deriving(derive):
         H.check(H.load().halo_plonk_verify_batch(
             _curve(curve), circuit.rows, k, H.ptr(a["C_qs"]), H.ptr(a["public_inputs"]), circuit.public_input_count,
             *[H.ptr(a[name]) for name in names], H.ptr(nLs), H.ptr(nRs), H.ptr(nU), H.ptr(nc), H.ptr(a["mds"]), H.ptr(rh),

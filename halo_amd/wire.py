@@ -158,7 +158,7 @@ def check_codes(buf, rhos=None, vec: bool = False, curve="pallas", bisect: bool 
     b = _u8(buf)
     offsets, ds, _ = walk(b, vec)  # raises before any launch
     k = len(ds)
-    rh = H.fe_array(rhos, k) if rhos is not None else None
+    rh, derive = H.fs_rhos(rhos, k)  # "fs": each d derives its own weights on the device
     codes = np.zeros(k, dtype=np.uint8)
     if k == 0:
         return codes
@@ -179,16 +179,17 @@ def check_codes(buf, rhos=None, vec: bool = False, curve="pallas", bisect: bool 
         H.check(L.halo_pcdl_instances_decode_dev(cid, d, n, d_bytes.data_ptr(), len(b), d_off.data_ptr(), *ptrs,
                                                  d_ok.data_ptr(), stream))
         d_rho = dev(rh[idx]) if rh is not None else None
-        H.check(L.halo_pcdl_check_fs_batch_dev(cid, d, n, *ptrs, d_rho.data_ptr() if rh is not None else None,
-                                               d_code.data_ptr(), d_comb.data_ptr(), stream))
+        with H.deriving(derive):
+            H.check(L.halo_pcdl_check_fs_batch_dev(cid, d, n, *ptrs, d_rho.data_ptr() if rh is not None else None,
+                                                   d_code.data_ptr(), d_comb.data_ptr(), stream))
         torch.cuda.current_stream().synchronize()
-        if rh is not None and n > 1 and not int(d_comb[0]):
+        if (rh is not None or derive) and n > 1 and not int(d_comb[0]):
             # the combination was rejected: per-instance verdicts by bisection (the host form's route) or exactly
             if bisect:
                 host = [t.cpu().numpy().view(np.uint64 if t.dtype == torch.int64 else np.uint8) for t in arrays]
                 C, z, v, Ls, Rs, U, c, hid, cb, wp = host
                 got = pcdl.check_fs_codes(C, d, z, v, Ls if lg else None, Rs if lg else None, U, c, hiding=hid, C_bars=cb,
-                                          w_primes=wp, rhos=rh[idx], curve=cid, bisect=True)
+                                          w_primes=wp, rhos="fs" if derive else rh[idx], curve=cid, bisect=True)
             else:
                 H.check(L.halo_pcdl_check_fs_batch_dev(cid, d, n, *ptrs, None, d_code.data_ptr(), d_comb.data_ptr(), stream))
                 torch.cuda.current_stream().synchronize()

@@ -86,8 +86,12 @@ int halo_stream_sync(void* stream);
  * decider commits its instances in groups whose coefficient rows hold at most this many scalars; default 2^25),
  * "decide_bisect" (what the host forms of the batched decider do with a combined batch that is rejected: 0, the
  * default, decide every live instance again in exact mode; 1 bisect the batch on the device, see
- * halo_pcdl_decide_bisect_dev).  Every setting yields the same results; the parity tests pin each path with it.  The
- * reference has no counterpart (host-side knob of this backend only).  HALO_EINVAL on an unknown key. */
+ * halo_pcdl_decide_bisect_dev), "decide_rho_fs" (what a NULL rho means to the batched decider's entry points: 0, the
+ * default, exact mode; 1 combined mode with weights derived from the batch by Fiat-Shamir on the device, see
+ * halo_pcdl_decide_rho; each call reads it once, on entry).  Every setting but "decide_rho_fs" = 1 yields the same
+ * results (that one trades the exact accept of a NULL rho for the bound stated at halo_pcdl_decide_rho); the parity
+ * tests pin each path with it.  The reference has no counterpart (host-side knob of this backend only).
+ * HALO_EINVAL on an unknown key. */
 int halo_set_tuning(const char* key, long long value);
 int halo_get_tuning(const char* key, long long* value);
 
@@ -545,21 +549,27 @@ int halo_pcdl_succinct_check_fs_batch_dev(halo_curve_t curve, size_t d, size_t k
  * instances, ONE MSM whatever k.  If that fails the live instances are decided again in exact mode (or, with the
  * tuning key "decide_bisect" = 1, the batch is bisected: halo_pcdl_decide_bisect_dev), so the verdicts are always
  * per instance and exact for rejects.  An accept in combined mode is sound up to a prover
- * guessing rho (probability about k / 2^254 over a uniform choice): rho must be drawn AFTER the proofs are
- * fixed, uniformly, from the caller's random number generator -- the library draws no randomness.
+ * guessing rho (probability about k / 2^254 over a uniform choice): a rho that the caller passes must be drawn
+ * AFTER the proofs are fixed, uniformly, from the caller's random number generator.  The library draws no
+ * randomness; with the tuning key "decide_rho_fs" = 1 it derives the weights instead: rho NULL and k >= 2 then
+ * means combined mode under the weights of halo_pcdl_decide_rho (for this host form, of the live instances that
+ * travel: they are gathered first), and no generator is needed.  k = 1 stays in exact mode.
  * Before any device work: HALO_ENOTPOW2 "n ({n}) is not a power of two", HALO_EINVAL for a null required pointer,
  * an xi that is not below the modulus, a rho entry that is zero (its instance would go unchecked) or not below
- * the modulus; then HALO_ESRSRANGE "d was larger than D!".  k = 0: HALO_OK. */
+ * the modulus, with "decide_rho_fs" = 1 and rho NULL missing Poseidon parameters of the curve's base field; then
+ * HALO_ESRSRANGE "d was larger than D!".  k = 0: HALO_OK. */
 int halo_pcdl_decide_batch(halo_curve_t curve, size_t d, size_t k, const halo_fe_t* xis, const halo_wrapped_point_t* U,
                            const uint8_t* live, const halo_fe_t* rho, uint8_t* ok_out);
 /* The same over device pointers, asynchronous on `stream`, no host wait.  d_combined (1 byte, may be NULL) is
- * written only with d_rho: 1 iff the combined check held.  It never falls back: with d_combined = 0 every d_ok
- * byte is 0 and the caller calls again with d_rho NULL.  Skipped instances are still computed in exact mode (the
- * host form leaves them out).  A rho or xi that is not below the modulus gives combined = 0 / an unspecified
+ * written only in combined mode (d_rho given, or derived under "decide_rho_fs" = 1 from d_xis, d_U and d_live as
+ * they are on the device, with no host wait): 1 iff the combined check held.  It never falls back: with
+ * d_combined = 0 every d_ok byte is 0 and the caller calls again in exact mode (d_rho NULL under "decide_rho_fs" = 0)
+ * or bisects.  Skipped instances are still computed in exact mode (the host form leaves them out).  A rho or xi that is not below the modulus gives combined = 0 / an unspecified
  * verdict for its instance. */
 int halo_pcdl_decide_batch_dev(halo_curve_t curve, size_t d, size_t k, const void* d_xis, const void* d_U,
                                const void* d_live, const void* d_rho, void* d_ok, void* d_combined, void* stream);
-/* Per-instance verdicts of a weighted batch by bisection, over device pointers; d_rho is required.  The combined
+/* Per-instance verdicts of a weighted batch by bisection, over device pointers; d_rho is required unless the
+ * tuning key "decide_rho_fs" is 1, when a NULL d_rho means the weights of halo_pcdl_decide_rho_dev.  The combined
  * pass runs first; when it rejects, D(S) = sum_{i in S} rho_i U_i - Commit(sum_{i in S} rho_i h_i) is followed down
  * a binary tree over the instances (left half = the first floor(size / 2) of a node): one combined pass over the
  * left half of every failing node gives D(left), and D(right) = D(node) - D(left) is one point subtraction, so b
@@ -571,16 +581,47 @@ int halo_pcdl_decide_batch_dev(halo_curve_t curve, size_t d, size_t k, const voi
  * rejected before the first pass and weighs nothing in any node; U = (0, 0) is a legal point and is decided.
  * Soundness: a reject is exact (a single instance has D != 0 iff it is wrong, because rho_i != 0).  An accept of
  * any subset is sound up to a prover guessing rho: the union bound over the at most 2 k - 1 nodes of the tree
- * gives about 2 k / 2^254 for rho drawn uniformly after the proofs are fixed.  k = 1 is exact mode.
+ * gives about 2 k / 2^254 for rho drawn uniformly after the proofs are fixed (for derived weights, Q 2 k / 2^254
+ * over Q batches tried).  k = 1 is exact mode.
  * The host forms halo_pcdl_decide_batch, halo_pcdl_check_fs_batch and halo_plonk_verify_batch take this route for
  * a rejected combined batch when the tuning key "decide_bisect" is 1 (the default 0 keeps the exact rerun).
- * Errors: those of halo_pcdl_decide_batch_dev, and HALO_EINVAL for a null d_rho. */
+ * Errors: those of halo_pcdl_decide_batch_dev, and HALO_EINVAL for a null d_rho under "decide_rho_fs" = 0. */
 int halo_pcdl_decide_bisect_dev(halo_curve_t curve, size_t d, size_t k, const void* d_xis, const void* d_U,
                                 const void* d_live, const void* d_rho, void* d_ok, void* stream);
+/* The weights of the combined decider derived from the batch itself by Fiat-Shamir, on the device: what a NULL rho
+ * means to the calls above and to halo_plonk_verify_batch under the tuning key "decide_rho_fs" = 1, so that a caller
+ * brings no random number generator and two runs over the same batch give the same verdicts.  xis, U, live as in
+ * halo_pcdl_decide_batch; rho_out: k scalars of `curve`.
+ * The decider's statement for instance i is "U_i == Commit(Gs[0..d], h(xi_(i,1..lg n)))", so the batch is d, k, the
+ * live mask and the pairs (U_i, xi_(i,1..lg n)); xi_(i,0) is not hashed, and nothing of an instance that is not
+ * live is read.  All hashing is the curve's Fiat-Shamir sponge (Sponge<P> of outer_sponge.rs: Poseidon over the
+ * base field, absorb_g, absorb_fr, challenge) under three protocol labels BATCH_LEAF = 4, BATCH_SEED = 5,
+ * BATCH_WEIGHT = 6 that continue the reference's 0..3.  THE LABELS AND THE DERIVATION ARE THIS BACKEND'S OWN: the
+ * reference has no batched decider.
+ *   leaf_i   live: a sponge with label 4 does absorb_g(U_i), absorb_fr(xi_(i,1)), ..., absorb_fr(xi_(i,lg n)); the
+ *            leaf is its inner sponge's squeeze(), a base-field element.  Not live: the element 0.
+ *   tree     level 0 is the k leaves; level l+1 [j] = N(level l [2j], level l [2j+1]) if 2j+1 < count, else
+ *            level l [2j] unchanged, until one element, the root, remains.  N(a, b): a fresh unlabelled inner
+ *            sponge absorbs a, then b, and squeezes once.  The shape is fixed by k, which the seed binds.
+ *   seed     a sponge with label 5 whose inner sponge absorbs root, k, d (the integers as field elements), squeezed once.
+ *   rho_i    live: a sponge with label 6 whose inner sponge absorbs seed, i; challenge() is the weight, and a
+ *            result of 0 (probability about 2^-254) is replaced by 1.  Not live: 0.
+ * Soundness: in the random-oracle model each rho_i is an independent uniform function of the whole statement.  An
+ * accept is sound up to a prover who tries Q batches and finds one whose weights cancel, about Q k / 2^254; for the
+ * bisection the bound is Q 2 k / 2^254.  A reject stays exact.
+ * Before any device work: the argument errors of halo_pcdl_decide_batch (an xi not below the modulus included) and
+ * HALO_EINVAL without Poseidon parameters for the curve's base field.  No SRS is needed.  k = 0: HALO_OK; k = 1
+ * gives a weight like any other k. */
+int halo_pcdl_decide_rho(halo_curve_t curve, size_t d, size_t k, const halo_fe_t* xis, const halo_wrapped_point_t* U,
+                         const uint8_t* live, halo_fe_t* rho_out);
+/* The same over device pointers, asynchronous on `stream`: 2 + ceil(lg k) launches and no host wait.  An xi that is
+ * not below the modulus is hashed as its residue. */
+int halo_pcdl_decide_rho_dev(halo_curve_t curve, size_t d, size_t k, const void* d_xis, const void* d_U,
+                             const void* d_live, void* d_rho_out, void* stream);
 /* pcdl::check (pcdl.rs:563-583) for k raw instances: halo_pcdl_succinct_check_fs_batch, then the decider above
  * with live = the succinct verdicts, the challenges never leaving the device.  The inputs and errors of
- * halo_pcdl_succinct_check_fs_batch, plus rho (NULL: exact mode) with the rule and the errors of
- * halo_pcdl_decide_batch.  ok_out[i]: 0 accept, 1 the succinct check failed ("C_(log_n) != CM.Commit_Sigma(c || v')"),
+ * halo_pcdl_succinct_check_fs_batch, plus rho (NULL: exact mode, or under "decide_rho_fs" = 1 derived weights,
+ * with the device's own succinct verdicts as the live mask) with the rule and the errors of halo_pcdl_decide_batch.  ok_out[i]: 0 accept, 1 the succinct check failed ("C_(log_n) != CM.Commit_Sigma(c || v')"),
  * 2 the decider failed ("U != CM.Commit(ck, h_vec)"). */
 int halo_pcdl_check_fs_batch(halo_curve_t curve, size_t d, size_t k,
         const halo_wrapped_point_t* C, const halo_fe_t* z, const halo_fe_t* v,
@@ -589,8 +630,8 @@ int halo_pcdl_check_fs_batch(halo_curve_t curve, size_t d, size_t k,
         const uint8_t* hiding, const halo_wrapped_point_t* C_bar, const halo_fe_t* w_prime,
         const halo_fe_t* rho, uint8_t* ok_out);
 /* The same over device pointers, asynchronous on `stream`; d_combined as in halo_pcdl_decide_batch_dev: with
- * d_rho and d_combined = 0 the codes 2 are not verdicts (every instance that passed the succinct check has one)
- * and the caller calls again with d_rho NULL. */
+ * d_rho (or derived weights) and d_combined = 0 the codes 2 are not verdicts (every instance that passed the
+ * succinct check has one) and the caller calls again in exact mode (d_rho NULL under "decide_rho_fs" = 0). */
 int halo_pcdl_check_fs_batch_dev(halo_curve_t curve, size_t d, size_t k, const void* d_C, const void* d_z,
         const void* d_v, const void* d_Ls, const void* d_Rs, const void* d_U, const void* d_c, const void* d_hiding,
         const void* d_C_bar, const void* d_w_prime, const void* d_rho, void* d_ok, void* d_combined, void* stream);
@@ -657,7 +698,8 @@ int halo_plonk_verify_succinct_batch_dev(halo_curve_t curve, size_t rows, size_t
  * acc::decider of acc_next, i.e. pcdl::check of (acc_next.C, d, acc_next.z, acc_next.v) with
  * acc_next.pi = acc_next_{Ls[i lg n + j], Rs[i lg n + j], U[i], c[i]}.  acc_next's PCDL transcript runs as a fourth
  * instance per proof inside the same chain of launches; the deciders follow as in halo_pcdl_decide_batch, over
- * the proofs whose verdict is still HALO_PLONK_ACCEPT, with rho (NULL: exact mode) under that call's rule and
+ * the proofs whose verdict is still HALO_PLONK_ACCEPT, with rho (NULL: exact mode, or under the tuning key
+ * "decide_rho_fs" = 1 the derived weights of halo_pcdl_decide_rho_dev over those proofs) under that call's rule and
  * errors.  verdict[i] is the verify_succinct code if that is nonzero, else HALO_PLONK_DECIDER_SUCCINCT,
  * HALO_PLONK_DECIDER or HALO_PLONK_ACCEPT.  A point of acc_next.pi that is neither (0, 0) nor on the curve gives
  * HALO_PLONK_DECIDER_SUCCINCT.  The errors of halo_plonk_verify_succinct_batch, acc_next_c included. */
@@ -671,9 +713,10 @@ int halo_plonk_verify_batch(halo_curve_t curve, size_t rows, size_t k,
         const halo_wrapped_point_t* acc_next_Ls, const halo_wrapped_point_t* acc_next_Rs,
         const halo_wrapped_point_t* acc_next_U, const halo_fe_t* acc_next_c,
         const halo_fe_t* mds, const halo_fe_t* rho, uint8_t* verdict);
-/* The same over device pointers, asynchronous on `stream`.  d_combined (1 byte, may be NULL) is written only with
- * d_rho; with d_combined = 0 every proof that reached the decider reports HALO_PLONK_DECIDER and the caller calls
- * again with d_rho NULL (it never falls back). */
+/* The same over device pointers, asynchronous on `stream`.  d_combined (1 byte, may be NULL) is written only in
+ * combined mode (d_rho, or derived weights); with d_combined = 0 every proof that reached the decider reports
+ * HALO_PLONK_DECIDER and the caller calls again in exact mode, d_rho NULL under "decide_rho_fs" = 0 (it never
+ * falls back). */
 int halo_plonk_verify_batch_dev(halo_curve_t curve, size_t rows, size_t k,
         const void* d_C_qs, const void* d_public_inputs, size_t npi, const void* d_C_ws, const void* d_C_z,
         const void* d_C_ts, const void* d_vs, const void* d_Ls, const void* d_Rs, const void* d_U, const void* d_c,

@@ -7,6 +7,7 @@ same session.  DESIGN §4.9 records the numbers.
                                   [--budget-ms 4000] [--loop-max 256] [--modes combined]
     python tools/bench_decider.py --ks 64,4096 --out profiles/decider_bisect_bench.json --alternations 3 \
                                   --modes combined,combined_one_bad,bisect_one_bad,bisect_all_bad,one_bad_alternated
+    python tools/bench_decider.py --ks 64,4096 --out profiles/decider_rho_bench.json --modes combined,derived,derived_alternated
 
 Per lg n and k:
   * exact mode and combined mode (all valid): the event-timed median of the _dev call (inputs resident) and the
@@ -20,7 +21,12 @@ Per lg n and k:
     beside exact mode on the same batch;
   * "one_bad_alternated": the two one-bad routes (key off, key on) alternated --alternations times, each a median,
     and whether their ranges are apart.
-A library without the key (HALO_LIB pointing at an older build) can run every mode that does not set it.
+  * "derived" (k > 1): combined mode under the weights the device derives from the batch (tuning key decide_rho_fs = 1,
+    rho NULL): the _dev call, the host-array call, the stages with "decide_rho" (the span of the derivation) and its
+    kernels "rho_leaves", "rho_level" (ceil(lg k) launches), "rho_weights", and halo_pcdl_decide_rho_dev on its own;
+    "derived_alternated": the _dev call with the caller's rho and with derived weights alternated --alternations
+    times, each a median.
+A library without a key (HALO_LIB pointing at an older build) can run every mode that does not set it.
 Medians of --reps calls after warm-up; a call that takes longer than --budget-ms is repeated fewer times (at
 least twice; the count is recorded).  The parent's loop over more than --loop-max instances is measured over
 --loop-max of them and scaled, which the entry says.  The xi rows are random; min(k, 64) of them are distinct and
@@ -42,11 +48,12 @@ for p in (ROOT, os.path.join(ROOT, "oracle"), os.path.dirname(os.path.abspath(__
 import torch  # noqa: E402
 
 from halo_amd import _lib as H  # noqa: E402
-from halo_amd import group, pcdl  # noqa: E402
+from halo_amd import group, pcdl, schnorr  # noqa: E402
 
 from bench_pcdl_check import dev, scalars  # noqa: E402
 
-STAGES = ("hpoly_rows", "hpoly_combine", "hpoly_segments", "lincomb_terms", "decide_msm")
+STAGES = ("hpoly_rows", "hpoly_combine", "hpoly_segments", "lincomb_terms", "decide_msm", "decide_rho", "rho_leaves",
+          "rho_level", "rho_weights")
 
 
 def median_ms(fn, reps, budget_ms, events):
@@ -111,6 +118,10 @@ def main():
     L = H.load()
     lgs = [int(x) for x in a.lgs.split(",")]
     group.PublicParams.synthesize("pallas", 1 << max(lgs), 7, precompute_windows=True)
+    if modes & {"derived", "derived_alternated"}:
+        tr = np.load(os.path.join(ROOT, "tests", "golden", "transcript.npz"))
+        for f in ("fp", "fq"):
+            schnorr.set_poseidon_params(f, tr[f"poseidon_{f}_mds"], tr[f"poseidon_{f}_rc"])
     sp = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     dp = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
     rng = np.random.default_rng(14)
@@ -162,6 +173,27 @@ def main():
                                      "host_wall": median_ms(lambda: host_call(True, U), a.reps, a.budget_ms, False),
                                      "stages": stages(L, lambda: dev_call(True))}
                 assert ok.tolist() == [1] * k and (k == 1 or int(d_c.cpu()[0]) == 1)
+            if "derived" in modes and k > 1:
+                d_w = torch.zeros((k, 4), dtype=torch.int64, device="cuda")
+
+                def rho_call():
+                    H.check(L.halo_pcdl_decide_rho_dev(H.PALLAS, d, k, dp(d_x), dp(d_U), None, dp(d_w), sp))
+
+                with H.deriving(True):
+                    entry["derived"] = {"dev_event": median_ms(lambda: dev_call(False), a.reps, a.budget_ms, True),
+                                        "host_wall": median_ms(lambda: host_call(False, U), a.reps, a.budget_ms, False),
+                                        "stages": stages(L, lambda: dev_call(False))}
+                assert ok.tolist() == [1] * k and int(d_c.cpu()[0]) == 1
+                entry["derived"]["decide_rho_dev_event"] = median_ms(rho_call, a.reps, a.budget_ms, True)
+                assert np.array_equal(d_w.cpu().numpy().view(np.uint64), pcdl.decide_rho(xis, U, d, curve="pallas"))
+            if "derived_alternated" in modes and k > 1:
+                runs = {"caller_rho": [], "derived": []}
+                for _ in range(a.alternations):
+                    for name, key in (("caller_rho", 0), ("derived", 1)):
+                        with H.tuning(decide_rho_fs=key):
+                            runs[name].append(median_ms(lambda: dev_call(key == 0), a.reps, a.budget_ms, True)["ms_median"])
+                        assert int(d_c.cpu()[0]) == 1
+                entry["derived_alternated"] = runs
             if "combined_one_bad" in modes:
                 entry["combined_one_bad"] = {"host_wall": median_ms(lambda: host_call(True, bad), a.reps, a.budget_ms, False),
                                              "stages": stages(L, lambda: host_call(True, bad))}

@@ -9,7 +9,8 @@
 //                  a base-field element; the element 0, with nothing read, for an instance that is not live
 //   k_rho_level    level l + 1 [j] = N(level l [2 j], level l [2 j + 1]), or level l [2 j] unchanged when it is alone;
 //                  N(a, b): a fresh unlabelled inner sponge absorbs a, b and squeezes once.  ceil(lg k) launches
-//                  between two buffers, until the root remains
+//                  between two buffers, until the root remains (rho_tree_device, which the weights of a combined
+//                  Schnorr batch share: schnorr_combined.hip)
 //   k_rho_weights  seed = squeeze of Sponge(BATCH_SEED) after root, k, d (recomputed by every sponge: two
 //                  permutations, cheaper than a launch); rho_i = challenge of Sponge(BATCH_WEIGHT) after seed, i,
 //                  zero replaced by one; rho_i = 0 for an instance that is not live
@@ -27,13 +28,6 @@
 #include "sponge_launch.hpp"
 
 namespace halo {
-
-// a small integer (k, d, an index) as a base-field element
-template <class F>
-HALO_DEV Fe<F> rho_int_element(uint64_t x) {
-    const uint32_t e[8] = {(uint32_t)x, (uint32_t)(x >> 32), 0u, 0u, 0u, 0u, 0u, 0u};
-    return poseidon::fe_from_canonical_words<F>(e);
-}
 
 template <class Cv, int LANES>
 __global__ __launch_bounds__(256) void k_rho_leaves(const uint32_t* __restrict__ params, const uint4* __restrict__ xis,
@@ -120,7 +114,7 @@ __global__ __launch_bounds__(256) void k_rho_weights(const uint32_t* __restrict_
             else if (e == 1)
                 x = out;
             else
-                x = rho_int_element<F>(phase == 1 ? (uint64_t)ic : e == 2 ? (uint64_t)k : (uint64_t)d);
+                x = poseidon::fe_from_u64<F>(phase == 1 ? (uint64_t)ic : e == 2 ? (uint64_t)k : (uint64_t)d);
             sp.absorb(x);
         }
         out = sp.inner.squeeze();
@@ -133,6 +127,26 @@ __global__ __launch_bounds__(256) void k_rho_weights(const uint32_t* __restrict_
         for (int q = 0; q < 8; q++) w[q] = 0;
     }
     if (writer && i < k) poseidon::scalar_words_to_ark<S>(rho + 2 * i, w);
+}
+
+int rho_tree_device(DeviceState* st, int curve, const uint32_t* params, uint4* const (&buf)[2], size_t k, hipStream_t s,
+                    int* root_at) {
+    int cur = 0;
+    for (size_t count = k; count > 1; count = rho_next_level(count), cur ^= 1) {
+        const size_t nodes = rho_next_level(count);
+        const int lanes = poseidon_lanes(st, nodes);
+        const HashGrid g = hash_grid(nodes, lanes);
+        ProfScope prof("rho_level", s);
+        DISPATCH_CURVE(curve, Cv, {
+            DISPATCH_LANES(lanes, L, {
+                HALO_LAUNCH(prof, (k_rho_level<typename Cv::Base, L>), dim3(g.blocks), dim3(g.threads), 0, s, params,
+                            (const uint4*)buf[cur], count, buf[cur ^ 1]);
+            });
+        });
+        HALO_HIP(hipGetLastError());
+    }
+    *root_at = cur;
+    return HALO_OK;
 }
 
 int decide_rho_device(DeviceState* st, int curve, size_t d, size_t k, const void* xis, const void* U, const void* live,
@@ -160,19 +174,7 @@ int decide_rho_device(DeviceState* st, int curve, size_t d, size_t k, const void
         HALO_HIP(hipGetLastError());
     }
     int cur = 0;
-    for (size_t count = k; count > 1; count = rho_next_level(count), cur ^= 1) {
-        const size_t nodes = rho_next_level(count);
-        const int lanes = poseidon_lanes(st, nodes);
-        const HashGrid g = hash_grid(nodes, lanes);
-        ProfScope prof("rho_level", s);
-        DISPATCH_CURVE(curve, Cv, {
-            DISPATCH_LANES(lanes, L, {
-                HALO_LAUNCH(prof, (k_rho_level<typename Cv::Base, L>), dim3(g.blocks), dim3(g.threads), 0, s, params,
-                            (const uint4*)buf[cur], count, buf[cur ^ 1]);
-            });
-        });
-        HALO_HIP(hipGetLastError());
-    }
+    HALO_CHECK(rho_tree_device(st, curve, params, buf, k, s, &cur));
     {
         const int lanes = poseidon_lanes(st, k);
         const HashGrid g = hash_grid(k, lanes);

@@ -56,6 +56,12 @@ int decide_resolved(DeviceState* st, const DecideCall& a, hipStream_t s);
 // the curve's base field installed, d + 1 a power of two.  Works in st->decide_rho[1].
 int decide_rho_device(DeviceState* st, int curve, size_t d, size_t k, const void* xis, const void* U, const void* live,
                       void* rho_out, hipStream_t s);
+// The hash tree above k >= 1 leaves (k_rho_level; shared with the weights of a combined Schnorr batch,
+// schnorr_combined.hip): the leaves as k packed base-field elements in buf[0], buf[1] of rho_next_level(k) elements;
+// ceil(lg k) launches on `s` between the two, the root then the first element of buf[*root_at].  params: the device's
+// Poseidon parameters of the curve's base field.
+int rho_tree_device(DeviceState* st, int curve, const uint32_t* params, uint4* const (&buf)[2], size_t k, hipStream_t s,
+                    int* root_at);
 // a.derive, no rho and k >= 2: derives the weights into st->decide_rho[0] and makes them a.rho.  Else nothing.
 int decide_rho_weights(DeviceState* st, DecideCall& a, hipStream_t s);
 

@@ -27,6 +27,11 @@ private:
     explicit MsmOpts(bool a) : async(a) {}
 };
 
+// The largest n msm_device takes.  Its sort holds the 2 n GLV half-scalars of every window as 32-bit entries and
+// counts them in 32 bits: W 2 n < 2^32 with W = ceil(129 / c) = 9 windows of c = 16 bits (msm_window_bits from 2^19
+// points up).  The 31-bit entry values (2 n < 2^31) are the weaker bound.
+constexpr size_t MSM_DEVICE_MAX_N = 0xffffffffull / 18;  // 238 609 294
+
 // MSM over device-resident internal-format affine bases (64 B each) and ark-format scalars.
 // Writes one ark WrappedPoint (64 B) to d_out_wrapped (device).  Optional hiding term
 // hide_scalar * P where hide_table = {2^i P : i < 256} (internal affine; both device pointers).

@@ -34,6 +34,13 @@ HALO_DEV Fe<F> fe_from_canonical_words(const uint32_t (&w)[8]) {
     return fe_mul(fe_unpack<F>(w), fe_from_const<F>(F::R2));
 }
 
+// a small integer (a count, an index) as a field element
+template <class F>
+HALO_DEV Fe<F> fe_from_u64(uint64_t x) {
+    const uint32_t e[8] = {(uint32_t)x, (uint32_t)(x >> 32), 0u, 0u, 0u, 0u, 0u, 0u};
+    return fe_from_canonical_words<F>(e);
+}
+
 template <class Cv, int LANES>
 struct OuterSponge {
     using F = typename Cv::Base;

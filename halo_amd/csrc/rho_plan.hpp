@@ -19,6 +19,9 @@ namespace halo {
 // The protocol labels of the three sponges.  They continue Protocols::{PCDL, ASDL, PLONK, SIGNATURE} = 0..3 of
 // the reference (outer_sponge.rs:17-22) and are this backend's own: the reference has no batched decider.
 constexpr int RHO_BATCH_LEAF = 4, RHO_BATCH_SEED = 5, RHO_BATCH_WEIGHT = 6;
+// ... and of the weights of a combined Schnorr batch (schnorr_combined.hip), which share the tree above the leaves.
+// This backend's own as well: the reference has no batched signature verification.
+constexpr int SIG_BATCH_LEAF = 7, SIG_BATCH_SEED = 8, SIG_BATCH_WEIGHT = 9;
 
 // Elements of level l + 1 of the tree from those of level l: pairs are hashed, an element left alone is promoted.
 inline size_t rho_next_level(size_t count) { return (count + 1) / 2; }

@@ -258,7 +258,7 @@ int halo_init(int device) {
 
 const char* halo_last_error(void) { return g_last_error.c_str(); }
 
-int halo_abi_version(void) { return 111; }
+int halo_abi_version(void) { return 112; }
 
 // Releases the library's HIP objects while the runtime is alive: pending profiling events, the MSM
 // pipeline's streams and events, the scratch fence events.  Python registers it with atexit

@@ -125,7 +125,9 @@ struct DeviceState {
     uint64_t poseidon_ver[2] = {0, 0};
     DevBuf schnorr_gtab[2];  // per curve: d G and phi(d G), 1 <= d <= 8, XYZZ (the fixed-base table of s G)
     DevBuf schnorr_e;        // the challenges of a verification batch (canonical words)
-    DevBuf lincomb_terms;    // the terms of a batch of linear combinations (lincomb.hip): packed XYZZ, then a byte each
+    // schnorr_combined.hip: the combined pass's e, liveness, derived weights, MSM terms and outputs; the hash tree
+    DevBuf schnorr_comb[2];
+    DevBuf lincomb_terms;   // the terms of a batch of linear combinations (lincomb.hip): packed XYZZ, then a byte each
     DevBuf decider[4];       // decider.hip: h rows / coefficients, half-tables, U' and masks, the xis of a check
     DevBuf bisect[3];        // decider.hip's descent: segment rows, the root's terms, node tables / commitments / defects
     DevBuf decide_rho[2];    // decide_rho.hip: the derived weights (no reserve of decider[] or bisect[] moves them), the hash tree

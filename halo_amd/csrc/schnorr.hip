@@ -15,6 +15,7 @@
 #include "poseidon.hpp"
 #include "quad_ladder.hpp"
 #include "runtime.hpp"
+#include "schnorr.hpp"
 #include "sponge_launch.hpp"
 #include "tree.hpp"
 
@@ -282,8 +283,8 @@ static int poseidon_hash_device(DeviceState* st, int field, const void* d_in, si
     return HALO_OK;
 }
 
-static int schnorr_hash_device(DeviceState* st, int curve, const void* d_pk, const void* d_R, const void* d_msgs,
-                               size_t msg_len, size_t k, void* d_e_ark, void* d_e_words, hipStream_t s) {
+int schnorr_hash_device(DeviceState* st, int curve, const void* d_pk, const void* d_R, const void* d_msgs, size_t msg_len,
+                        size_t k, void* d_e_ark, void* d_e_words, hipStream_t s) {
     const uint32_t* params;
     HALO_CHECK(poseidon_device_params(st, base_field(curve), &params));
     const int lanes = poseidon_lanes(st, k);
@@ -298,9 +299,9 @@ static int schnorr_hash_device(DeviceState* st, int curve, const void* d_pk, con
     return HALO_OK;
 }
 
-// Hash into st->schnorr_e, then the ladder.  st->mu and a ScratchUse of `s` held by the caller.
-static int schnorr_verify_device(DeviceState* st, int curve, const void* d_pk, const void* d_R, const void* d_s,
-                                 const void* d_msgs, size_t msg_len, size_t k, void* d_ok, hipStream_t s) {
+// The ladder over challenges already on the device (e_words: k_schnorr_hash's canonical words).  st->mu held.
+int schnorr_ladder_device(DeviceState* st, int curve, const void* d_pk, const void* d_R, const void* d_s,
+                          const void* d_e_words, size_t k, void* d_ok, hipStream_t s) {
     DevBuf& gt = st->schnorr_gtab[curve];
     if (!gt.ptr) {
         HALO_CHECK(gt.reserve(GTAB_U4 * sizeof(uint4)));
@@ -313,16 +314,35 @@ static int schnorr_verify_device(DeviceState* st, int curve, const void* d_pk, c
                              hipGetErrorString(e));
         }
     }
-    HALO_CHECK(st->schnorr_e.reserve(k * 32));
-    HALO_CHECK(schnorr_hash_device(st, curve, d_pk, d_R, d_msgs, msg_len, k, nullptr, st->schnorr_e.ptr, s));
     const unsigned blocks = (unsigned)((4 * k + VERIFY_THREADS - 1) / VERIFY_THREADS);
     DISPATCH_CURVE(curve, Cv, {
         hipLaunchKernelGGL(k_schnorr_verify<Cv>, dim3(blocks), dim3(VERIFY_THREADS), VERIFY_LDS, s, (const uint4*)d_pk,
-                           (const uint4*)d_R, (const uint4*)d_s, st->schnorr_e.as<const uint4>(), gt.as<const uint4>(), k,
+                           (const uint4*)d_R, (const uint4*)d_s, (const uint4*)d_e_words, gt.as<const uint4>(), k,
                            (uint8_t*)d_ok);
     });
     HALO_HIP(hipGetLastError());
     return HALO_OK;
+}
+
+// Hash into st->schnorr_e, then the ladder.  st->mu and a ScratchUse of `s` held by the caller.
+static int schnorr_verify_device(DeviceState* st, int curve, const void* d_pk, const void* d_R, const void* d_s,
+                                 const void* d_msgs, size_t msg_len, size_t k, void* d_ok, hipStream_t s) {
+    HALO_CHECK(st->schnorr_e.reserve(k * 32));
+    HALO_CHECK(schnorr_hash_device(st, curve, d_pk, d_R, d_msgs, msg_len, k, nullptr, st->schnorr_e.ptr, s));
+    return schnorr_ladder_device(st, curve, d_pk, d_R, d_s, st->schnorr_e.ptr, k, d_ok, s);
+}
+
+int check_schnorr_args(const char* call, int curve, const void* pk, const void* R, const void* s, bool need_s,
+                       const void* msgs, size_t msg_len, size_t k, const void* out, bool& done) {
+    done = false;
+    if (!valid_curve(curve)) return set_error(HALO_EINVAL, "%s: unknown curve", call);
+    if (k == 0) {
+        done = true;
+        return HALO_OK;
+    }
+    if (!pk || !R || (need_s && !s) || !out || (msg_len && !msgs)) return set_error(HALO_EINVAL, "%s: null pointer", call);
+    if (msg_len > (SIZE_MAX / 32) / k) return set_error(HALO_EINVAL, "%s: msg_len * k overflows", call);
+    return require_poseidon_params(call, curve);
 }
 
 }  // namespace halo
@@ -387,19 +407,6 @@ extern "C" int halo_poseidon_hash_batch_dev(halo_field_t field, const void* d_in
     if (!st) return HALO_EDEVICE;
     std::lock_guard<std::mutex> g(st->mu);
     return poseidon_hash_device(st, field, d_in, len, k, d_out, (hipStream_t)stream);
-}
-
-static int check_schnorr_args(const char* call, halo_curve_t curve, const void* pk, const void* R, const void* s,
-                              bool need_s, const void* msgs, size_t msg_len, size_t k, const void* out, bool& done) {
-    done = false;
-    if (!valid_curve(curve)) return set_error(HALO_EINVAL, "%s: unknown curve", call);
-    if (k == 0) {
-        done = true;
-        return HALO_OK;
-    }
-    if (!pk || !R || (need_s && !s) || !out || (msg_len && !msgs)) return set_error(HALO_EINVAL, "%s: null pointer", call);
-    if (msg_len > (SIZE_MAX / 32) / k) return set_error(HALO_EINVAL, "%s: msg_len * k overflows", call);
-    return require_poseidon_params(call, curve);
 }
 
 extern "C" int halo_schnorr_hash_batch(halo_curve_t curve, const halo_wrapped_point_t* pk, const halo_wrapped_point_t* R,

@@ -483,6 +483,54 @@ int halo_schnorr_verify_batch(halo_curve_t curve, const halo_wrapped_point_t* pk
  * call per device and curve builds the generator's table and waits for it). */
 int halo_schnorr_verify_batch_dev(halo_curve_t curve, const void* d_pk, const void* d_R, const void* d_s,
                                   const void* d_msgs, size_t msg_len, size_t k, void* d_ok, void* stream);
+/* The same k verifications as ONE MSM under random weights, the method of halo_pcdl_decide_batch's combined mode
+ * (opt-in; the calls above and their results are unchanged).  For weights rho_i all of s_i G == R_i + e_i pk_i hold
+ * iff D = (sum rho_i s_i) G - sum rho_i R_i - sum (rho_i e_i) pk_i is the identity, up to the bound below; Pallas and
+ * Vesta have cofactor 1, so no subgroup caveat applies.  D is one MSM of 2 k + 1 terms whatever k, where the exact
+ * call runs k ladders; each e_i is hashed once.  Item i is live iff pk_i and R_i are each (0, 0) or on the curve
+ * (the rule above): an item that is not live has verdict 0 and weighs nothing in D; (0, 0) is a legal point and
+ * takes part.  k is at most 119 304 646: the 2 k + 1 terms must not exceed 238 609 294 = floor((2^32 - 1) / 18), the
+ * largest MSM over caller bases (its sort counts 9 windows of 2 (2 k + 1) GLV half-scalars in 32 bits).
+ * rho: k scalars of `curve`, or NULL for the weights of halo_schnorr_batch_rho (no generator needed).
+ * If the combined pass holds, ok_out[i] = live_i and *combined_out (may be NULL) = 1.  If it fails, the live items
+ * are decided by the exact ladder over the e already on the device and *combined_out = 0: the verdicts are always
+ * per item and exact for rejects.  For s below the modulus they equal halo_schnorr_verify_batch's.
+ * Soundness: a rho that the caller passes must be drawn uniformly, from the caller's random number generator, AFTER
+ * the signatures are fixed (with rho known in advance, errors that cancel pass: s_0 + x, s_1 - x under rho = (1, 1)).
+ * An accept is then sound up to a signer guessing rho, probability about k / 2^254; for derived weights about
+ * Q k / 2^254 over Q batches tried.  A reject is exact.
+ * Before any device work: the errors of halo_schnorr_verify_batch, HALO_EINVAL for a k above the bound and for a
+ * rho entry that is zero (its item would go unchecked) or not below the modulus.  k = 0: HALO_OK, nothing touched. */
+int halo_schnorr_verify_combined(halo_curve_t curve, const halo_wrapped_point_t* pk, const halo_wrapped_point_t* R,
+                                 const halo_fe_t* s, const halo_fe_t* msgs, size_t msg_len, size_t k, const halo_fe_t* rho,
+                                 uint8_t* ok_out, uint8_t* combined_out);
+/* The combined pass over device pointers, asynchronous on `stream`, no host wait; d_rho NULL: derived weights, from
+ * the inputs as they are on the device.  d_ok[i] = live_i && combined; d_combined (1 byte, may be NULL) = 1 iff the
+ * pass held.  It never falls back: with combined = 0 every d_ok byte is 0 and the caller runs
+ * halo_schnorr_verify_batch_dev.  A live item whose rho is zero or not below the modulus gives combined = 0. */
+int halo_schnorr_verify_combined_dev(halo_curve_t curve, const void* d_pk, const void* d_R, const void* d_s,
+                                     const void* d_msgs, size_t msg_len, size_t k, const void* d_rho, void* d_ok,
+                                     void* d_combined, void* stream);
+/* The weights that a NULL rho means above, derived from the batch itself by Fiat-Shamir on the device, as
+ * halo_pcdl_decide_rho derives the decider's: rho_out is k scalars of `curve`, and two runs over one batch agree.
+ * All hashing is the curve's sponge (Sponge<P> of outer_sponge.rs) under three protocol labels SIG_BATCH_LEAF = 7,
+ * SIG_BATCH_SEED = 8, SIG_BATCH_WEIGHT = 9 that continue halo_pcdl_decide_rho's 4..6.  THE LABELS AND THE DERIVATION
+ * ARE THIS BACKEND'S OWN: the reference has no batched verification.
+ *   leaf_i   live: a sponge with label 7 does absorb_fr(e_i), absorb_fr(s_i), e_i = hash_message(pk_i, R_i, m_i); the
+ *            leaf is its inner sponge's squeeze(), a base-field element.  Not live: the element 0, nothing is read.
+ *            e_i is already a collision-resistant digest of (pk_i, R_i, m_i) under SIGNATURE, so it stands for them:
+ *            hashing the points and the message a second time would double the dominant cost of the batch.
+ *   tree     that of halo_pcdl_decide_rho over the k leaves: N(a, b) a fresh unlabelled inner sponge, an odd node
+ *            carried up unchanged.
+ *   seed     a sponge with label 8 whose inner sponge absorbs root, k, msg_len, squeezed once.
+ *   rho_i    live: a sponge with label 9 whose inner sponge absorbs seed, i; challenge() is the weight, 0 replaced by
+ *            1.  Not live: 0.
+ * Errors as for halo_schnorr_verify_combined; an s that is not below the modulus is hashed as its residue. */
+int halo_schnorr_batch_rho(halo_curve_t curve, const halo_wrapped_point_t* pk, const halo_wrapped_point_t* R,
+                           const halo_fe_t* s, const halo_fe_t* msgs, size_t msg_len, size_t k, halo_fe_t* rho_out);
+/* The same over device pointers, asynchronous on `stream`: the hash, 3 + ceil(lg k) launches, no host wait. */
+int halo_schnorr_batch_rho_dev(halo_curve_t curve, const void* d_pk, const void* d_R, const void* d_s, const void* d_msgs,
+                               size_t msg_len, size_t k, void* d_rho_out, void* stream);
 
 /* ------------------------------------------------------------------ the PCDL verifier
  * k linear combinations of t terms each, out[i] = add[i] + sum_{j < t} scalars[i t + j] pts[i t + j]

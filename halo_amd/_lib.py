@@ -141,6 +141,10 @@ SIGNATURES = {
     "halo_schnorr_verify_combined_dev": [ctypes.c_int, _vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp],
     "halo_schnorr_batch_rho": [ctypes.c_int, _vp, _vp, _vp, _vp, _sz, _sz, _vp],
     "halo_schnorr_batch_rho_dev": [ctypes.c_int, _vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp],
+    "halo_generator_mul_batch": [ctypes.c_int, _vp, _sz, _vp],
+    "halo_generator_mul_batch_dev": [ctypes.c_int, _vp, _sz, _vp, _vp],
+    "halo_schnorr_sign_batch": [ctypes.c_int, _vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp],
+    "halo_schnorr_sign_batch_dev": [ctypes.c_int, _vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp],
     "halo_point_lincomb_batch": [ctypes.c_int, _vp, _vp, _vp, _sz, _sz, _vp],
     "halo_point_lincomb_batch_dev": [ctypes.c_int, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp],
     "halo_pcdl_succinct_check_batch": [ctypes.c_int, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],

@@ -258,7 +258,7 @@ int halo_init(int device) {
 
 const char* halo_last_error(void) { return g_last_error.c_str(); }
 
-int halo_abi_version(void) { return 112; }
+int halo_abi_version(void) { return 113; }
 
 // Releases the library's HIP objects while the runtime is alive: pending profiling events, the MSM
 // pipeline's streams and events, the scratch fence events.  Python registers it with atexit
@@ -287,6 +287,7 @@ int halo_shutdown(void) {
         }
         st->scratch_used = false;
         st->scratch_last = nullptr;
+        for (DevBuf& t : st->fixed_base_tab) t.release();  // rebuilt on next use
     }
     return HALO_OK;
 }

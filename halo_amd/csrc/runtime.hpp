@@ -125,6 +125,10 @@ struct DeviceState {
     uint64_t poseidon_ver[2] = {0, 0};
     DevBuf schnorr_gtab[2];  // per curve: d G and phi(d G), 1 <= d <= 8, XYZZ (the fixed-base table of s G)
     DevBuf schnorr_e;        // the challenges of a verification batch (canonical words)
+    // fixed_base.hip: per curve the comb table d 2^(c w) G (internal affine, built on first use, released by
+    // halo_shutdown); the derived keys and challenges of a signing batch
+    DevBuf fixed_base_tab[2];
+    DevBuf schnorr_sign;
     // schnorr_combined.hip: the combined pass's e, liveness, derived weights, MSM terms and outputs; the hash tree
     DevBuf schnorr_comb[2];
     DevBuf lincomb_terms;   // the terms of a batch of linear combinations (lincomb.hip): packed XYZZ, then a byte each

@@ -1,20 +1,31 @@
-"""Mirror of crates/schnorr/src/lib.rs (hash_message, PublicKey::verify) and of the inner Poseidon
-sponge (crates/poseidon/src/inner_sponge.rs) on the MI355X backend, as batches of independent items:
-the reference's benchmark verifies 40 000 signatures in a parallel loop (crates/plonk/src/main.rs:35-47).
+"""Mirror of crates/schnorr/src/lib.rs (generate_keypair, SecretKey::sign, hash_message, PublicKey::verify) and of
+the inner Poseidon sponge (crates/poseidon/src/inner_sponge.rs) on the MI355X backend, as batches of independent
+items: the reference's benchmark verifies 40 000 signatures in a parallel loop (crates/plonk/src/main.rs:35-47).
 
 verify_batch's default is exact, one ladder per signature; with ``rhos`` it checks the whole batch by one MSM of
 2 k + 1 terms under the caller's random weights or under weights derived from the batch (batch_weights), which the
 reference does not have: an accept is then sound up to about k / 2^254, a reject is resolved exactly.
 
-Signing and key generation stay with the caller (they need its RNG).  The Poseidon constants are the
-caller's too (``PastaConfig::POSEIDON_*``): install them once per field with set_poseidon_params.
+Key derivation and signing run on the device too (public_key_batch, sign_batch: a fixed-base comb over the
+generator, halo_generator_mul_batch / halo_schnorr_sign_batch).  The library never draws randomness: secrets and
+nonces are the caller's, and where this module is asked to draw them (generate_keypairs, sign_batch without
+nonces) it does so here, from ``secrets``.  The kernels are not hardened against side channels.  The Poseidon
+constants are the caller's as well (``PastaConfig::POSEIDON_*``): install them once per field with
+set_poseidon_params.
 """
 from __future__ import annotations
+
+import secrets
 
 import numpy as np
 
 from . import _lib as H
 from .group import _curve, _field
+
+SCALAR_MODULUS = {  # ark_pallas::Fr (Pallas scalars) and ark_pallas::Fq (Vesta scalars)
+    H.PALLAS: 0x40000000000000000000000000000000224698FC0994A8DD8C46EB2100000001,
+    H.VESTA: 0x40000000000000000000000000000000224698FC094CF91B992D30ED00000001,
+}
 
 
 def set_poseidon_params(field, mds, rc) -> None:
@@ -93,3 +104,48 @@ def batch_weights(pk, R, s, msgs, curve="pallas") -> np.ndarray:
     out = np.zeros((k, 4), dtype=np.uint64)
     H.check(H.load().halo_schnorr_batch_rho(_curve(curve), H.ptr(pk), H.ptr(R), H.ptr(s), H.ptr(m), ml, k, H.ptr(out)))
     return out
+
+
+def _random_scalars(k: int, curve="pallas") -> np.ndarray:
+    """k scalars of `curve`, uniform in [1, r - 1], from the operating system's generator (``secrets``), as
+    (k, 4) ark Montgomery limbs: what generate_keypairs and sign_batch draw when the caller passes none."""
+    r = SCALAR_MODULUS[_curve(curve)]
+    out = np.zeros((k, 4), dtype=np.uint64)
+    for i in range(k):
+        v = ((secrets.randbelow(r - 1) + 1) << 256) % r
+        out[i] = [(v >> (64 * j)) & (2**64 - 1) for j in range(4)]
+    return out
+
+
+def public_key_batch(sk, curve="pallas") -> np.ndarray:
+    """lib.rs:41-43 ``generate_keypair``'s pk = sk G for k secrets the caller drew: sk (k, 4) scalars below the
+    modulus -> (k, 8) WrappedPoints; sk = 0 gives (0, 0)."""
+    H.ensure_device()
+    sk = H.fe_array(sk)
+    out = np.zeros((len(sk), 8), dtype=np.uint64)
+    H.check(H.load().halo_generator_mul_batch(_curve(curve), H.ptr(sk), len(sk), H.ptr(out)))
+    return out
+
+
+def generate_keypairs(k: int, curve="pallas"):
+    """lib.rs:38-46 ``generate_keypair`` k times: (sk (k, 4), pk (k, 8)), the secrets drawn here from ``secrets``, uniform in [1, r - 1]."""
+    sk = _random_scalars(k, curve)
+    return sk, public_key_batch(sk, curve)
+
+
+def sign_batch(sk, msgs, curve="pallas", nonces=None, pk=None):
+    """lib.rs:49-66 ``SecretKey::sign`` for k (sk[i], msgs[i]) pairs: (R (k, 8), s (k, 4)) with R = nonce G,
+    s = nonce + hash_message(pk, R, m) sk.  ``nonces``: (k, 4) scalars below the modulus, each uniform, secret and
+    used once; None draws them here from ``secrets``.  ``pk``: the keys of sk where the caller has them (hashed as
+    given); None derives pk = sk G on the device, as the reference does on every sign."""
+    H.ensure_device()
+    sk = H.fe_array(sk)
+    k = len(sk)
+    nonces = _random_scalars(k, curve) if nonces is None else H.fe_array(nonces, k)
+    pk = None if pk is None else H.point_array(pk)
+    assert pk is None or len(pk) == k
+    m, ml = _messages(msgs, k)
+    R, s = np.zeros((k, 8), dtype=np.uint64), np.zeros((k, 4), dtype=np.uint64)
+    H.check(H.load().halo_schnorr_sign_batch(_curve(curve), H.ptr(sk), H.ptr(pk), H.ptr(nonces), H.ptr(m), ml, k, H.ptr(R),
+                                             H.ptr(s)))
+    return R, s

@@ -531,6 +531,39 @@ int halo_schnorr_batch_rho(halo_curve_t curve, const halo_wrapped_point_t* pk, c
 /* The same over device pointers, asynchronous on `stream`: the hash, 3 + ceil(lg k) launches, no host wait. */
 int halo_schnorr_batch_rho_dev(halo_curve_t curve, const void* d_pk, const void* d_R, const void* d_s, const void* d_msgs,
                                size_t msg_len, size_t k, void* d_rho_out, void* stream);
+/* The signer's half of crates/schnorr/src/lib.rs, with every random scalar drawn by the CALLER: the library never
+ * draws randomness.  Both calls multiply the generator G = Affine::generator() = (-1, 2) over a fixed-base comb: a
+ * table of the affine multiples d 2^(8 w) G (1 <= d <= 128, w < 32; 256 KiB per device and curve, built on the
+ * device by the first call, which waits for it, and released by halo_shutdown), about 32 mixed additions per scalar
+ * and no doublings, then one shared inversion per workgroup for the affine results.
+ * SECRETS: the host forms zero the device staging that held the scalars before they return.  The kernels index the
+ * table by the scalars' digits, skip zero digits and branch on exceptional additions: they are NOT hardened against
+ * side channels (timing, cache).  Do not sign on a device shared with an adversary.
+ *
+ * out[i] = scalars[i] G: generate_keypair's public key (lib.rs:41-43) for caller-drawn secrets.  Scalars of `curve`
+ * (ark Montgomery limbs); 0 gives the identity (0, 0).  Needs no Poseidon parameters.
+ * Before any device work: HALO_EINVAL for an unknown curve, a null pointer, a k too large to address, and the first
+ * scalar that is not below the modulus (naming its index).  k = 0: HALO_OK, nothing touched. */
+int halo_generator_mul_batch(halo_curve_t curve, const halo_fe_t* scalars, size_t k, halo_wrapped_point_t* out);
+/* The same over device pointers, asynchronous on `stream`.  The scalars must be below the modulus: this is the
+ * caller's to ensure and is not checked (a larger value is reduced). */
+int halo_generator_mul_batch_dev(halo_curve_t curve, const void* d_scalars, size_t k, void* d_out, void* stream);
+/* SecretKey::sign (lib.rs:49-66) for k (sk, message) pairs with the nonces given: R_out[i] = nonce[i] G (affine: the
+ * hash absorbs it), e_i = hash_message(pk_i, R_i, msgs[i]) as halo_schnorr_hash_batch, s_out[i] = nonce[i] + e_i sk[i].
+ * pk NULL: pk_i = sk[i] G is derived, as the reference does on every sign (lib.rs:59).  A pk that is passed is
+ * hashed AS GIVEN: that it belongs to sk is the caller's business, and a wrong one yields signatures that do not
+ * verify.  nonce = 0 gives R = (0, 0) and sk = 0 gives pk = (0, 0): the reference's arithmetic, which
+ * halo_schnorr_verify_batch follows too.  A nonce must be uniform, secret and never reused across messages.
+ * msgs: k x msg_len base-field elements, row-major; NULL allowed only when msg_len = 0.
+ * Before any device work: HALO_EINVAL for an unknown curve, a null pointer, msg_len * k overflow, Poseidon parameters
+ * not installed, and the first sk or nonce entry that is not below the modulus (naming the array and the index).
+ * k = 0: HALO_OK, nothing touched. */
+int halo_schnorr_sign_batch(halo_curve_t curve, const halo_fe_t* sk, const halo_wrapped_point_t* pk, const halo_fe_t* nonce,
+                            const halo_fe_t* msgs, size_t msg_len, size_t k, halo_wrapped_point_t* R_out, halo_fe_t* s_out);
+/* The same over device pointers (d_pk may be NULL), asynchronous on `stream`, no host wait.  d_sk and d_nonce must be
+ * below the modulus: not checked.  The caller owns the secrets' device memory and clears it. */
+int halo_schnorr_sign_batch_dev(halo_curve_t curve, const void* d_sk, const void* d_pk, const void* d_nonce,
+                                const void* d_msgs, size_t msg_len, size_t k, void* d_R_out, void* d_s_out, void* stream);
 
 /* ------------------------------------------------------------------ the PCDL verifier
  * k linear combinations of t terms each, out[i] = add[i] + sum_{j < t} scalars[i t + j] pts[i t + j]

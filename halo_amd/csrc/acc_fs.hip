@@ -49,10 +49,7 @@ __global__ __launch_bounds__(256) void k_acc_challenges(const uint32_t* __restri
     using S = typename Cv::Scalar;
     constexpr int NS = Sp::FR_ELEMENTS;
     __shared__ uint32_t tab[poseidon::TABLE_WORDS];
-    poseidon::stage_params(params, tab);
-    bool writer;
-    const size_t i = sponge_index<LANES>(writer);
-    const size_t ic = i < k ? i : k - 1;
+    SPONGE_PROLOGUE(LANES, params, tab, k, i, ic, writer);
     xis += 2 * m * (lg + 1) * ic;
     U += 4 * m * ic;
     Sp sp;
@@ -183,17 +180,8 @@ int acc_challenges_launch(DeviceState* st, int curve, const void* d_xis, const v
                           void* d_asdl, hipStream_t s, const char* prof_name) {
     const uint32_t* params;
     HALO_CHECK(poseidon_device_params(st, base_field(curve), &params));
-    const int lanes = poseidon_lanes(st, k);
-    const HashGrid g = hash_grid(k, lanes);
-    ProfScope prof(prof_name, s);
-    DISPATCH_CURVE(curve, Cv, {
-        DISPATCH_LANES(lanes, L, {
-            HALO_LAUNCH(prof, (k_acc_challenges<Cv, L>), dim3(g.blocks), dim3(g.threads), 0, s, params, (const uint4*)d_xis,
-                        (const uint4*)d_U, lg, k, m, (uint4*)d_asdl);
-        });
-    });
-    HALO_HIP(hipGetLastError());
-    return HALO_OK;
+    return SPONGE_LAUNCH(st, curve, Cv, L, k, prof_name, s, (k_acc_challenges<Cv, L>), params, (const uint4*)d_xis,
+                         (const uint4*)d_U, lg, k, m, (uint4*)d_asdl);
 }
 
 int acc_terms_launch(int curve, const void* d_asdl, const void* d_xis, const void* d_U, const void* d_acc_C,

@@ -9,15 +9,16 @@
 //                  a base-field element; the element 0, with nothing read, for an instance that is not live
 //   k_rho_level    level l + 1 [j] = N(level l [2 j], level l [2 j + 1]), or level l [2 j] unchanged when it is alone;
 //                  N(a, b): a fresh unlabelled inner sponge absorbs a, b and squeezes once.  ceil(lg k) launches
-//                  between two buffers, until the root remains (rho_tree_device, which the weights of a combined
-//                  Schnorr batch share: schnorr_combined.hip)
-//   k_rho_weights  seed = squeeze of Sponge(BATCH_SEED) after root, k, d (recomputed by every sponge: two
-//                  permutations, cheaper than a launch); rho_i = challenge of Sponge(BATCH_WEIGHT) after seed, i,
-//                  zero replaced by one; rho_i = 0 for an instance that is not live
+//                  between two buffers, until the root remains
+//   k_rho_weights  seed = squeeze of Sponge(seed label) after root, k and a third integer (recomputed by every
+//                  sponge: two permutations, cheaper than a launch); rho_i = challenge of Sponge(weight label) after
+//                  seed, i, zero replaced by one; rho_i = 0 for an instance that is not live.  The decider's labels
+//                  are BATCH_SEED and BATCH_WEIGHT and its third integer is d
+// The tree and the weights are one driver, rho_derive_device, which the weights of a combined Schnorr batch share
+// under labels of their own (schnorr_combined.hip).
 //
 // One sponge per instance / node in either lane layout.  Each kernel walks its transcript as an element stream
-// through ONE absorb call and ONE squeeze call (outer_sponge.hpp says why).  Lanes past the batch repeat its last
-// sponge and store nothing.
+// through ONE absorb call and ONE squeeze call (outer_sponge.hpp says why).
 #include "curve.hpp"
 #include "decider.hpp"
 #include "dispatch.hpp"
@@ -38,10 +39,7 @@ __global__ __launch_bounds__(256) void k_rho_leaves(const uint32_t* __restrict__
     using S = typename Cv::Scalar;
     constexpr unsigned NS = Sp::FR_ELEMENTS;
     __shared__ uint32_t tab[poseidon::TABLE_WORDS];
-    poseidon::stage_params(params, tab);
-    bool writer;
-    const size_t i = sponge_index<LANES>(writer);
-    const size_t ic = i < k ? i : k - 1;
+    SPONGE_PROLOGUE(LANES, params, tab, k, i, ic, writer);
     const bool on = !live || live[ic] != 0;  // the row of an instance that is not live is not read
     const uint4* row = xis + 2 * (size_t)(lg + 1) * ic;
     Sp sp;
@@ -73,11 +71,8 @@ template <class F, int LANES>
 __global__ __launch_bounds__(256) void k_rho_level(const uint32_t* __restrict__ params, const uint4* __restrict__ in, size_t count,
                                                    uint4* __restrict__ out) {
     __shared__ uint32_t tab[poseidon::TABLE_WORDS];
-    poseidon::stage_params(params, tab);
     const size_t nodes = (count + 1) / 2;
-    bool writer;
-    const size_t j = sponge_index<LANES>(writer);
-    const size_t jc = j < nodes ? j : nodes - 1;
+    SPONGE_PROLOGUE(LANES, params, tab, nodes, j, jc, writer);
     const bool pair = 2 * jc + 1 < count;
     const Fe<F> a = fe_load<F>(in + 2 * (2 * jc));
     const Fe<F> b = pair ? fe_load<F>(in + 2 * (2 * jc + 1)) : fe_zero<F>();
@@ -91,15 +86,13 @@ __global__ __launch_bounds__(256) void k_rho_level(const uint32_t* __restrict__ 
 
 template <class Cv, int LANES>
 __global__ __launch_bounds__(256) void k_rho_weights(const uint32_t* __restrict__ params, const uint4* __restrict__ root, size_t k,
-                                                     size_t d, const uint8_t* __restrict__ live, uint4* __restrict__ rho) {
+                                                     int seed_label, int weight_label, size_t third,
+                                                     const uint8_t* __restrict__ live, uint4* __restrict__ rho) {
     using Sp = poseidon::OuterSponge<Cv, LANES>;
     using F = typename Cv::Base;
     using S = typename Cv::Scalar;
     __shared__ uint32_t tab[poseidon::TABLE_WORDS];
-    poseidon::stage_params(params, tab);
-    bool writer;
-    const size_t i = sponge_index<LANES>(writer);
-    const size_t ic = i < k ? i : k - 1;
+    SPONGE_PROLOGUE(LANES, params, tab, k, i, ic, writer);
     Sp sp;
     Fe<F> out = fe_load<F>(root);  // the root, then the seed, then the squeezed weight
 #pragma unroll 1
@@ -110,11 +103,11 @@ __global__ __launch_bounds__(256) void k_rho_weights(const uint32_t* __restrict_
         for (int e = 0; e < total; e++) {
             Fe<F> x;
             if (e == 0)
-                x = Sp::label_element(phase == 0 ? RHO_BATCH_SEED : RHO_BATCH_WEIGHT);
+                x = Sp::label_element(phase == 0 ? seed_label : weight_label);
             else if (e == 1)
                 x = out;
             else
-                x = poseidon::fe_from_u64<F>(phase == 1 ? (uint64_t)ic : e == 2 ? (uint64_t)k : (uint64_t)d);
+                x = poseidon::fe_from_u64<F>(phase == 1 ? (uint64_t)ic : e == 2 ? (uint64_t)k : (uint64_t)third);
             sp.absorb(x);
         }
         out = sp.inner.squeeze();
@@ -129,64 +122,36 @@ __global__ __launch_bounds__(256) void k_rho_weights(const uint32_t* __restrict_
     if (writer && i < k) poseidon::scalar_words_to_ark<S>(rho + 2 * i, w);
 }
 
-int rho_tree_device(DeviceState* st, int curve, const uint32_t* params, uint4* const (&buf)[2], size_t k, hipStream_t s,
-                    int* root_at) {
-    int cur = 0;
-    for (size_t count = k; count > 1; count = rho_next_level(count), cur ^= 1) {
-        const size_t nodes = rho_next_level(count);
-        const int lanes = poseidon_lanes(st, nodes);
-        const HashGrid g = hash_grid(nodes, lanes);
-        ProfScope prof("rho_level", s);
-        DISPATCH_CURVE(curve, Cv, {
-            DISPATCH_LANES(lanes, L, {
-                HALO_LAUNCH(prof, (k_rho_level<typename Cv::Base, L>), dim3(g.blocks), dim3(g.threads), 0, s, params,
-                            (const uint4*)buf[cur], count, buf[cur ^ 1]);
-            });
-        });
-        HALO_HIP(hipGetLastError());
-    }
-    *root_at = cur;
+int rho_buffers(DevBuf& work, size_t k, uint4* (&buf)[2]) {
+    ScratchLayout lay;
+    const size_t o_ping = lay.take(k * 32), o_pong = lay.take(rho_next_level(k) * 32);
+    HALO_CHECK(work.reserve(lay.total()));
+    uint8_t* base = work.as<uint8_t>();
+    buf[0] = (uint4*)(base + o_ping), buf[1] = (uint4*)(base + o_pong);
     return HALO_OK;
+}
+
+int rho_derive_device(DeviceState* st, int curve, const uint32_t* params, uint4* const (&buf)[2], size_t k, const RhoWeights& w,
+                      const void* live, void* rho_out, hipStream_t s) {
+    int cur = 0;
+    for (size_t count = k; count > 1; count = rho_next_level(count), cur ^= 1)
+        HALO_CHECK(SPONGE_LAUNCH(st, curve, Cv, L, rho_next_level(count), "rho_level", s, (k_rho_level<typename Cv::Base, L>), params,
+                                 (const uint4*)buf[cur], count, buf[cur ^ 1]));
+    return SPONGE_LAUNCH(st, curve, Cv, L, k, w.profile, s, (k_rho_weights<Cv, L>), params, (const uint4*)buf[cur], k, w.seed_label,
+                         w.weight_label, w.third, (const uint8_t*)live, (uint4*)rho_out);
 }
 
 int decide_rho_device(DeviceState* st, int curve, size_t d, size_t k, const void* xis, const void* U, const void* live,
                       void* rho_out, hipStream_t s) {
     const uint32_t* params;
     HALO_CHECK(poseidon_device_params(st, base_field(curve), &params));
-    const unsigned lg = ilog2(d + 1);
-    // the leaves and every second level; the levels between them
-    ScratchLayout lay;
-    const size_t o_ping = lay.take(k * 32), o_pong = lay.take(rho_next_level(k) * 32);
-    HALO_CHECK(st->decide_rho[1].reserve(lay.total()));
-    uint8_t* base = st->decide_rho[1].as<uint8_t>();
-    uint4* buf[2] = {(uint4*)(base + o_ping), (uint4*)(base + o_pong)};
+    uint4* buf[2];
+    HALO_CHECK(rho_buffers(st->decide_rho[1], k, buf));
     StageScope stage("decide_rho", s);
-    {
-        const int lanes = poseidon_lanes(st, k);
-        const HashGrid g = hash_grid(k, lanes);
-        ProfScope prof("rho_leaves", s);
-        DISPATCH_CURVE(curve, Cv, {
-            DISPATCH_LANES(lanes, L, {
-                HALO_LAUNCH(prof, (k_rho_leaves<Cv, L>), dim3(g.blocks), dim3(g.threads), 0, s, params, (const uint4*)xis,
-                            (const uint4*)U, (const uint8_t*)live, lg, k, buf[0]);
-            });
-        });
-        HALO_HIP(hipGetLastError());
-    }
-    int cur = 0;
-    HALO_CHECK(rho_tree_device(st, curve, params, buf, k, s, &cur));
-    {
-        const int lanes = poseidon_lanes(st, k);
-        const HashGrid g = hash_grid(k, lanes);
-        ProfScope prof("rho_weights", s);
-        DISPATCH_CURVE(curve, Cv, {
-            DISPATCH_LANES(lanes, L, {
-                HALO_LAUNCH(prof, (k_rho_weights<Cv, L>), dim3(g.blocks), dim3(g.threads), 0, s, params, (const uint4*)buf[cur], k, d,
-                            (const uint8_t*)live, (uint4*)rho_out);
-            });
-        });
-        HALO_HIP(hipGetLastError());
-    }
+    HALO_CHECK(SPONGE_LAUNCH(st, curve, Cv, L, k, "rho_leaves", s, (k_rho_leaves<Cv, L>), params, (const uint4*)xis, (const uint4*)U,
+                             (const uint8_t*)live, ilog2(d + 1), k, buf[0]));
+    HALO_CHECK(rho_derive_device(st, curve, params, buf, k, RhoWeights{RHO_BATCH_SEED, RHO_BATCH_WEIGHT, d, "rho_weights"}, live,
+                                 rho_out, s));
     stage.end();
     return HALO_OK;
 }

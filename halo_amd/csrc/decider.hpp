@@ -56,12 +56,22 @@ int decide_resolved(DeviceState* st, const DecideCall& a, hipStream_t s);
 // the curve's base field installed, d + 1 a power of two.  Works in st->decide_rho[1].
 int decide_rho_device(DeviceState* st, int curve, size_t d, size_t k, const void* xis, const void* U, const void* live,
                       void* rho_out, hipStream_t s);
-// The hash tree above k >= 1 leaves (k_rho_level; shared with the weights of a combined Schnorr batch,
-// schnorr_combined.hip): the leaves as k packed base-field elements in buf[0], buf[1] of rho_next_level(k) elements;
-// ceil(lg k) launches on `s` between the two, the root then the first element of buf[*root_at].  params: the device's
-// Poseidon parameters of the curve's base field.
-int rho_tree_device(DeviceState* st, int curve, const uint32_t* params, uint4* const (&buf)[2], size_t k, hipStream_t s,
-                    int* root_at);
+// What tells one derivation's weights kernel from another's: the labels of the seed and weight sponges, the third
+// integer the seed absorbs after the root and k, and the profile name of the launch.
+struct RhoWeights {
+    int seed_label, weight_label;
+    size_t third;
+    const char* profile;
+};
+// The two buffers of a derivation over k >= 1 leaves, carved from `work`: buf[0] of k packed base-field elements
+// (the leaves), buf[1] of rho_next_level(k).
+int rho_buffers(DevBuf& work, size_t k, uint4* (&buf)[2]);
+// From the leaves in buf[0] to the weights: the hash tree (k_rho_level, ceil(lg k) launches between the two
+// buffers) and k_rho_weights over its root, k ark scalars at rho_out (0 where `live`, which may be null, has 0).
+// Shared with the weights of a combined Schnorr batch (schnorr_combined.hip).  params: the device's Poseidon
+// parameters of the curve's base field.
+int rho_derive_device(DeviceState* st, int curve, const uint32_t* params, uint4* const (&buf)[2], size_t k, const RhoWeights& w,
+                      const void* live, void* rho_out, hipStream_t s);
 // a.derive, no rho and k >= 2: derives the weights into st->decide_rho[0] and makes them a.rho.  Else nothing.
 int decide_rho_weights(DeviceState* st, DecideCall& a, hipStream_t s);
 

@@ -18,6 +18,7 @@
 #include "runtime.hpp"
 #include "schnorr.hpp"
 #include "sponge_launch.hpp"
+#include <vector>
 
 namespace halo {
 
@@ -272,14 +273,24 @@ static int check_canonical(const char* call, const char* what, int curve, const 
     return HALO_OK;
 }
 
-// Zeroes the device staging of a host call's secrets on the call's stream and waits, however the call ends.
+// Zeroes the device staging of a host call's secrets on the call's stream and waits, however the call ends.  The
+// staging is upload_parts' st->scratch[0]; the secrets are the leading `secret` rows of the call's table, so their
+// bytes are [0, end of the last secret row) of that buffer.  arm() reserves the buffer that upload_parts then finds
+// in place, before a byte is copied: a failure part-way through the upload is wiped like any other return.
 struct SecretWipe {
     hipStream_t s;
-    void* p[2] = {nullptr, nullptr};
+    void* base = nullptr;
     size_t bytes = 0;
+    int arm(DeviceState* st, const HostParts& parts, size_t secret) {
+        if (secret == 0 || secret > parts.rows.size() || parts.rows[0].off != 0)
+            return set_error(HALO_EINVAL, "SecretWipe: the secrets are not the leading rows of the table");
+        HALO_CHECK(st->scratch[0].reserve(parts.total()));
+        base = st->scratch[0].ptr;
+        bytes = parts.rows[secret - 1].off + parts.rows[secret - 1].bytes;
+        return HALO_OK;
+    }
     ~SecretWipe() {
-        for (void* q : p)
-            if (q) (void)hipMemsetAsync(q, 0, bytes, s);
+        if (base) (void)hipMemsetAsync(base, 0, bytes, s);
         (void)hipStreamSynchronize(s);
     }
 };
@@ -299,13 +310,13 @@ extern "C" int halo_generator_mul_batch(halo_curve_t curve, const halo_fe_t* sca
     std::lock_guard<std::mutex> g(st->mu);
     hipStream_t s = 0;
     ScratchUse su(st, s);
-    HALO_CHECK(st->scratch[0].reserve(k * 32));
-    HALO_CHECK(st->scratch[1].reserve(k * 64));
+    const HostParts parts{{scalars, k * 32}};  // the secret row first: SecretWipe wipes the leading rows
     SecretWipe wipe{s};
-    wipe.p[0] = st->scratch[0].ptr;
-    wipe.bytes = k * 32;
-    HALO_CHECK(copy_h2d(st->scratch[0].ptr, scalars, k * 32, s));
-    HALO_CHECK(generator_mul_device(st, curve, st->scratch[0].ptr, st->scratch[1].ptr, nullptr, nullptr, k, s));
+    HALO_CHECK(wipe.arm(st, parts, 1));
+    std::vector<const void*> at;
+    HALO_CHECK(upload_parts(st, parts, s, at));
+    HALO_CHECK(st->scratch[1].reserve(k * 64));
+    HALO_CHECK(generator_mul_device(st, curve, at[0], st->scratch[1].ptr, nullptr, nullptr, k, s));
     return copy_d2h(out, st->scratch[1].ptr, k * 64, s);
 }
 
@@ -334,24 +345,19 @@ extern "C" int halo_schnorr_sign_batch(halo_curve_t curve, const halo_fe_t* sk, 
     std::lock_guard<std::mutex> g(st->mu);
     hipStream_t s = 0;
     ScratchUse su(st, s);
-    HALO_CHECK(st->scratch[0].reserve(k * 32));
-    HALO_CHECK(st->scratch[1].reserve(k * 32));
-    HALO_CHECK(st->scratch[2].reserve(k * 64));
-    HALO_CHECK(st->scratch[3].reserve(msg_len * k * 32));
-    HALO_CHECK(st->scratch[4].reserve(k * 64));
-    HALO_CHECK(st->scratch[5].reserve(k * 32));
+    // sk and nonce first: SecretWipe wipes the leading rows, so a secret row must not move behind a public one
+    const HostParts parts{{sk, k * 32}, {nonce, k * 32}, {pk, pk ? k * 64 : 0}, {msgs, msg_len * k * 32}};
     SecretWipe wipe{s};
-    wipe.p[0] = st->scratch[0].ptr;
-    wipe.p[1] = st->scratch[1].ptr;
-    wipe.bytes = k * 32;
-    HALO_CHECK(copy_h2d(st->scratch[0].ptr, sk, k * 32, s));
-    HALO_CHECK(copy_h2d(st->scratch[1].ptr, nonce, k * 32, s));
-    if (pk) HALO_CHECK(copy_h2d(st->scratch[2].ptr, pk, k * 64, s));
-    HALO_CHECK(copy_h2d(st->scratch[3].ptr, msgs, msg_len * k * 32, s));
-    HALO_CHECK(schnorr_sign_device(st, curve, st->scratch[0].ptr, pk ? st->scratch[2].ptr : nullptr, st->scratch[1].ptr,
-                                   st->scratch[3].ptr, msg_len, k, st->scratch[4].ptr, st->scratch[5].ptr, s));
-    HALO_CHECK(copy_d2h(R_out, st->scratch[4].ptr, k * 64, s));
-    return copy_d2h(s_out, st->scratch[5].ptr, k * 32, s);
+    HALO_CHECK(wipe.arm(st, parts, 2));
+    std::vector<const void*> at;
+    HALO_CHECK(upload_parts(st, parts, s, at));
+    ScratchLayout out;
+    const size_t o_R = out.take(k * 64), o_s = out.take(k * 32);
+    HALO_CHECK(st->scratch[1].reserve(out.total()));
+    uint8_t* dout = st->scratch[1].as<uint8_t>();
+    HALO_CHECK(schnorr_sign_device(st, curve, at[0], at[2], at[1], at[3], msg_len, k, dout + o_R, dout + o_s, s));
+    HALO_CHECK(copy_d2h(R_out, dout + o_R, k * 64, s));
+    return copy_d2h(s_out, dout + o_s, k * 32, s);
 }
 
 extern "C" int halo_schnorr_sign_batch_dev(halo_curve_t curve, const void* d_sk, const void* d_pk, const void* d_nonce,

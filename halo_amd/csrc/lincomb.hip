@@ -25,7 +25,7 @@
 namespace halo {
 
 constexpr int LINCOMB_THREADS = 64;  // one wave: 16 terms
-constexpr int LINCOMB_TAB_U4 = 8 * 8;  // d P at d - 1 (1 <= d <= 8) per quad: XYZZ, 128 B each; 16 KB per block
+constexpr int LINCOMB_TAB_U4 = QUAD_TAB_U4;  // d P at d - 1 (1 <= d <= 8) per quad: XYZZ, 128 B each; 16 KB per block
 // Waves per SIMD the term kernel is compiled for: at 206 VGPRs it spills nothing; compiled for three it
 // spills 116 VGPRs and the 16 KB tables admit only 2.5, and it measured 16 % slower.
 constexpr int LINCOMB_TERM_WAVES = 2;
@@ -57,25 +57,7 @@ __global__ __launch_bounds__(LINCOMB_THREADS, LINCOMB_TERM_WAVES) void k_lincomb
         g1.recode(k1);
         g2.recode(k2);
     }
-    // acc + t (t the same in every lane of the quad; trivial when either is the identity)
-    auto add = [&](const XYZZ<F>& acc, const XYZZ<F>& t, bool tid) -> XYZZ<F> {
-        const bool idp = xyzz_is_id(acc), idq = tid || xyzz_is_id(t);
-        XYZZ<F> r = xyzz_id<F>();
-        if (!__all(idp || idq)) r = xyzz_add_quad(role == 1 ? t : acc, s1, s1 + 1, idp, idq);
-        const XYZZ<F> sum = xyzz_quad_lane2(r);
-        return idq ? acc : (idp ? t : sum);
-    };
-    // the quad's table: d P at entry d - 1, 1 <= d <= 8
-    const XYZZ<F> p1 = xyzz_from_aff(P);
-    if (role == 0) xyzz_store(pt, p1);
-    __syncthreads();
-    XYZZ<F> prev = p1;
-    for (int d = 2; d <= 8; d++) {
-        const XYZZ<F> v = (d & 1) ? add(prev, p1, false) : xyzz_dbl_quad(xyzz_load<F>(pt + 8 * (d / 2 - 1)));
-        if (role == 0) xyzz_store(pt + 8 * (d - 1), v);
-        __syncthreads();
-        prev = v;
-    }
+    QUAD_TABLE_BUILD(F, pt, P, role, s1);
     const Fe<F> beta = fe_from_const<F>(Cv::K::BETA);
     XYZZ<F> acc = xyzz_id<F>();
 #pragma unroll 1
@@ -86,12 +68,12 @@ __global__ __launch_bounds__(LINCOMB_THREADS, LINCOMB_TERM_WAVES) void k_lincomb
         uint32_t d = g1.next(neg);  // + k1 P
         XYZZ<F> t = xyzz_load<F>(pt + 8 * (d ? d - 1 : 0));
         if (n1 != neg) t.Y = fe_neg(t.Y);
-        acc = add(acc, t, d == 0);
+        acc = quad_add(acc, t, d == 0, role, s1);
         d = g2.next(neg);  // + k2 phi(P)
         t = xyzz_load<F>(pt + 8 * (d ? d - 1 : 0));
         t.X = fe_mul(t.X, beta);
         if (n2 != neg) t.Y = fe_neg(t.Y);
-        acc = add(acc, t, d == 0);
+        acc = quad_add(acc, t, d == 0, role, s1);
     }
     if (role == 0 && i < n) {
         xyzz_store(terms + 8 * i, acc);

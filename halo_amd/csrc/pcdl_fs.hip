@@ -52,10 +52,7 @@ __global__ __launch_bounds__(256) void k_pcdl_alpha(const uint32_t* __restrict__
     using F = typename Cv::Base;
     using S = typename Cv::Scalar;
     __shared__ uint32_t tab[poseidon::TABLE_WORDS];
-    poseidon::stage_params(params, tab);
-    bool writer;
-    const size_t i = sponge_index<LANES>(writer);
-    const size_t ic = i < k ? i : k - 1;  // lanes past the batch repeat its last instance (they take part in the shuffles)
+    SPONGE_PROLOGUE(LANES, params, tab, k, i, ic, writer);
     poseidon::OuterSponge<Cv, LANES> sp;
     sp.init(tab);
     uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -112,10 +109,7 @@ __global__ __launch_bounds__(256) void k_pcdl_challenges(const uint32_t* __restr
                                                          size_t k, uint4* __restrict__ xis) {
     using S = typename Cv::Scalar;
     __shared__ uint32_t tab[poseidon::TABLE_WORDS];
-    poseidon::stage_params(params, tab);
-    bool writer;
-    const size_t i = sponge_index<LANES>(writer);
-    const size_t ic = i < k ? i : k - 1;
+    SPONGE_PROLOGUE(LANES, params, tab, k, i, ic, writer);
     poseidon::OuterSponge<Cv, LANES> sp;
     sp.init(tab);
     uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -239,24 +233,14 @@ int fs_device(const char* call, DeviceState* st, const FsCall& a, hipStream_t s)
     uint4* xis = a.xis_out ? (uint4*)a.xis_out : (uint4*)(base + o_xis);
     const uint4* Cp = (const uint4*)a.C;
     uint8_t* bad = nullptr;
-    const int lanes = poseidon_lanes(st, k);
-    const HashGrid g = hash_grid(k, lanes);
     const dim3 per_lane(grid_for(k, FS_THREADS));
     if (a.hiding) {
         bad = base + o_bad;
         PackedAffine S_int;
         for (int q = 0; q < 16; q++) S_int.w[q] = srs.S[q];
-        {
-            ProfScope prof("pcdl_alpha", s);
-            DISPATCH_CURVE(a.curve, Cv, {
-                DISPATCH_LANES(lanes, L, {
-                    HALO_LAUNCH(prof, (k_pcdl_alpha<Cv, L>), dim3(g.blocks), dim3(g.threads), 0, s, params,
-                                (const uint8_t*)a.hiding, (const uint4*)a.C, (const uint4*)a.C_bar, (const uint4*)a.z,
-                                (const uint4*)a.v, (const uint4*)a.w_prime, S_int, k, (uint4*)a.alpha_out, pts, sc, bad);
-                });
-            });
-            HALO_HIP(hipGetLastError());
-        }
+        HALO_CHECK(SPONGE_LAUNCH(st, a.curve, Cv, L, k, "pcdl_alpha", s, (k_pcdl_alpha<Cv, L>), params, (const uint8_t*)a.hiding,
+                                 (const uint4*)a.C, (const uint4*)a.C_bar, (const uint4*)a.z, (const uint4*)a.v,
+                                 (const uint4*)a.w_prime, S_int, k, (uint4*)a.alpha_out, pts, sc, bad));
         HALO_CHECK(lincomb_device(st, a.curve, a.C, pts, sc, k, 2, sum, nullptr, s));
         uint4* cp = (uint4*)(base + o_cp);
         DISPATCH_CURVE(a.curve, Cv, {
@@ -268,17 +252,9 @@ int fs_device(const char* call, DeviceState* st, const FsCall& a, hipStream_t s)
     } else if (a.alpha_out) {
         HALO_HIP(hipMemsetAsync(a.alpha_out, 0, k * 32, s));
     }
-    {
-        ProfScope prof("pcdl_challenges", s);
-        DISPATCH_CURVE(a.curve, Cv, {
-            DISPATCH_LANES(lanes, L, {
-                HALO_LAUNCH(prof, (k_pcdl_challenges<Cv, L>), dim3(g.blocks), dim3(g.threads), 0, s, params,
-                            (const uint8_t*)a.hiding, (const uint4*)a.C, (const uint4*)a.C_bar, Cp, (const uint4*)a.z,
-                            (const uint4*)a.v, (const uint4*)a.Ls, (const uint4*)a.Rs, lg, k, xis);
-            });
-        });
-        HALO_HIP(hipGetLastError());
-    }
+    HALO_CHECK(SPONGE_LAUNCH(st, a.curve, Cv, L, k, "pcdl_challenges", s, (k_pcdl_challenges<Cv, L>), params,
+                             (const uint8_t*)a.hiding, (const uint4*)a.C, (const uint4*)a.C_bar, Cp, (const uint4*)a.z,
+                             (const uint4*)a.v, (const uint4*)a.Ls, (const uint4*)a.Rs, lg, k, xis));
     {
         ProfScope prof("pcdl_terms", s);
         DISPATCH_CURVE(a.curve, Cv, {

@@ -120,6 +120,9 @@ __global__ __launch_bounds__(64) void k_open_fs_round(const uint32_t* __restrict
 
 namespace {
 
+// one block of one wave: the transcript of one opening, in the lane layout its caller chose
+inline SpongeLaunchPlan one_wave(int lanes) { return {lanes, {1, 64}}; }
+
 int launch_start(halo_ipa_session* ses, const uint32_t* params, int lanes, int mode, const halo_wrapped_point_t* p0,
                  const halo_wrapped_point_t* p1, const halo_fe_t* v) {
     OpenFsStart a{};
@@ -128,13 +131,8 @@ int launch_start(halo_ipa_session* ses, const uint32_t* params, int lanes, int m
     if (v) memcpy(a.v, v, 32);
     a.mode = mode;
     a.has_v = v != nullptr;
-    DISPATCH_CURVE(ses->op.curve, Cv, {
-        DISPATCH_LANES(lanes, L, {
-            hipLaunchKernelGGL((k_open_fs_start<Cv, L>), dim3(1), dim3(64), 0, ses->s, params, ses->small.as<uint4>(), a);
-        });
-    });
-    HALO_HIP(hipGetLastError());
-    return HALO_OK;
+    return SPONGE_LAUNCH_AT(DISPATCH_CURVE, ses->op.curve, Cv, L, one_wave(lanes), nullptr, ses->s, (k_open_fs_start<Cv, L>), params,
+                            ses->small.as<uint4>(), a);
 }
 
 // Round j of an opening whose xi_0 is resident: L_j and R_j, the transcript kernel, the fold.  Nothing here
@@ -146,15 +144,8 @@ int enqueue_round(DeviceState* st, halo_ipa_session* ses, const uint32_t* params
     ses->poll_pending = false;  // (what a tail / pair round emits to the pinned staging is not waited for)
     const uint4* xi_prev = (const uint4*)(sm + (j ? SM_XI : SM_XI0));
     uint4* row = (uint4*)(sm + SM_PROOF + 128 * j);
-    {
-        ProfScope prof("open_fs_round", s);
-        DISPATCH_CURVE(ses->op.curve, Cv, {
-            DISPATCH_LANES(lanes, L, {
-                HALO_LAUNCH(prof, (k_open_fs_round<Cv, L>), dim3(1), dim3(64), 0, s, params, (uint4*)sm, xi_prev, row);
-            });
-        });
-        HALO_HIP(hipGetLastError());
-    }
+    HALO_CHECK(SPONGE_LAUNCH_AT(DISPATCH_CURVE, ses->op.curve, Cv, L, one_wave(lanes), "open_fs_round", s, (k_open_fs_round<Cv, L>),
+                                params, (uint4*)sm, xi_prev, row));
     return ipa_fold_launch(st, ses, nullptr, nullptr);
 }
 

@@ -107,10 +107,7 @@ __global__ __launch_bounds__(256) void k_plonk_challenges(const uint32_t* __rest
     using Sp = poseidon::OuterSponge<Cv, LANES>;
     using S = typename Cv::Scalar;
     __shared__ uint32_t tab[poseidon::TABLE_WORDS];
-    poseidon::stage_params(params, tab);
-    bool writer;
-    const size_t i = sponge_index<LANES>(writer);
-    const size_t ic = i < k ? i : k - 1;
+    SPONGE_PROLOGUE(LANES, params, tab, k, i, ic, writer);
     Sp sp;
     sp.init(tab);
     int out = 0;
@@ -559,8 +556,6 @@ static int plonk_device(const char* call, DeviceState* st, const PlonkCall& a, h
     uint4* sides = a.sides_out ? (uint4*)a.sides_out : u4(o_sides);
     uint4* asdl = a.asdl_out ? (uint4*)a.asdl_out : u4(o_asdl);
     uint8_t *mal = base + o_mal, *bits = base + o_bits, *ok3 = base + o_ok3, *cid = base + o_cid;
-    const int lanes = poseidon_lanes(st, k);
-    const HashGrid g = hash_grid(k, lanes);
     const dim3 per_proof(grid_for(k, PV_THREADS)), blk(PV_THREADS);
     auto cp = [](const void* p) { return (const uint4*)p; };
 
@@ -574,16 +569,8 @@ static int plonk_device(const char* call, DeviceState* st, const PlonkCall& a, h
         });
         HALO_HIP(hipGetLastError());
     }
-    {
-        ProfScope prof("plonk_challenges", s);
-        DISPATCH_CURVE(a.curve, Cv, {
-            DISPATCH_LANES(lanes, L, {
-                HALO_LAUNCH(prof, (k_plonk_challenges<Cv, L>), dim3(g.blocks), dim3(g.threads), 0, s, params, cp(a.C_ws),
-                            cp(a.C_z), cp(a.C_ts), k, chal);
-            });
-        });
-        HALO_HIP(hipGetLastError());
-    }
+    HALO_CHECK(SPONGE_LAUNCH(st, a.curve, Cv, L, k, "plonk_challenges", s, (k_plonk_challenges<Cv, L>), params, cp(a.C_ws),
+                             cp(a.C_z), cp(a.C_ts), k, chal));
     {
         ProfScope prof("plonk_identity", s);
         DISPATCH_CURVE(a.curve, Cv, {

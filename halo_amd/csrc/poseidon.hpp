@@ -14,6 +14,7 @@
 //                 three times the waves for the same batch.
 #pragma once
 #include "fields.hpp"
+#include "sponge_plan.hpp"
 
 HALO_ARITH_BEGIN
 namespace poseidon {
@@ -21,7 +22,7 @@ namespace poseidon {
 constexpr int WIDTH = 3, RATE = 2, ROUNDS = 55;
 constexpr int N_CONST = WIDTH * WIDTH + ROUNDS * WIDTH;  // 174
 constexpr int TABLE_WORDS = N_CONST * NLIMB;
-constexpr int SPONGES_PER_WAVE_3 = 21;
+constexpr int SPONGES_PER_WAVE_3 = (int)::halo::SPONGES_PER_WAVE_3;  // sponge_plan.hpp: the launch plan counts with it
 constexpr int STATE_U4 = 2 * WIDTH + 1;  // a sponge's state in memory (Sponge::store): 3 x 32 B, then (squeezed, n)
 
 // global table -> LDS, by the whole block

@@ -1,7 +1,12 @@
-// Pieces of the quad-cooperative variable-base ladder shared by the Schnorr verification
-// (schnorr.hip, k_schnorr_verify) and the batched linear combinations of points (lincomb.hip,
-// k_lincomb_terms): the on-curve test of an input point, the signed 4-bit recoding of a GLV half-scalar
-// and the broadcast of a quad addition's sum, in the arithmetic namespace of the including unit.
+// The quad-cooperative variable-base ladder of the Schnorr verification (schnorr.hip, k_schnorr_verify) and
+// of the batched linear combinations of points (lincomb.hip, k_lincomb_terms), in the arithmetic namespace of the
+// including unit: the on-curve test of an input point, the signed 4-bit recoding of a GLV half-scalar, the quad
+// addition with its trivial-case rule and the build of a quad's table d P (1 <= d <= 8) in LDS.  A kernel keeps its
+// own load, validity rule, decomposition, window loop (doublings and table terms) and epilogue.
+//
+// One aligned quad of lanes works on one point, every lane of the quad holding the same values (tree.hpp's
+// quad doubling / addition); role = lane & 3, s1 = the wave lane of the quad's lane 0.  Quads of one wave stay
+// in lockstep: an addition is skipped only when it is trivial for every quad.
 #pragma once
 #include "curve.hpp"
 #include "tree.hpp"
@@ -57,5 +62,42 @@ struct SignedDigits {
         return neg ? 16u - n : n;
     }
 };
+
+// Eight canonical words as two uint4 (k_schnorr_hash's e_words).
+HALO_DEV void words_from_u4(const uint4* p, uint32_t (&w)[8]) {
+    const uint4 lo = p[0], hi = p[1];
+    w[0] = lo.x, w[1] = lo.y, w[2] = lo.z, w[3] = lo.w, w[4] = hi.x, w[5] = hi.y, w[6] = hi.z, w[7] = hi.w;
+}
+
+// acc + t (t the same in every lane of the quad; trivial when either is the identity)
+template <class F>
+HALO_DEV XYZZ<F> quad_add(const XYZZ<F>& acc, const XYZZ<F>& t, bool t_is_id, uint32_t role, uint32_t s1) {
+    const bool idp = xyzz_is_id(acc), idq = t_is_id || xyzz_is_id(t);
+    XYZZ<F> r = xyzz_id<F>();
+    if (!__all(idp || idq)) r = xyzz_add_quad(role == 1 ? t : acc, s1, s1 + 1, idp, idq);
+    const XYZZ<F> sum = xyzz_quad_lane2(r);
+    return idq ? acc : (idp ? t : sum);
+}
+
+constexpr int QUAD_TAB_U4 = 8 * 8;  // d P at d - 1 (1 <= d <= 8): XYZZ, 128 B each
+
+// The quad's table in its LDS slice `pt` of QUAD_TAB_U4: d P at entry d - 1, P affine.  Eight block barriers: every
+// lane of the block runs it.  (The first barrier also completes whatever the block staged before.)  A macro, not a
+// function: with this loop one inlining level down, the compiler gives k_schnorr_verify 243 VGPRs for 237 and
+// k_lincomb_terms other SGPRs; expanded in the kernel's body both compile as they always did.
+#define QUAD_TABLE_BUILD(F, pt, P, role, s1)                                                                       \
+    do {                                                                                                           \
+        const XYZZ<F> p1_ = xyzz_from_aff(P);                                                                      \
+        if ((role) == 0) xyzz_store((pt), p1_);                                                                    \
+        __syncthreads();                                                                                           \
+        XYZZ<F> prev_ = p1_;                                                                                       \
+        for (int d_ = 2; d_ <= 8; d_++) {                                                                          \
+            const XYZZ<F> v_ = (d_ & 1) ? quad_add(prev_, p1_, false, (role), (s1))                                \
+                                        : xyzz_dbl_quad(xyzz_load<F>((pt) + 8 * (d_ / 2 - 1)));                    \
+            if ((role) == 0) xyzz_store((pt) + 8 * (d_ - 1), v_);                                                  \
+            __syncthreads();                                                                                       \
+            prev_ = v_;                                                                                            \
+        }                                                                                                          \
+    } while (0)
 
 HALO_ARITH_END

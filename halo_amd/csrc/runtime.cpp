@@ -185,7 +185,7 @@ static const char* const kTuneNames[TUNE_COUNT] = {"ipa_weighted", "ipa_tail",  
 // ntt_big_max_log: the largest transform split into two passes on 2048-element blocks (2^17..2^this);
 // larger ones, and any below 2^17, take passes of <= 8 bits on 1024-element blocks (ntt.hip ntt_radices)
 // ntt_even_split: passes of <= 8 bits split into even radices where possible (ntt_radices)
-// poseidon_lanes: lanes per sponge of the batched Poseidon kernels (1 or 3; 0 = by batch size, schnorr.hip)
+// poseidon_lanes: lanes per sponge of the batched Poseidon kernels (1 or 3; 0 = by batch size, sponge_plan.hpp)
 // ipa_pair_max: weighted IPA rounds up to this many terms per side run L and R as one MSM (2^19: every
 // weighted round of a 2^20 opening; the pair's 17-bit keys sort in a 9-bit and an 8-bit pass)
 // decide_group_scalars: the exact decider's h rows of one group hold at most this many scalars (2^25: 1 GiB,

@@ -20,6 +20,7 @@
 #include "tree.hpp"
 
 #include <cstring>
+#include <vector>
 
 namespace halo {
 
@@ -31,10 +32,7 @@ template <class F, int LANES>
 __global__ __launch_bounds__(256) void k_poseidon_hash(const uint32_t* __restrict__ params, const uint4* __restrict__ in,
                                                        size_t len, size_t k, uint4* __restrict__ out) {
     __shared__ uint32_t tab[poseidon::TABLE_WORDS];
-    poseidon::stage_params(params, tab);
-    bool writer;
-    const size_t i = sponge_index<LANES>(writer);
-    const size_t ic = i < k ? i : k - 1;  // lanes past the batch repeat its last row (they take part in the shuffles)
+    SPONGE_PROLOGUE(LANES, params, tab, k, i, ic, writer);
     poseidon::Sponge<F, LANES> sp;
     sp.init(tab);
     for (size_t j = 0; j < len; j++) sp.absorb(fe_from_ark<F>(in + 2 * (ic * len + j)));
@@ -55,10 +53,7 @@ __global__ __launch_bounds__(256) void k_schnorr_hash(const uint32_t* __restrict
     using F = typename Cv::Base;
     using S = typename Cv::Scalar;
     __shared__ uint32_t tab[poseidon::TABLE_WORDS];
-    poseidon::stage_params(params, tab);
-    bool writer;
-    const size_t i = sponge_index<LANES>(writer);
-    const size_t ic = i < k ? i : k - 1;
+    SPONGE_PROLOGUE(LANES, params, tab, k, i, ic, writer);
     poseidon::Sponge<F, LANES> sp;
     sp.init(tab);
     const Fe<F> one = fe_one<F>();
@@ -95,7 +90,7 @@ __global__ __launch_bounds__(256) void k_schnorr_hash(const uint32_t* __restrict
 // ---------------------------------------------------------------------------------------------
 constexpr int VERIFY_THREADS = 64;                    // one wave: 16 signatures
 constexpr int GTAB_U4 = 16 * 8;                       // d G at d - 1, phi(d G) at 8 + d - 1 (1 <= d <= 8): XYZZ, 128 B each
-constexpr int PKTAB_U4 = 8 * 8;                       // d pk at d - 1 (1 <= d <= 8) per quad
+constexpr int PKTAB_U4 = QUAD_TAB_U4;                 // d pk at d - 1 (1 <= d <= 8) per quad
 constexpr size_t VERIFY_LDS = (size_t)(GTAB_U4 + (VERIFY_THREADS / 4) * PKTAB_U4) * sizeof(uint4);  // 18 KB: 8 blocks per CU
 
 template <class Cv>
@@ -149,8 +144,7 @@ __global__ __launch_bounds__(VERIFY_THREADS) void k_schnorr_verify(const uint4* 
     {
         uint32_t sw[8], ew[8], k1[5], k2[5];
         fe_ark_to_canonical_words<S>(s + 2 * ic, sw);
-        const uint4 lo = e_words[2 * ic], hi = e_words[2 * ic + 1];
-        ew[0] = lo.x, ew[1] = lo.y, ew[2] = lo.z, ew[3] = lo.w, ew[4] = hi.x, ew[5] = hi.y, ew[6] = hi.z, ew[7] = hi.w;
+        words_from_u4(e_words + 2 * ic, ew);
         glv::decompose<typename Cv::K>(sw, ns1, k1, ns2, k2);
         gs1.recode(k1);
         gs2.recode(k2);
@@ -158,25 +152,7 @@ __global__ __launch_bounds__(VERIFY_THREADS) void k_schnorr_verify(const uint4* 
         ge1.recode(k1);
         ge2.recode(k2);
     }
-    // acc + t (t the same in every lane of the quad; trivial when either is the identity)
-    auto add = [&](const XYZZ<F>& acc, const XYZZ<F>& t, bool tid) -> XYZZ<F> {
-        const bool idp = xyzz_is_id(acc), idq = tid || xyzz_is_id(t);
-        XYZZ<F> r = xyzz_id<F>();
-        if (!__all(idp || idq)) r = xyzz_add_quad(role == 1 ? t : acc, s1, s1 + 1, idp, idq);
-        const XYZZ<F> sum = xyzz_quad_lane2(r);
-        return idq ? acc : (idp ? t : sum);
-    };
-    // the quad's table: d pk at entry d - 1, 1 <= d <= 8
-    const XYZZ<F> p1 = xyzz_from_aff(P);
-    if (role == 0) xyzz_store(pt, p1);
-    __syncthreads();  // (also: the block's copy of the G table is complete)
-    XYZZ<F> prev = p1;
-    for (int d = 2; d <= 8; d++) {
-        const XYZZ<F> v = (d & 1) ? add(prev, p1, false) : xyzz_dbl_quad(xyzz_load<F>(pt + 8 * (d / 2 - 1)));
-        if (role == 0) xyzz_store(pt + 8 * (d - 1), v);
-        __syncthreads();
-        prev = v;
-    }
+    QUAD_TABLE_BUILD(F, pt, P, role, s1);  // (its first barrier: the block's copy of the G table is complete)
     const Fe<F> beta = fe_from_const<F>(Cv::K::BETA);
     XYZZ<F> acc = xyzz_id<F>();
 #pragma unroll 1
@@ -187,20 +163,20 @@ __global__ __launch_bounds__(VERIFY_THREADS) void k_schnorr_verify(const uint4* 
         uint32_t d = gs1.next(neg);
         XYZZ<F> t = xyzz_load<F>(gt + 8 * (d ? d - 1 : 0));
         if (ns1 != neg) t.Y = fe_neg(t.Y);
-        acc = add(acc, t, d == 0);
+        acc = quad_add(acc, t, d == 0, role, s1);
         d = gs2.next(neg);
         t = xyzz_load<F>(gt + 8 * (8 + (d ? d - 1 : 0)));
         if (ns2 != neg) t.Y = fe_neg(t.Y);
-        acc = add(acc, t, d == 0);
+        acc = quad_add(acc, t, d == 0, role, s1);
         d = ge1.next(neg);  // - e1 pk
         t = xyzz_load<F>(pt + 8 * (d ? d - 1 : 0));
         if (ne1 == neg) t.Y = fe_neg(t.Y);
-        acc = add(acc, t, d == 0);
+        acc = quad_add(acc, t, d == 0, role, s1);
         d = ge2.next(neg);  // - e2 phi(pk)
         t = xyzz_load<F>(pt + 8 * (d ? d - 1 : 0));
         t.X = fe_mul(t.X, beta);
         if (ne2 == neg) t.Y = fe_neg(t.Y);
-        acc = add(acc, t, d == 0);
+        acc = quad_add(acc, t, d == 0, role, s1);
     }
     acc = xyzz_madd(acc, aff_neg(Rp));
     if (role == 0 && i < k) ok[i] = (valid && xyzz_is_id(acc)) ? 1 : 0;
@@ -254,49 +230,20 @@ int poseidon_device_params(DeviceState* st, int field, const uint32_t** out) {
     return HALO_OK;
 }
 
-// Lanes per sponge.  Three lanes triple the waves and cut the dependent chain to a third, which pays
-// while the batch leaves SIMDs short of work: measured on the MI355X, 40 000 hashes of
-// 15 elements take 1.77 ms on 1905 three-lane waves against 2.72 ms on 625 one-lane waves, but 65 536
-// take 3.46 ms on 3121 three-lane waves against 2.72 ms on 1024 one-lane waves, and from there on the
-// one-lane layout stays 5-20 % ahead (its lanes are all busy and it has no crossbar traffic).  So: three
-// lanes while their waves number at most two per SIMD.  The poseidon_lanes tuning key pins either.
-int poseidon_lanes(const DeviceState* st, size_t k) {
-    const long long t = tuning(TUNE_POSEIDON_LANES);
-    if (t == 1 || t == 3) return (int)t;
-    const size_t waves3 = (k + poseidon::SPONGES_PER_WAVE_3 - 1) / poseidon::SPONGES_PER_WAVE_3;
-    return waves3 <= (size_t)8 * st->num_cu ? 3 : 1;
-}
-
 static int poseidon_hash_device(DeviceState* st, int field, const void* d_in, size_t len, size_t k, void* d_out,
                                 hipStream_t s) {
     const uint32_t* params;
     HALO_CHECK(poseidon_device_params(st, field, &params));
-    const int lanes = poseidon_lanes(st, k);
-    const HashGrid g = hash_grid(k, lanes);
-    DISPATCH_FIELD(field, F, {
-        DISPATCH_LANES(lanes, L, {
-            hipLaunchKernelGGL((k_poseidon_hash<F, L>), dim3(g.blocks), dim3(g.threads), 0, s, params, (const uint4*)d_in, len,
-                               k, (uint4*)d_out);
-        });
-    });
-    HALO_HIP(hipGetLastError());
-    return HALO_OK;
+    return SPONGE_LAUNCH_FIELD(st, field, F, L, k, nullptr, s, (k_poseidon_hash<F, L>), params, (const uint4*)d_in, len, k,
+                               (uint4*)d_out);
 }
 
 int schnorr_hash_device(DeviceState* st, int curve, const void* d_pk, const void* d_R, const void* d_msgs, size_t msg_len,
                         size_t k, void* d_e_ark, void* d_e_words, hipStream_t s) {
     const uint32_t* params;
     HALO_CHECK(poseidon_device_params(st, base_field(curve), &params));
-    const int lanes = poseidon_lanes(st, k);
-    const HashGrid g = hash_grid(k, lanes);
-    DISPATCH_CURVE(curve, Cv, {
-        DISPATCH_LANES(lanes, L, {
-            hipLaunchKernelGGL((k_schnorr_hash<Cv, L>), dim3(g.blocks), dim3(g.threads), 0, s, params, (const uint4*)d_pk,
-                               (const uint4*)d_R, (const uint4*)d_msgs, msg_len, k, (uint4*)d_e_ark, (uint4*)d_e_words);
-        });
-    });
-    HALO_HIP(hipGetLastError());
-    return HALO_OK;
+    return SPONGE_LAUNCH(st, curve, Cv, L, k, nullptr, s, (k_schnorr_hash<Cv, L>), params, (const uint4*)d_pk, (const uint4*)d_R,
+                         (const uint4*)d_msgs, msg_len, k, (uint4*)d_e_ark, (uint4*)d_e_words);
 }
 
 // The ladder over challenges already on the device (e_words: k_schnorr_hash's canonical words).  st->mu held.
@@ -390,10 +337,10 @@ extern "C" int halo_poseidon_hash_batch(halo_field_t field, const halo_fe_t* in,
     std::lock_guard<std::mutex> g(st->mu);
     hipStream_t s = 0;
     ScratchUse su(st, s);
-    HALO_CHECK(st->scratch[0].reserve(len * k * 32));
+    std::vector<const void*> at;
+    HALO_CHECK(upload_parts(st, HostParts{{in, len * k * 32}}, s, at));
     HALO_CHECK(st->scratch[1].reserve(k * 32));
-    HALO_CHECK(copy_h2d(st->scratch[0].ptr, in, len * k * 32, s));
-    HALO_CHECK(poseidon_hash_device(st, field, st->scratch[0].ptr, len, k, st->scratch[1].ptr, s));
+    HALO_CHECK(poseidon_hash_device(st, field, at[0], len, k, st->scratch[1].ptr, s));
     return copy_d2h(out, st->scratch[1].ptr, k * 32, s);
 }
 
@@ -420,16 +367,11 @@ extern "C" int halo_schnorr_hash_batch(halo_curve_t curve, const halo_wrapped_po
     std::lock_guard<std::mutex> g(st->mu);
     hipStream_t s = 0;
     ScratchUse su(st, s);
-    HALO_CHECK(st->scratch[0].reserve(k * 64));
-    HALO_CHECK(st->scratch[1].reserve(k * 64));
-    HALO_CHECK(st->scratch[2].reserve(msg_len * k * 32));
-    HALO_CHECK(st->scratch[3].reserve(k * 32));
-    HALO_CHECK(copy_h2d(st->scratch[0].ptr, pk, k * 64, s));
-    HALO_CHECK(copy_h2d(st->scratch[1].ptr, R, k * 64, s));
-    HALO_CHECK(copy_h2d(st->scratch[2].ptr, msgs, msg_len * k * 32, s));
-    HALO_CHECK(schnorr_hash_device(st, curve, st->scratch[0].ptr, st->scratch[1].ptr, st->scratch[2].ptr, msg_len, k,
-                                   st->scratch[3].ptr, nullptr, s));
-    return copy_d2h(e_out, st->scratch[3].ptr, k * 32, s);
+    std::vector<const void*> at;
+    HALO_CHECK(upload_parts(st, HostParts{{pk, k * 64}, {R, k * 64}, {msgs, msg_len * k * 32}}, s, at));
+    HALO_CHECK(st->scratch[1].reserve(k * 32));
+    HALO_CHECK(schnorr_hash_device(st, curve, at[0], at[1], at[2], msg_len, k, st->scratch[1].ptr, nullptr, s));
+    return copy_d2h(e_out, st->scratch[1].ptr, k * 32, s);
 }
 
 extern "C" int halo_schnorr_hash_batch_dev(halo_curve_t curve, const void* d_pk, const void* d_R, const void* d_msgs,
@@ -457,18 +399,11 @@ extern "C" int halo_schnorr_verify_batch(halo_curve_t curve, const halo_wrapped_
     std::lock_guard<std::mutex> g(st->mu);
     hipStream_t s = 0;
     ScratchUse su(st, s);
-    HALO_CHECK(st->scratch[0].reserve(k * 64));
-    HALO_CHECK(st->scratch[1].reserve(k * 64));
-    HALO_CHECK(st->scratch[2].reserve(msg_len * k * 32));
-    HALO_CHECK(st->scratch[3].reserve(k * 32));
-    HALO_CHECK(st->scratch[4].reserve(k));
-    HALO_CHECK(copy_h2d(st->scratch[0].ptr, pk, k * 64, s));
-    HALO_CHECK(copy_h2d(st->scratch[1].ptr, R, k * 64, s));
-    HALO_CHECK(copy_h2d(st->scratch[2].ptr, msgs, msg_len * k * 32, s));
-    HALO_CHECK(copy_h2d(st->scratch[3].ptr, s_in, k * 32, s));
-    HALO_CHECK(schnorr_verify_device(st, curve, st->scratch[0].ptr, st->scratch[1].ptr, st->scratch[3].ptr,
-                                     st->scratch[2].ptr, msg_len, k, st->scratch[4].ptr, s));
-    return copy_d2h(ok_out, st->scratch[4].ptr, k, s);
+    std::vector<const void*> at;
+    HALO_CHECK(upload_parts(st, HostParts{{pk, k * 64}, {R, k * 64}, {s_in, k * 32}, {msgs, msg_len * k * 32}}, s, at));
+    HALO_CHECK(st->scratch[1].reserve(k));
+    HALO_CHECK(schnorr_verify_device(st, curve, at[0], at[1], at[2], at[3], msg_len, k, st->scratch[1].ptr, s));
+    return copy_d2h(ok_out, st->scratch[1].ptr, k, s);
 }
 
 extern "C" int halo_schnorr_verify_batch_dev(halo_curve_t curve, const void* d_pk, const void* d_R, const void* d_s,

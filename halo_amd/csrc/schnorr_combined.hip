@@ -26,9 +26,9 @@
 //                     0 with nothing read for an item that is not live.  e_i is already a collision-resistant digest
 //                     of (pk_i, R_i, m_i) under SIGNATURE, so the points and the message are not hashed again (that
 //                     would double the batch's dominant cost)
-//   (k_rho_level)     decide_rho.hip's tree (rho_tree_device)
-//   k_sig_weights     seed = squeeze of Sponge(SIG_BATCH_SEED) after root, k, msg_len; rho_i = challenge of
-//                     Sponge(SIG_BATCH_WEIGHT) after seed, i, zero replaced by one; 0 for an item that is not live
+//   (k_rho_level, k_rho_weights)  decide_rho.hip's tree and weights (rho_derive_device): seed = squeeze of
+//                     Sponge(SIG_BATCH_SEED) after root, k, msg_len; rho_i = challenge of Sponge(SIG_BATCH_WEIGHT) after
+//                     seed, i, zero replaced by one; 0 for an item that is not live
 #include "curve.hpp"
 #include "decider.hpp"
 #include "dispatch.hpp"
@@ -172,10 +172,7 @@ __global__ __launch_bounds__(256) void k_sig_leaves(const uint32_t* __restrict__
     using S = typename Cv::Scalar;
     constexpr unsigned NS = Sp::FR_ELEMENTS;
     __shared__ uint32_t tab[poseidon::TABLE_WORDS];
-    poseidon::stage_params(params, tab);
-    bool writer;
-    const size_t i = sponge_index<LANES>(writer);
-    const size_t ic = i < k ? i : k - 1;
+    SPONGE_PROLOGUE(LANES, params, tab, k, i, ic, writer);
     const bool on = live[ic] != 0;  // nothing of an item that is not live is read
     Sp sp;
     sp.init(tab);
@@ -190,8 +187,7 @@ __global__ __launch_bounds__(256) void k_sig_leaves(const uint32_t* __restrict__
             const unsigned q = e - 1;
             uint32_t w[8];
             if (q < NS) {
-                const uint4 lo = e_words[2 * ic], hi = e_words[2 * ic + 1];
-                w[0] = lo.x, w[1] = lo.y, w[2] = lo.z, w[3] = lo.w, w[4] = hi.x, w[5] = hi.y, w[6] = hi.z, w[7] = hi.w;
+                words_from_u4(e_words + 2 * ic, w);
             } else {
                 fe_ark_to_canonical_words<S>(s + 2 * ic, w);
             }
@@ -201,46 +197,6 @@ __global__ __launch_bounds__(256) void k_sig_leaves(const uint32_t* __restrict__
     }
     const Fe<F> leaf = fe_select(on, sp.inner.squeeze(), fe_zero<F>());
     if (writer && i < k) fe_store(leaves + 2 * i, leaf);
-}
-
-template <class Cv, int LANES>
-__global__ __launch_bounds__(256) void k_sig_weights(const uint32_t* __restrict__ params, const uint4* __restrict__ root, size_t k,
-                                                     size_t msg_len, const uint8_t* __restrict__ live, uint4* __restrict__ rho) {
-    using Sp = poseidon::OuterSponge<Cv, LANES>;
-    using F = typename Cv::Base;
-    using S = typename Cv::Scalar;
-    __shared__ uint32_t tab[poseidon::TABLE_WORDS];
-    poseidon::stage_params(params, tab);
-    bool writer;
-    const size_t i = sponge_index<LANES>(writer);
-    const size_t ic = i < k ? i : k - 1;
-    Sp sp;
-    Fe<F> out = fe_load<F>(root);  // the root, then the seed, then the squeezed weight
-#pragma unroll 1
-    for (int phase = 0; phase < 2; phase++) {
-        sp.init(tab);
-        const int total = phase == 0 ? 4 : 3;
-#pragma unroll 1
-        for (int e = 0; e < total; e++) {
-            Fe<F> x;
-            if (e == 0)
-                x = Sp::label_element(phase == 0 ? SIG_BATCH_SEED : SIG_BATCH_WEIGHT);
-            else if (e == 1)
-                x = out;
-            else
-                x = poseidon::fe_from_u64<F>(phase == 1 ? (uint64_t)ic : e == 2 ? (uint64_t)k : (uint64_t)msg_len);
-            sp.absorb(x);
-        }
-        out = sp.inner.squeeze();
-    }
-    uint32_t w[8];
-    Sp::challenge_words(out, w);
-    rho_zero_becomes_one(w);
-    if (live[ic] == 0) {
-#pragma unroll
-        for (int q = 0; q < 8; q++) w[q] = 0;
-    }
-    if (writer && i < k) poseidon::scalar_words_to_ark<S>(rho + 2 * i, w);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -286,36 +242,13 @@ static int sig_rho_device(DeviceState* st, int curve, const void* d_s, size_t ms
                           void* d_rho_out, hipStream_t s) {
     const uint32_t* params;
     HALO_CHECK(poseidon_device_params(st, base_field(curve), &params));
-    ScratchLayout lay;
-    const size_t o_ping = lay.take(k * 32), o_pong = lay.take(rho_next_level(k) * 32);
-    HALO_CHECK(st->schnorr_comb[1].reserve(lay.total()));
-    uint8_t* base = st->schnorr_comb[1].as<uint8_t>();
-    uint4* buf[2] = {(uint4*)(base + o_ping), (uint4*)(base + o_pong)};
-    const int lanes = poseidon_lanes(st, k);
-    const HashGrid g = hash_grid(k, lanes);
+    uint4* buf[2];
+    HALO_CHECK(rho_buffers(st->schnorr_comb[1], k, buf));
     StageScope stage("sig_rho", s);
-    {
-        ProfScope prof("sig_leaves", s);
-        DISPATCH_CURVE(curve, Cv, {
-            DISPATCH_LANES(lanes, L, {
-                HALO_LAUNCH(prof, (k_sig_leaves<Cv, L>), dim3(g.blocks), dim3(g.threads), 0, s, params,
-                            st->schnorr_e.as<const uint4>(), (const uint4*)d_s, (const uint8_t*)w.live, k, buf[0]);
-            });
-        });
-        HALO_HIP(hipGetLastError());
-    }
-    int cur = 0;
-    HALO_CHECK(rho_tree_device(st, curve, params, buf, k, s, &cur));
-    {
-        ProfScope prof("sig_weights", s);
-        DISPATCH_CURVE(curve, Cv, {
-            DISPATCH_LANES(lanes, L, {
-                HALO_LAUNCH(prof, (k_sig_weights<Cv, L>), dim3(g.blocks), dim3(g.threads), 0, s, params, (const uint4*)buf[cur],
-                            k, msg_len, (const uint8_t*)w.live, (uint4*)d_rho_out);
-            });
-        });
-        HALO_HIP(hipGetLastError());
-    }
+    HALO_CHECK(SPONGE_LAUNCH(st, curve, Cv, L, k, "sig_leaves", s, (k_sig_leaves<Cv, L>), params, st->schnorr_e.as<const uint4>(),
+                             (const uint4*)d_s, (const uint8_t*)w.live, k, buf[0]));
+    HALO_CHECK(rho_derive_device(st, curve, params, buf, k, RhoWeights{SIG_BATCH_SEED, SIG_BATCH_WEIGHT, msg_len, "sig_weights"},
+                                 w.live, d_rho_out, s));
     stage.end();
     return HALO_OK;
 }

@@ -45,10 +45,7 @@ __global__ __launch_bounds__(256) void k_sponge_absorb(const uint32_t* __restric
     using S = typename Cv::Scalar;
     constexpr size_t NS = Sp::FR_ELEMENTS;
     __shared__ uint32_t tab[poseidon::TABLE_WORDS];
-    poseidon::stage_params(params, tab);
-    bool writer;
-    const size_t i = sponge_index<LANES>(writer);
-    const size_t ic = i < k ? i : k - 1;
+    SPONGE_PROLOGUE(LANES, params, tab, k, i, ic, writer);
     uint4* mine_state = state + (size_t)poseidon::STATE_U4 * ic;
     Sp sp;
     if (init == SPONGE_LOAD)
@@ -87,10 +84,7 @@ __global__ __launch_bounds__(256) void k_sponge_challenge(const uint32_t* __rest
                                                           size_t c, size_t k, int squeezed, int fill, uint4* __restrict__ out) {
     using S = typename Cv::Scalar;
     __shared__ uint32_t tab[poseidon::TABLE_WORDS];
-    poseidon::stage_params(params, tab);
-    bool writer;
-    const size_t i = sponge_index<LANES>(writer);
-    const size_t ic = i < k ? i : k - 1;
+    SPONGE_PROLOGUE(LANES, params, tab, k, i, ic, writer);
     uint4* mine_state = state + (size_t)poseidon::STATE_U4 * ic;
     poseidon::OuterSponge<Cv, LANES> sp;
     sp.load(tab, mine_state);
@@ -115,16 +109,8 @@ int sponge_absorb_launch(SpongeHandle& h, int init, int kind, const void* d_in, 
     const SpongeMode before = init == SPONGE_LOAD ? h.mode : SpongeMode{false, 0};
     const size_t elements = (init == SPONGE_FRESH ? 1 : 0) + n * sponge_item_elements(kind, h.curve == HALO_PALLAS);
     const SpongeStep step = sponge_step(before, elements, 0);
-    const int lanes = poseidon_lanes(st, h.k);
-    const HashGrid g = hash_grid(h.k, lanes);
-    ProfScope prof("sponge_absorb", s);
-    DISPATCH_CURVE(h.curve, Cv, {
-        DISPATCH_LANES(lanes, L, {
-            HALO_LAUNCH(prof, (k_sponge_absorb<Cv, L>), dim3(g.blocks), dim3(g.threads), 0, s, params, h.state.as<uint4>(),
-                        (const uint4*)d_in, kind, n, h.k, init, h.protocol, before.squeezed ? 1 : 0, before.n);
-        });
-    });
-    HALO_HIP(hipGetLastError());
+    HALO_CHECK(SPONGE_LAUNCH(st, h.curve, Cv, L, h.k, "sponge_absorb", s, (k_sponge_absorb<Cv, L>), params, h.state.as<uint4>(),
+                             (const uint4*)d_in, kind, n, h.k, init, h.protocol, before.squeezed ? 1 : 0, before.n));
     h.mode = step.mode;
     prof_count("sponge_permutations", h.k * step.permutations);
     return HALO_OK;
@@ -135,16 +121,8 @@ int sponge_challenge_launch(SpongeHandle& h, size_t n, void* d_out, hipStream_t 
     const uint32_t* params;
     HALO_CHECK(poseidon_device_params(st, base_field(h.curve), &params));
     const SpongeStep step = sponge_step(h.mode, 0, n);
-    const int lanes = poseidon_lanes(st, h.k);
-    const HashGrid g = hash_grid(h.k, lanes);
-    ProfScope prof("sponge_challenge", s);
-    DISPATCH_CURVE(h.curve, Cv, {
-        DISPATCH_LANES(lanes, L, {
-            HALO_LAUNCH(prof, (k_sponge_challenge<Cv, L>), dim3(g.blocks), dim3(g.threads), 0, s, params, h.state.as<uint4>(), n,
-                        h.k, h.mode.squeezed ? 1 : 0, h.mode.n, (uint4*)d_out);
-        });
-    });
-    HALO_HIP(hipGetLastError());
+    HALO_CHECK(SPONGE_LAUNCH(st, h.curve, Cv, L, h.k, "sponge_challenge", s, (k_sponge_challenge<Cv, L>), params,
+                             h.state.as<uint4>(), n, h.k, h.mode.squeezed ? 1 : 0, h.mode.n, (uint4*)d_out));
     h.mode = step.mode;
     prof_count("sponge_permutations", h.k * step.permutations);
     return HALO_OK;

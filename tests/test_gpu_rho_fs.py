@@ -83,7 +83,7 @@ def rho_dev(hal, cname, d, xis, Us, live=None):
 @pytest.mark.parametrize("lg", [0, 1, 3, 10])
 @pytest.mark.parametrize("cname", CURVES)
 def test_decide_rho_equals_the_restated_derivation(fs, cname, lg):
-    ks = [1, 2, 3, 64, 65] + ([257] if lg == 3 else [])
+    ks = [1, 2, 3, 21, 22, 64, 65] + ([257] if lg == 3 else [])
     xis, Us, leaves = _leaves(cname, lg, max(ks))
     d = (1 << lg) - 1
     for k in ks:

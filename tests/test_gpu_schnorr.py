@@ -237,6 +237,51 @@ def test_dev_variants_match(hal, sch, batches, cname):
     assert SR.from_fe(d_h.cpu().numpy().view(np.uint64)[0], c.base) < c.base
 
 
+@pytest.mark.parametrize("cname", CURVES)
+def test_the_ladder_agrees_with_the_linear_combination(hal, sch, keys, cname):
+    """The two users of the shared quad ladder (quad_ladder.hpp) on one statement: the verdict of
+    halo_schnorr_verify_batch for item i and the "valid and the identity" byte of halo_point_lincomb_batch_dev for
+    -R_i + s_i G - e_i pk_i (e_i from halo_schnorr_hash_batch), each against the CPU restatement's verdict.
+    17 signatures over one-element messages: one quad more than a wave's 16; among them a wrong s, an identity pk
+    (signed by sk = 0: valid) and a pk off the curve.  The _dev form is the one called: the host form returns the
+    affine sums only, where an invalid item and an identity sum are both (0, 0); the byte is the _dev form's."""
+    import torch
+    c = P.CURVES[cname]
+    rng = np.random.default_rng(17)
+    sks, pks = keys[cname]["sk"], keys[cname]["pk"]
+    k = 17
+    items = []
+    for i in range(k):
+        msg = rand_msg(rng, c.base, 1)
+        sk, pk = (0, None) if i == 7 else (sks[i % 3], pks[i % 3])
+        R, s = SR.sign(cname, sk, int.from_bytes(rng.bytes(32), "little") % c.scalar, msg)
+        if i == 3:
+            s = (s + 1) % c.scalar
+        if i == 12:
+            pk = ((pk[0] + 1) % c.base, pk[1])
+        items.append((pk, msg, R, s))
+    exp = np.array([SR.verify(cname, *it) for it in items], dtype=np.uint8)
+    assert exp[3] == 0 and exp[7] == 1 and exp[12] == 0 and exp.sum() == k - 2
+    pk, R, s, msgs = encode(cname, items, 1)
+    got = sch.verify_batch(pk, R, s, msgs, cname)
+    assert np.array_equal(got, exp), np.nonzero(got != exp)[0]
+
+    e = [SR.from_fe(row, c.scalar) for row in sch.hash_message_batch(pk, R, msgs, cname)]
+    assert e == [SR.hash_message(cname, it[0], it[2], it[1]) for it in items]
+    neg_R = SR.points(cname, [None if it[2] is None else (it[2][0], -it[2][1] % c.base) for it in items])
+    G = SR.points(cname, [c.generator])[0]
+    pts = np.stack([np.stack([G, pk[i]]) for i in range(k)])
+    sc = np.stack([SR.fe_rows([items[i][3], -e[i] % c.scalar], c.scalar) for i in range(k)])
+    d_add, d_pts, d_sc = _cuda(neg_R), _cuda(pts), _cuda(sc)
+    d_out = torch.zeros((k, 16), dtype=torch.int64, device="cuda")
+    d_id = torch.full((k,), 7, dtype=torch.uint8, device="cuda")
+    sp = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    hal.check(hal.load().halo_point_lincomb_batch_dev(hal.CURVES[cname], _dev(d_add), _dev(d_pts), _dev(d_sc), k, 2,
+                                                     _dev(d_out), _dev(d_id), sp))
+    is_id = d_id.cpu().numpy()
+    assert np.array_equal(is_id, exp), np.nonzero(is_id != exp)[0]
+
+
 def test_reference_shape_and_asynchrony(hal, sch, keys):
     """crates/plonk/src/main.rs:39-43 verifies ONE (pk, message, signature) many times over: 4096 copies
     all verify.  The device-pointer call is asynchronous: several batches are queued and the stream is

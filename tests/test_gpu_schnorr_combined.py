@@ -231,7 +231,7 @@ def test_equal_points(hal, sch, data, cname):
 @pytest.mark.parametrize("cname", CURVES)
 def test_derived_weights(hal, sch, data, cname, msg_len):
     it, at = data(cname, msg_len)
-    for k in (1, 2, 3, 5, 64, 65):
+    for k in (1, 2, 3, 5, 21, 22, 64, 65):
         idx = list(np.arange(k) % 6)
         if k >= 5:
             idx[3] = at["R_off_curve"]

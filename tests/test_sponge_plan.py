@@ -7,6 +7,11 @@ e = 0 .. 33 absorbed elements (0 .. 5 cover every transition; 32 is a batch of 1
 squeezes.  The resulting mode and the permutation count must be those of oracle/poseidon.InnerSponge driven the
 same way (a subclass counts its _permute calls instead of running them).
 The elements per absorbed item are 2 for a point, 1 for an fq, and 2 / 1 for an fr on Pallas / Vesta.
+
+The launch plan of a batch of k sponges (the lane rule and the grid, which every sponge kernel's launcher reads) is
+swept against its restatement here: three lanes per sponge (21 sponges a wave) while their waves number at most
+eight per compute unit, else one lane (64 a wave), unless the tuning value pins 1 or 3; blocks of one wave up to
+4096 waves and of four waves beyond.
 """
 import os
 import shutil
@@ -18,6 +23,24 @@ import poseidon
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STARTS = [(0, 0), (0, 1), (0, 2), (1, 1), (1, 2)]
+TUNES = (0, 1, 3)      # the free choice and both pinned layouts
+CUS = (1, 8, 256, 304)
+
+
+def plan_ks(cu):
+    """Around a wave of either layout (20..22, 63..65), around the lane rule's switch at 21 * 8 * CU sponges and
+    around the switch of waves per block at 4096 / 4097 waves of either layout."""
+    edge = 21 * 8 * cu
+    return sorted({1, 20, 21, 22, 63, 64, 65, edge - 1, edge, edge + 1, 21 * 4096, 21 * 4096 + 1, 64 * 4096, 64 * 4096 + 1,
+                   1000003} - {0})
+
+
+def plan_ref(tune, cu, k):
+    waves3 = -(-k // 21)
+    lanes = tune if tune in (1, 3) else (3 if waves3 <= 8 * cu else 1)
+    waves = waves3 if lanes == 3 else -(-k // 64)
+    wpb = 4 if waves > 4096 else 1
+    return lanes, -(-waves // wpb), 64 * wpb
 
 
 class CountingSponge(poseidon.InnerSponge):
@@ -38,14 +61,16 @@ def dump(tmp_path_factory):
     exe = str(tmp_path_factory.mktemp("sponge_plan") / "sponge_plan_dump")
     subprocess.run([cxx, "-std=c++17", "-O2", "-Wall", "-I", os.path.join(ROOT, "halo_amd", "csrc"),
                     os.path.join(ROOT, "tests", "sponge_plan_dump.cpp"), "-o", exe], check=True)
-    out = subprocess.run([exe], input="steps 33 4\nitems 0 0\n", capture_output=True, text=True, check=True)
+    plans = "".join(f"plan {t} {cu} {k}\n" for t in TUNES for cu in CUS for k in plan_ks(cu))
+    out = subprocess.run([exe], input="steps 33 4\nitems 0 0\n" + plans, capture_output=True, text=True, check=True)
     rows = [l.split() for l in out.stdout.splitlines()]
     return ([tuple(int(x) for x in r[1:]) for r in rows if r[0] == "s"],
-            [tuple(int(x) for x in r[1:]) for r in rows if r[0] == "i"])
+            [tuple(int(x) for x in r[1:]) for r in rows if r[0] == "i"],
+            [tuple(int(x) for x in r[1:]) for r in rows if r[0] == "p"])
 
 
 def test_every_step_matches_the_inner_sponge(dump):
-    steps, _ = dump
+    steps = dump[0]
     assert len(steps) == 5 * 34 * 5
     seen = set()
     for sq, n, e, c, sq2, n2, perms in steps:
@@ -73,5 +98,30 @@ def test_the_cases_the_prover_transcript_takes(dump):
 
 
 def test_elements_per_item(dump):
-    _, items = dump
+    items = dump[1]
     assert sorted(items) == [(0, 0, 2), (0, 1, 2), (1, 0, 1), (1, 1, 2), (2, 0, 1), (2, 1, 1)]
+
+
+def test_the_launch_plan_matches_its_restatement(dump):
+    plans = dump[2]
+    assert [(t, cu, k) for t, cu, k, *_ in plans] == [(t, cu, k) for t in TUNES for cu in CUS for k in plan_ks(cu)]
+    for t, cu, k, lanes, blocks, threads in plans:
+        assert (lanes, blocks, threads) == plan_ref(t, cu, k), (t, cu, k)
+
+
+def test_the_grid_covers_every_sponge_and_wastes_less_than_a_block(dump):
+    for t, cu, k, lanes, blocks, threads in dump[2]:
+        per_block = (threads // 64) * (21 if lanes == 3 else 64)
+        assert threads in (64, 256) and lanes in (1, 3)
+        assert blocks * per_block >= k > (blocks - 1) * per_block, (t, cu, k)
+        if t in (1, 3):
+            assert lanes == t
+
+
+def test_the_lane_rule_switches_at_eight_waves_per_compute_unit(dump):
+    free = {(cu, k): lanes for t, cu, k, lanes, _, _ in dump[2] if t == 0}
+    for cu in CUS:
+        assert free[cu, 21 * 8 * cu] == 3 and free[cu, 21 * 8 * cu + 1] == 1
+    grid = {(t, k): (blocks, threads) for t, cu, k, _, blocks, threads in dump[2] if cu == 256}
+    assert grid[3, 21 * 4096] == (4096, 64) and grid[3, 21 * 4096 + 1] == (1025, 256)
+    assert grid[1, 64 * 4096] == (4096, 64) and grid[1, 64 * 4096 + 1] == (1025, 256)

@@ -139,6 +139,7 @@ SIGNATURES = {
     "halo_schnorr_verify_batch_dev": [ctypes.c_int, _vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp],
     "halo_schnorr_verify_combined": [ctypes.c_int, _vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp],
     "halo_schnorr_verify_combined_dev": [ctypes.c_int, _vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp],
+    "halo_schnorr_verify_bisect_dev": [ctypes.c_int, _vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp],
     "halo_schnorr_batch_rho": [ctypes.c_int, _vp, _vp, _vp, _vp, _sz, _sz, _vp],
     "halo_schnorr_batch_rho_dev": [ctypes.c_int, _vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp],
     "halo_generator_mul_batch": [ctypes.c_int, _vp, _sz, _vp],

@@ -1,5 +1,6 @@
 // Runtime: error state, device selection, per-device state, buffers.
 #include "runtime.hpp"
+#include "schnorr_bisect.hpp"
 
 #include <atomic>
 #include <cstdio>
@@ -181,7 +182,8 @@ static void prof_drain() {
 static const char* const kTuneNames[TUNE_COUNT] = {"ipa_weighted", "ipa_tail",           "ipa_srs_tail_n", "ipa_mat_n",
                                                    "msm_multi_max", "ipa_pool_keep_bytes", "ntt_big_max_log",
                                                    "ntt_even_split", "ipa_pair_max",    "poseidon_lanes",
-                                                   "decide_group_scalars", "decide_bisect",  "decide_rho_fs"};
+                                                   "decide_group_scalars", "decide_bisect",  "decide_rho_fs",
+                                                   "schnorr_bisect", "schnorr_bisect_leaf", "schnorr_bisect_pass_items"};
 // ntt_big_max_log: the largest transform split into two passes on 2048-element blocks (2^17..2^this);
 // larger ones, and any below 2^17, take passes of <= 8 bits on 1024-element blocks (ntt.hip ntt_radices)
 // ntt_even_split: passes of <= 8 bits split into even radices where possible (ntt_radices)
@@ -194,9 +196,15 @@ static const char* const kTuneNames[TUNE_COUNT] = {"ipa_weighted", "ipa_tail",  
 // 1 bisect it on the device (decider.hip decide_bisect_device)
 // decide_rho_fs: what a null rho means to the batched decider's entry points: 0 exact mode, 1 combined mode with
 // weights derived from the batch by Fiat-Shamir on the device (decide_rho.hip); read once per call, at the entry point
-static const long long kTuneDefault[TUNE_COUNT] = {1, 1, 4096, 2048, 1ll << 18, 1ll << 30, 22, 0, 1ll << 19, 0, 1ll << 25, 0, 0};
+// schnorr_bisect: what halo_schnorr_verify_combined does with a rejected combined batch: 0 the ladder over the whole
+// batch, 1 the descent of schnorr_bisect.hpp on the device (schnorr_bisect.hip sig_bisect_device)
+// schnorr_bisect_leaf, schnorr_bisect_pass_items: that descent's L (a failing node of at most L items goes to the
+// ladder) and c (ladder items that cost as much as one pass; the budget rule)
+static const long long kTuneDefault[TUNE_COUNT] = {1, 1, 4096, 2048, 1ll << 18, 1ll << 30, 22, 0, 1ll << 19, 0, 1ll << 25, 0, 0,
+                                                   0, SIG_BISECT_LEAF_DEFAULT, SIG_BISECT_PASS_ITEMS_DEFAULT};
 static std::atomic<long long> g_tune[TUNE_COUNT] = {{1},  {1},  {4096}, {2048}, {1ll << 18},
-                                                    {1ll << 30}, {22}, {0},  {1ll << 19}, {0}, {1ll << 25}, {0}, {0}};
+                                                    {1ll << 30}, {22}, {0},  {1ll << 19}, {0}, {1ll << 25}, {0}, {0},
+                                                    {0}, {SIG_BISECT_LEAF_DEFAULT}, {SIG_BISECT_PASS_ITEMS_DEFAULT}};
 long long tuning(TuneKey k) { return g_tune[k].load(std::memory_order_relaxed); }
 static int tune_index(const char* key) {
     if (!key) return -1;
@@ -258,7 +266,7 @@ int halo_init(int device) {
 
 const char* halo_last_error(void) { return g_last_error.c_str(); }
 
-int halo_abi_version(void) { return 113; }
+int halo_abi_version(void) { return 114; }
 
 // Releases the library's HIP objects while the runtime is alive: pending profiling events, the MSM
 // pipeline's streams and events, the scratch fence events.  Python registers it with atexit

@@ -39,7 +39,8 @@ void clear_error();
 // ---- tuning (halo_set_tuning): path selections the parity tests pin; read on every use
 enum TuneKey { TUNE_IPA_WEIGHTED, TUNE_IPA_TAIL, TUNE_IPA_SRS_TAIL_N, TUNE_IPA_MAT_N, TUNE_MSM_MULTI_MAX, TUNE_IPA_POOL_KEEP,
                TUNE_NTT_BIG_MAX_LOG, TUNE_NTT_EVEN_SPLIT, TUNE_IPA_PAIR_MAX, TUNE_POSEIDON_LANES, TUNE_DECIDE_GROUP_SCALARS,
-               TUNE_DECIDE_BISECT, TUNE_DECIDE_RHO_FS, TUNE_COUNT };
+               TUNE_DECIDE_BISECT, TUNE_DECIDE_RHO_FS, TUNE_SCHNORR_BISECT, TUNE_SCHNORR_BISECT_LEAF,
+               TUNE_SCHNORR_BISECT_PASS_ITEMS, TUNE_COUNT };
 long long tuning(TuneKey k);
 
 // ---- device buffers ---------------------------------------------------------------------------
@@ -129,7 +130,8 @@ struct DeviceState {
     // halo_shutdown); the derived keys and challenges of a signing batch
     DevBuf fixed_base_tab[2];
     DevBuf schnorr_sign;
-    // schnorr_combined.hip: the combined pass's e, liveness, derived weights, MSM terms and outputs; the hash tree
+    // schnorr_combined.hip: the combined pass's e, liveness, derived weights, MSM terms and outputs; the hash tree,
+    // and once the pass has run the descent's prefix sums, node tables and defects (schnorr_bisect.hip)
     DevBuf schnorr_comb[2];
     DevBuf lincomb_terms;   // the terms of a batch of linear combinations (lincomb.hip): packed XYZZ, then a byte each
     DevBuf decider[4];       // decider.hip: h rows / coefficients, half-tables, U' and masks, the xis of a check

@@ -21,6 +21,10 @@
 //   (msm_device)      D over the 2 k + 1 terms, MsmOpts::Sync(): the stream waits for the tail on the device
 //   k_sig_finish      combined = D is the identity and no flag; ok[i] = live_i && combined
 //
+// A rejected pass leaves its terms, liveness bytes, e and D on the device (SigScratch, schnorr.hpp): the host form
+// resolves it by the ladder over every item or, under the tuning key schnorr_bisect, by the descent of
+// schnorr_bisect.hip, which halo_schnorr_verify_bisect_dev always takes.
+//
 // Derived weights (no caller RNG), after decide_rho.hip, under labels of their own (rho_plan.hpp):
 //   k_sig_leaves      leaf_i = the inner sponge's squeeze after Sponge(SIG_BATCH_LEAF).absorb_fr(e_i).absorb_fr(s_i);
 //                     0 with nothing read for an item that is not live.  e_i is already a collision-resistant digest
@@ -42,9 +46,6 @@
 #include "sponge_launch.hpp"
 
 namespace halo {
-
-constexpr int SIG_THREADS = 256;
-constexpr int SIG_WAVES = SIG_THREADS / 64;
 
 template <class Cv>
 __global__ __launch_bounds__(SIG_THREADS) void k_sig_live(const uint4* __restrict__ pk, const uint4* __restrict__ R, size_t k,
@@ -152,11 +153,12 @@ __global__ __launch_bounds__(SIG_THREADS) void k_sig_sum(const uint4* __restrict
 template <class Cv>
 __global__ __launch_bounds__(SIG_THREADS) void k_sig_finish(const uint4* __restrict__ D, const uint8_t* __restrict__ flag,
                                                             const uint8_t* __restrict__ live, size_t k, uint8_t* __restrict__ ok,
-                                                            uint8_t* __restrict__ combined) {
+                                                            uint8_t* __restrict__ combined, uint8_t* __restrict__ combined_own) {
     using F = typename Cv::Base;
     const size_t i = (size_t)blockIdx.x * SIG_THREADS + threadIdx.x;
     const bool comb = xyzz_is_id(xyzz_load<F>(D)) && flag[0] == 0;
     if (i == 0 && combined) combined[0] = comb ? 1 : 0;
+    if (i == 0) combined_own[0] = comb ? 1 : 0;  // the pass's own copy, beside the flag (SigScratch::bad)
     if (i < k) ok[i] = live[i] != 0 && comb ? 1 : 0;
 }
 
@@ -202,21 +204,18 @@ __global__ __launch_bounds__(256) void k_sig_leaves(const uint32_t* __restrict__
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-// st->schnorr_comb[0] for a batch of k: what one combined pass or one derivation keeps on the device.
-struct SigScratch {
-    size_t nb;  // blocks of k_sig_prepare
-    uint8_t *e_ark, *live, *rho, *bases, *scalars, *partials, *bad, *D;
-};
+// SigScratch (schnorr.hpp) for a batch of k, in st->schnorr_comb[0].
 static int sig_scratch(DeviceState* st, size_t k, SigScratch& w) {
     const size_t n = 2 * k + 1;
     w.nb = grid_for(k, SIG_THREADS);
     ScratchLayout lay;
     const size_t o_e = lay.take(k * 32), o_live = lay.take(k), o_rho = lay.take(k * 32), o_bases = lay.take(n * 64),
-                 o_scalars = lay.take(n * 32), o_part = lay.take(w.nb * 32), o_bad = lay.take(w.nb + 1), o_D = lay.take(128);
+                 o_scalars = lay.take(n * 32), o_part = lay.take(w.nb * 32), o_bad = lay.take(w.nb + 2), o_D = lay.take(128);
     HALO_CHECK(st->schnorr_comb[0].reserve(lay.total()));
     uint8_t* base = st->schnorr_comb[0].as<uint8_t>();
     w.e_ark = base + o_e, w.live = base + o_live, w.rho = base + o_rho, w.bases = base + o_bases;
     w.scalars = base + o_scalars, w.partials = base + o_part, w.bad = base + o_bad, w.D = base + o_D;
+    w.rho_used = nullptr;
     return HALO_OK;
 }
 
@@ -253,19 +252,16 @@ static int sig_rho_device(DeviceState* st, int curve, const void* d_s, size_t ms
     return HALO_OK;
 }
 
-// The combined pass, every launch on `s`, no host wait: d_ok[i] = live_i && combined, the byte also at d_combined
-// (may be null).  d_rho null: derived weights.  st->mu and a ScratchUse of `s` held, k >= 1 within sig_check_args' bound.
-// Leaves e's canonical words in st->schnorr_e for the exact ladder.
-static int sig_combined_device(DeviceState* st, int curve, const void* d_pk, const void* d_R, const void* d_s,
-                               const void* d_msgs, size_t msg_len, size_t k, const void* d_rho, void* d_ok, void* d_combined,
-                               hipStream_t s) {
-    SigScratch w;
+// The combined pass (schnorr.hpp).
+int sig_combined_device(DeviceState* st, int curve, const void* d_pk, const void* d_R, const void* d_s, const void* d_msgs,
+                        size_t msg_len, size_t k, const void* d_rho, void* d_ok, void* d_combined, hipStream_t s, SigScratch& w) {
     HALO_CHECK(sig_scratch(st, k, w));
     HALO_CHECK(sig_hash_live(st, curve, d_pk, d_R, d_msgs, msg_len, k, w, s));
     if (!d_rho) {
         HALO_CHECK(sig_rho_device(st, curve, d_s, msg_len, k, w, w.rho, s));
         d_rho = w.rho;
     }
+    w.rho_used = d_rho;
     {
         ProfScope prof("sig_prepare", s);
         DISPATCH_CURVE(curve, Cv, {
@@ -289,14 +285,24 @@ static int sig_combined_device(DeviceState* st, int curve, const void* d_pk, con
     ProfScope prof("sig_finish", s);
     DISPATCH_CURVE(curve, Cv, {
         HALO_LAUNCH(prof, k_sig_finish<Cv>, dim3(grid_for(k, SIG_THREADS)), dim3(SIG_THREADS), 0, s, (const uint4*)w.D,
-                    (const uint8_t*)(w.bad + w.nb), (const uint8_t*)w.live, k, (uint8_t*)d_ok, (uint8_t*)d_combined);
+                    (const uint8_t*)(w.bad + w.nb), (const uint8_t*)w.live, k, (uint8_t*)d_ok, (uint8_t*)d_combined,
+                    w.bad + w.nb + 1);
     });
     HALO_HIP(hipGetLastError());
     return HALO_OK;
 }
 
+// The pass's two bytes on the host, after a wait for `s`: descend iff it rejected and no live item had a bad rho.
+static int sig_rejected(const SigScratch& w, hipStream_t s, uint8_t& combined, bool& descend) {
+    uint8_t two[2] = {0, 0};  // the bad-rho flag, the combined byte
+    HALO_CHECK(copy_d2h(two, w.bad + w.nb, 2, s));
+    combined = two[1];
+    descend = !two[1] && !two[0];
+    return HALO_OK;
+}
+
 // check_schnorr_args, and the k whose 2 k + 1 terms msm_device takes.
-static int sig_check_args(const char* call, int curve, const void* pk, const void* R, const void* s, const void* msgs,
+int sig_check_args(const char* call, int curve, const void* pk, const void* R, const void* s, const void* msgs,
                           size_t msg_len, size_t k, const void* out, bool& done) {
     HALO_CHECK(check_schnorr_args(call, curve, pk, R, s, true, msgs, msg_len, k, out, done));
     if (!done && k > (MSM_DEVICE_MAX_N - 1) / 2)
@@ -358,7 +364,29 @@ extern "C" int halo_schnorr_verify_combined_dev(halo_curve_t curve, const void* 
     std::lock_guard<std::mutex> g(st->mu);
     hipStream_t s = (hipStream_t)stream;
     ScratchUse su(st, s);
-    return sig_combined_device(st, curve, d_pk, d_R, d_s, d_msgs, msg_len, k, d_rho, d_ok, d_combined, s);
+    SigScratch w;
+    return sig_combined_device(st, curve, d_pk, d_R, d_s, d_msgs, msg_len, k, d_rho, d_ok, d_combined, s, w);
+}
+
+extern "C" int halo_schnorr_verify_bisect_dev(halo_curve_t curve, const void* d_pk, const void* d_R, const void* d_s,
+                                              const void* d_msgs, size_t msg_len, size_t k, const void* d_rho, void* d_ok,
+                                              void* d_combined, void* stream) {
+    clear_error();
+    bool done;
+    HALO_CHECK(sig_check_args("halo_schnorr_verify_bisect_dev", curve, d_pk, d_R, d_s, d_msgs, msg_len, k, d_ok, done));
+    if (done) return HALO_OK;
+    DeviceState* st = current_state();
+    if (!st) return HALO_EDEVICE;
+    std::lock_guard<std::mutex> g(st->mu);
+    hipStream_t s = (hipStream_t)stream;
+    ScratchUse su(st, s);
+    SigScratch w;
+    HALO_CHECK(sig_combined_device(st, curve, d_pk, d_R, d_s, d_msgs, msg_len, k, d_rho, d_ok, d_combined, s, w));
+    uint8_t combined;
+    bool descend;
+    HALO_CHECK(sig_rejected(w, s, combined, descend));
+    if (!descend) return HALO_OK;  // accepted, or a live item's rho is bad: every byte stays 0
+    return sig_bisect_device(st, curve, d_pk, d_R, d_s, k, w, d_ok, s);
 }
 
 extern "C" int halo_schnorr_verify_combined(halo_curve_t curve, const halo_wrapped_point_t* pk, const halo_wrapped_point_t* R,
@@ -381,11 +409,17 @@ extern "C" int halo_schnorr_verify_combined(halo_curve_t curve, const halo_wrapp
     HALO_CHECK(st->scratch[1].reserve(align256(k) + 1));
     uint8_t* dout = st->scratch[1].as<uint8_t>();
     uint8_t* dcomb = dout + align256(k);
-    HALO_CHECK(sig_combined_device(st, curve, at[0], at[1], at[2], at[3], msg_len, k, at[4], dout, dcomb, s));
+    SigScratch w;
+    HALO_CHECK(sig_combined_device(st, curve, at[0], at[1], at[2], at[3], msg_len, k, at[4], dout, dcomb, s, w));
     uint8_t combined = 0;
-    HALO_CHECK(copy_d2h(&combined, dcomb, 1, s));
-    if (!combined)  // some live item fails: the exact verdicts, over the e already on the device
-        HALO_CHECK(schnorr_ladder_device(st, curve, at[0], at[1], at[2], st->schnorr_e.ptr, k, dout, s));
+    bool descend;
+    HALO_CHECK(sig_rejected(w, s, combined, descend));
+    if (!combined) {  // some live item fails: the exact verdicts, over the e already on the device
+        if (descend && tuning(TUNE_SCHNORR_BISECT) > 0)
+            HALO_CHECK(sig_bisect_device(st, curve, at[0], at[1], at[2], k, w, dout, s));
+        else
+            HALO_CHECK(schnorr_ladder_device(st, curve, at[0], at[1], at[2], st->schnorr_e.ptr, k, dout, s));
+    }
     if (combined_out) *combined_out = combined;
     return copy_d2h(ok_out, dout, k, s);
 }

@@ -4,7 +4,8 @@ items: the reference's benchmark verifies 40 000 signatures in a parallel loop (
 
 verify_batch's default is exact, one ladder per signature; with ``rhos`` it checks the whole batch by one MSM of
 2 k + 1 terms under the caller's random weights or under weights derived from the batch (batch_weights), which the
-reference does not have: an accept is then sound up to about k / 2^254, a reject is resolved exactly.
+reference does not have: an accept is then sound up to about k / 2^254, a reject is resolved exactly, by every ladder
+or, with ``bisect=True``, by a descent that halves the failing parts of the batch.
 
 Key derivation and signing run on the device too (public_key_batch, sign_batch: a fixed-base comb over the
 generator, halo_generator_mul_batch / halo_schnorr_sign_batch).  The library never draws randomness: secrets and
@@ -67,7 +68,7 @@ def hash_message_batch(pk, R, msgs, curve="pallas") -> np.ndarray:
     return out
 
 
-def verify_batch(pk, R, s, msgs, curve="pallas", rhos=None, return_combined=False):
+def verify_batch(pk, R, s, msgs, curve="pallas", rhos=None, return_combined=False, bisect=False):
     """lib.rs:71-79 ``PublicKey::verify`` for k signatures (R[i], s[i]) over msgs[i] under pk[i]:
     (k,) uint8, 1 = valid.  A pk or R that is neither (0, 0) nor on the curve gives 0.
 
@@ -76,7 +77,16 @@ def verify_batch(pk, R, s, msgs, curve="pallas", rhos=None, return_combined=Fals
     (halo_schnorr_verify_combined): ONE MSM of 2 k + 1 terms, and only if that rejects the exact ladders, so the
     verdicts are per item either way.  The caller's weights must be drawn uniformly AFTER the signatures are fixed; an
     accept is then sound up to about k / 2^254 (derived weights: Q k / 2^254 over Q batches tried), a reject is exact.
-    ``return_combined``: also return the combined pass's byte (1 = it held; None for the exact call)."""
+    ``return_combined``: also return the combined pass's byte (1 = it held; None for the exact call).
+
+    ``bisect`` (needs ``rhos``): a rejected combined batch is resolved by bisection on the device (tuning key
+    schnorr_bisect = 1 for this call; halo_schnorr_verify_bisect_dev states the method) instead of the ladder over every
+    item: a failing node is halved at the cost of one MSM over its left half, down to single items or to slices small
+    enough for the ladder.  The contract changes for the items of a rejected batch: a reject found by the descent is
+    exact; an item in a half that passes is accepted up to about 1 / 2^254 per node tested, for weights drawn after
+    the signatures were fixed (with weights known in advance, errors that cancel inside one half pass there)."""
+    if bisect and rhos is None:
+        raise ValueError("bisect=True needs rhos (weights, or 'fs'): the exact call has no combined batch to bisect")
     H.ensure_device()
     pk, R, s = H.point_array(pk), H.point_array(R), H.fe_array(s)
     k = len(pk)
@@ -88,8 +98,9 @@ def verify_batch(pk, R, s, msgs, curve="pallas", rhos=None, return_combined=Fals
         return (out, None) if return_combined else out
     rho, _ = H.fs_rhos(rhos, k)
     comb = np.zeros(1, dtype=np.uint8)
-    H.check(H.load().halo_schnorr_verify_combined(_curve(curve), H.ptr(pk), H.ptr(R), H.ptr(s), H.ptr(m), ml, k, H.ptr(rho),
-                                                  H.ptr(out), H.ptr(comb)))
+    with H.tuning(schnorr_bisect=1) if bisect else H.tuning():
+        H.check(H.load().halo_schnorr_verify_combined(_curve(curve), H.ptr(pk), H.ptr(R), H.ptr(s), H.ptr(m), ml, k, H.ptr(rho),
+                                                      H.ptr(out), H.ptr(comb)))
     return (out, int(comb[0])) if return_combined else out
 
 

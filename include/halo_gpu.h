@@ -88,8 +88,12 @@ int halo_stream_sync(void* stream);
  * default, decide every live instance again in exact mode; 1 bisect the batch on the device, see
  * halo_pcdl_decide_bisect_dev), "decide_rho_fs" (what a NULL rho means to the batched decider's entry points: 0, the
  * default, exact mode; 1 combined mode with weights derived from the batch by Fiat-Shamir on the device, see
- * halo_pcdl_decide_rho; each call reads it once, on entry).  Every setting but "decide_rho_fs" = 1 yields the same
- * results (that one trades the exact accept of a NULL rho for the bound stated at halo_pcdl_decide_rho); the parity
+ * halo_pcdl_decide_rho; each call reads it once, on entry), "schnorr_bisect" (what halo_schnorr_verify_combined does
+ * with a combined batch that is rejected: 0, the default, the ladder over every item; 1 the descent of
+ * halo_schnorr_verify_bisect_dev), "schnorr_bisect_leaf" and "schnorr_bisect_pass_items" (that descent's L and c).
+ * Every setting but "decide_rho_fs" = 1 and "schnorr_bisect" = 1 yields the same results (the first trades the exact
+ * accept of a NULL rho for the bound stated at halo_pcdl_decide_rho, the second the exact accept of an item inside a
+ * rejected batch for the bound stated at halo_schnorr_verify_bisect_dev); the parity
  * tests pin each path with it.  The reference has no counterpart (host-side knob of this backend only).
  * HALO_EINVAL on an unknown key. */
 int halo_set_tuning(const char* key, long long value);
@@ -511,6 +515,31 @@ int halo_schnorr_verify_combined(halo_curve_t curve, const halo_wrapped_point_t*
 int halo_schnorr_verify_combined_dev(halo_curve_t curve, const void* d_pk, const void* d_R, const void* d_s,
                                      const void* d_msgs, size_t msg_len, size_t k, const void* d_rho, void* d_ok,
                                      void* d_combined, void* stream);
+/* The combined pass and, where it rejects, per-item verdicts by bisection on the device instead of every ladder
+ * (arguments and refusals those of halo_schnorr_verify_combined_dev; d_rho NULL: derived weights; k = 0: HALO_OK).
+ * With D(S) the defect above restricted to the items of S, D is additive over disjoint sets, so a failing node
+ * [lo, hi) splits into [lo, lo + (hi - lo) / 2) and the rest at the cost of ONE pass: the left half's defect is an MSM
+ * over that half's 2 (mid - lo) terms, which the combined pass left on the device, plus one generator multiple from a
+ * prefix sum of rho_i s_i, and D(right) = D(node) - D(left).  Nothing is hashed again.  A failing node of one item is
+ * a verdict.  Two rules bound the cost under the tuning keys "schnorr_bisect_leaf" (L) and
+ * "schnorr_bisect_pass_items" (c, the ladder items that cost as much as one pass): a failing node of at most L items
+ * is resolved by the exact ladder over its slice, and before a level of f nodes with p passes done the descent stops
+ * if (p + f) c > k, every node of that level going to the ladder.  The passes then never cost more than the ladder
+ * over the whole batch, and the ladder slices are disjoint: a rejected batch costs at most about twice the
+ * whole-batch ladder, whatever the forger does.  At k < c or k <= L the root goes straight to the ladder (k = 1: the
+ * root's defect is the item's own verdict, no ladder runs).
+ * d_ok: the per-item verdicts; d_combined (1 byte, may be NULL): the root pass's byte.  The call reads that byte and
+ * so waits on `stream`, then once per level of the descent.  A live item whose rho is zero or not below the modulus
+ * still gives combined = 0 and every d_ok byte 0, with no descent.
+ * Contract: a reject found by the descent is exact (a single item's defect is nonzero iff the item is wrong, its rho
+ * being nonzero; the ladder is exact).  An item in a half that passes is accepted up to a signer guessing the
+ * weights, about 1 / 2^254 per node tested, for weights drawn after the signatures were fixed: with weights known in
+ * advance, errors that cancel inside one half pass there (s_0 + x, s_1 - x under rho = (1, 1)).
+ * halo_schnorr_verify_combined takes this descent over a rejected batch, in place of the whole-batch ladder, when the
+ * tuning key "schnorr_bisect" is 1 (default 0: unchanged). */
+int halo_schnorr_verify_bisect_dev(halo_curve_t curve, const void* d_pk, const void* d_R, const void* d_s,
+                                   const void* d_msgs, size_t msg_len, size_t k, const void* d_rho, void* d_ok,
+                                   void* d_combined, void* stream);
 /* The weights that a NULL rho means above, derived from the batch itself by Fiat-Shamir on the device, as
  * halo_pcdl_decide_rho derives the decider's: rho_out is k scalars of `curve`, and two runs over one batch agree.
  * All hashing is the curve's sponge (Sponge<P> of outer_sponge.rs) under three protocol labels SIG_BATCH_LEAF = 7,

@@ -6,7 +6,7 @@
 // and FFT polynomial multiplication (`&Poly * &Poly`, protocol.rs:132-139, pcdl.rs:215).
 //
 // Algorithm: Stockham auto-sort, radix R = 2^r per pass (Σ r = log N; the pass split is
-// `ntt_radices` below: two passes of up to 11 bits for 2^17..2^22, passes of <= 8 bits otherwise),
+// ntt_plan.hpp's: two passes of up to 11 bits for 2^17..2^22, passes of <= 8 bits otherwise),
 // natural order in and out, out-of-place ping-pong.  One workgroup owns T = E / R consecutive
 // columns j of a pass (E = 1024 or 2048 elements per workgroup): it loads x[j + r N/R] (T-element
 // contiguous runs), multiplies by the Stockham twiddle read coalesced from the per-pass
@@ -20,21 +20,18 @@
 
 #include "dispatch.hpp"
 #include "ntt.hpp"
+#include "ntt_plan.hpp"
 #include "points.hpp"
 #include "runtime.hpp"
 
 namespace halo {
 
-constexpr int NTT_E = 1024;        // elements per workgroup for passes with R <= 256
-constexpr int NTT_E_BIG = 2048;    // ... and for the two-pass split of 2^17..2^22 (R up to 2048)
-// Elements per thread: radix-4 register groups, two stages per LDS round trip.  (Round 3 measured radix-8
-// groups on the 2048-element blocks -- 4 LDS round trips per 11-bit pass instead of 6 -- slower: 192 VGPRs
-// leave 2 waves per SIMD and the barrier waits were hidden worse than they were saved.)
-constexpr int NTT_EPT = 4;
-constexpr int NTT_MAX_LOG_R_MULTI = 8;
+// (the block sizes, NTT_EPT, the radix bounds and every host-side decision: ntt_plan.hpp)
 constexpr int NTT_TW_MAX = 2048;  // stage-twiddle table entries (stages 0..10), read through L1/L2
 constexpr int NTT_TW_U4 = 3;      // one stage twiddle: its 9 limbs in a 48-B entry (no unpacking in the groups)
-constexpr unsigned NTT_FULL_TABLE_MAX_LOG = 24;  // per-pass twiddle tables up to 2^24
+static_assert(NTT_LDS_BYTES_PER_ELEM == NLIMB * 4, "the plan's LDS bytes are the limb-major layout's");
+static_assert(NTT_TW_MAX == (1 << NTT_MAX_LOG_R_BIG), "a stage twiddle for every stage of the widest pass");
+static_assert(sizeof(DeviceState::Twiddles::pass) / sizeof(DevBuf) >= NTT_MAX_PASSES, "a table slot per pass");
 
 struct NttPassArgs {
     const uint4* in;
@@ -388,8 +385,10 @@ __global__ __launch_bounds__(NE / NTT_EPT, 4) void k_ntt_pass(NttPassArgs a) {
         }
     }
     // on the wide blocks the short group goes first (r mod 2 stages), so later groups stay in range
+    // (ntt_plan.hpp's ntt_g0(NE, r), which the prune rule is written in; tests/test_ntt_plan.py pins the agreement.
+    // The call in place of the expression swaps two operand bytes in every instantiation, so the expression stays)
     const uint32_t G0 = (NE >= NTT_E_BIG && (r & 1)) ? 1u : (r < 2u ? r : 2u);
-    if (!a.prune) ntt_first<F>(v, G0, a.stage_tw);  // (pruned: host guarantees prune >= G0)
+    if (!a.prune) ntt_first<F>(v, G0, a.stage_tw);  // (pruned: ntt_pass0_prune grants prune >= ntt_g0 only)
     {
         const uint32_t pb = ntt_swz<NE>(base);
 #pragma unroll
@@ -622,74 +621,30 @@ static int launch_pow_table(uint4* out, size_t count, const Fe<F>& base, uint64_
     return HALO_OK;
 }
 
-// Pass split: N <= 2^8 in one pass; 2^17..2^22 in two passes of up to 11 bits on 2048-element
-// blocks (one fewer pass than the 8-bit split: one pre-twiddle multiplication and one HBM round
-// trip per element saved; measured A/B on one box: 2^20 pair 0.28 -> 0.25 ms, 2^22 equal at
-// 1.03 ms, where the single-column 11-bit pass loses on its strided 32-B loads what it saves in
-// work); everything else in passes of <= 8 bits on 1024-element blocks.
-constexpr unsigned NTT_MAX_LOG_R_BIG = 11;
-static std::vector<unsigned> ntt_radices(unsigned logn) {
-    std::vector<unsigned> r;
-    if (logn <= NTT_MAX_LOG_R_MULTI) {
-        r.push_back(logn);
-        return r;
-    }
-    if (logn >= 17 && logn <= std::min<long long>(2 * NTT_MAX_LOG_R_BIG, tuning(TUNE_NTT_BIG_MAX_LOG))) {
-        r.push_back((logn + 1) / 2);
-        r.push_back(logn / 2);
-        return r;
-    }
-    const unsigned passes = (logn + NTT_MAX_LOG_R_MULTI - 1) / NTT_MAX_LOG_R_MULTI;
-    if (tuning(TUNE_NTT_EVEN_SPLIT)) {
-        // even radices where possible (an odd pass ends in a one-stage group: a whole LDS round trip
-        // and normalization for half a group's butterflies): 8s, trimmed by 2 from the back, at most
-        // one odd pass (2^22 = 8 + 8 + 6, 2^23 = 8 + 8 + 7)
-        r.assign(passes, (unsigned)NTT_MAX_LOG_R_MULTI);
-        unsigned excess = passes * NTT_MAX_LOG_R_MULTI - logn;
-        for (unsigned k = passes; excess >= 2; k = (k == 1 ? passes : k - 1)) {
-            r[k - 1] -= 2;
-            excess -= 2;
-        }
-        if (excess) r[passes - 1] -= 1;
-        return r;
-    }
-    unsigned left = logn;
-    for (unsigned p = 0; p < passes; p++) {
-        unsigned take = (left + (passes - p) - 1) / (passes - p);
-        r.push_back(take);
-        left -= take;
-    }
-    return r;
+// The plan of a transform under the tunings as they stand: read once per transform and handed down (ntt_plan.hpp)
+static NttPlan ntt_plan_now(unsigned logn, int inverse, bool in_place, unsigned prune_request = 0) {
+    return ntt_plan(logn, inverse != 0, in_place, prune_request, tuning(TUNE_NTT_BIG_MAX_LOG),
+                    tuning(TUNE_NTT_EVEN_SPLIT) != 0);
 }
 
-// the split as one key (5 bits per pass) for the twiddle-table cache
-static uint64_t ntt_split_key(const std::vector<unsigned>& rad) {
-    uint64_t k = 0;
-    for (unsigned x : rad) k = (k << 5) | x;
-    return k;
+// ntt_check's refusals as a status with its message (NttCheck::Empty is the caller's to return HALO_OK on)
+static int ntt_refusal(unsigned log_n, size_t batch) {
+    switch (ntt_check(log_n, batch)) {
+        case NttCheck::LogTooLarge: return set_error(HALO_EINVAL, "NTT domain 2^%u too large", log_n);
+        case NttCheck::BatchTooLarge:
+            return set_error(HALO_EINVAL, "NTT batch %zu too large: at most %zu transforms per call", batch, NTT_MAX_BATCH);
+        default: return HALO_OK;
+    }
 }
 
-// Stages of pass 0 (radix 2^lr) that a zero tail lets the pass skip (NttPassArgs::prune): only when
-// they cover its first register group; on one-column wide blocks a trailing single-stage group would
-// reach past the column, so the stages left after the pruned ones must pair up (as G0 = 1 arranges).
-static unsigned ntt_pass0_prune(unsigned lr, unsigned prune) {
-    if (!prune) return 0;
-    const bool big = lr > NTT_MAX_LOG_R_MULTI;
-    const unsigned lg = 2u;
-    const unsigned g0 = (big && (lr % lg)) ? lr % lg : std::min(lr, lg);
-    unsigned pr = std::min(prune, lr);
-    while (big && pr > 0 && ((lr - pr) % lg)) pr--;
-    return (pr >= g0 && pr < lr) ? pr : 0u;
-}
-
-// `rad`: the pass split the caller launches with (ntt_radices read once per transform, so a concurrent
-// halo_set_tuning of the split keys cannot pair tables built for one split with passes of another)
+// The tables of the transform `pl` plans: cached under (field, log n, direction, pl.split_key), so the per-pass
+// tables always match the passes the caller launches
 template <class F>
-static int get_twiddles(DeviceState* st, int field, unsigned logn, int inverse, const std::vector<unsigned>& rad,
-                        DeviceState::Twiddles** out, hipStream_t s) {
-    const uint64_t split = ntt_split_key(rad);
+static int get_twiddles(DeviceState* st, int field, const NttPlan& pl, DeviceState::Twiddles** out, hipStream_t s) {
+    const unsigned logn = pl.logn;
+    const int inverse = pl.inverse;
     for (auto& t : st->tw)
-        if (t->field == field && t->logn == (int)logn && t->inverse == inverse && t->split == split) {
+        if (t->field == field && t->logn == (int)logn && t->inverse == inverse && t->split == pl.split_key) {
             *out = t.get();
             return HALO_OK;
         }
@@ -697,9 +652,9 @@ static int get_twiddles(DeviceState* st, int field, unsigned logn, int inverse, 
     t->field = field;
     t->logn = (int)logn;
     t->inverse = inverse;
-    t->split = split;
-    t->lo_bits = (int)((logn + 1) / 2);
-    const size_t nlo = (size_t)1 << t->lo_bits, nhi = (size_t)1 << (logn - t->lo_bits);
+    t->split = pl.split_key;
+    t->lo_bits = (int)pl.lo_bits;
+    const size_t nlo = pl.nlo, nhi = pl.nhi;
     HALO_CHECK(t->lo.reserve(nlo * 32));
     HALO_CHECK(t->hi.reserve(nhi * 32));
     const Fe<F> w = host_fe<F>(inverse ? F::OMEGA_INV[logn] : F::OMEGA[logn]);
@@ -714,104 +669,92 @@ static int get_twiddles(DeviceState* st, int field, unsigned logn, int inverse, 
                            t->stage.as<uint4>() + NTT_TW_U4 * (cnt - 1), cnt, ws);
         HALO_HIP(hipGetLastError());
     }
-    // per-pass pre-twiddle tables (one multiplication per element instead of two)
-    if (logn <= NTT_FULL_TABLE_MAX_LOG) {
-        unsigned log_ns = 0;
-        for (size_t p = 0; p < rad.size(); p++) {
-            if (p > 0) {
-                const size_t cnt = (size_t)1 << (rad[p] + log_ns);
-                HALO_CHECK(t->pass[p].reserve(cnt * 32));
-                const unsigned thr = 256, blocks = (unsigned)((cnt + thr - 1) / thr);
-                // the last pass's table is pre-scaled by the output constant (NttPassArgs::out_scaled)
-                Fe<F> oc;
-                for (int l = 0; l < NLIMB; l++) oc.v[l] = inverse ? F::NINV_ARK[logn][l] : F::ONE[l];
-                hipLaunchKernelGGL(k_pass_twiddles<F>, dim3(blocks), dim3(thr), 0, s, t->pass[p].as<uint4>(), rad[p],
-                                   log_ns, logn, t->lo.as<const uint4>(), t->hi.as<const uint4>(),
-                                   (uint32_t)t->lo_bits, oc, (int)(p + 1 == rad.size()));
-                HALO_HIP(hipGetLastError());
-            }
-            log_ns += rad[p];
-        }
-        t->has_pass = true;
+    // per-pass pre-twiddle tables; the last pass's is pre-scaled by the output constant (NttPassArgs::out_scaled)
+    for (unsigned p = 0; p < pl.npass; p++) {
+        const NttPassPlan& q = pl.pass[p];
+        if (!q.table) continue;
+        HALO_CHECK(t->pass[p].reserve(q.table_entries * 32));
+        const unsigned thr = 256, blocks = (unsigned)((q.table_entries + thr - 1) / thr);
+        Fe<F> oc;
+        for (int l = 0; l < NLIMB; l++) oc.v[l] = inverse ? F::NINV_ARK[logn][l] : F::ONE[l];
+        hipLaunchKernelGGL(k_pass_twiddles<F>, dim3(blocks), dim3(thr), 0, s, t->pass[p].as<uint4>(), q.log_r, q.log_ns,
+                           logn, t->lo.as<const uint4>(), t->hi.as<const uint4>(), (uint32_t)t->lo_bits, oc,
+                           (int)q.out_scaled);
+        HALO_HIP(hipGetLastError());
     }
+    t->has_pass = pl.tables;
     *out = t.get();
     st->tw.push_back(std::move(t));
     return HALO_OK;
 }
 
-// Device NTT over `batch` transforms: reads d_in (ark format), writes d_out (ark format).
-// The passes ping-pong between d_out and d_tmp; when d_in == d_out and the first pass would write
-// d_in, d_tmp2 (same size) takes that pass's output instead.  Buffers hold batch * N elements.
+// The instantiation of k_ntt_pass that a pass's (ne, full) names, on its grid
+template <class F>
+static int launch_ntt_pass(const NttPassPlan& q, size_t batch, hipStream_t s, const NttPassArgs& a) {
+    const dim3 grid(q.grid_x, (unsigned)batch), block(q.threads);
+    ProfScope prof("ntt_pass", s);
+    if (q.ne == NTT_E_BIG && q.full)
+        HALO_LAUNCH(prof, (k_ntt_pass<F, NTT_E_BIG, true>), grid, block, q.lds_bytes, s, a);
+    else if (q.ne == NTT_E_BIG)
+        HALO_LAUNCH(prof, (k_ntt_pass<F, NTT_E_BIG, false>), grid, block, q.lds_bytes, s, a);
+    else if (q.full)
+        HALO_LAUNCH(prof, (k_ntt_pass<F, NTT_E, true>), grid, block, q.lds_bytes, s, a);
+    else
+        HALO_LAUNCH(prof, (k_ntt_pass<F, NTT_E, false>), grid, block, q.lds_bytes, s, a);
+    HALO_HIP(hipGetLastError());
+    return HALO_OK;
+}
+
+// Device NTT over `batch` transforms: reads d_in (ark format), writes d_out (ark format), pass by pass as the
+// plan says (null: planned here).  NttBuf's roles are d_in, d_out, d_tmp and d_tmp2 (needed only where the plan
+// says so); buffers hold batch * N elements.
 template <class F>
 static int ntt_device(DeviceState* st, int field, const void* d_in, void* d_out, void* d_tmp, void* d_tmp2,
-                      unsigned logn, size_t batch, int inverse, hipStream_t s, unsigned prune,
-                      const std::vector<unsigned>* rad_in) {
-    if (logn > 30) return set_error(HALO_EINVAL, "NTT domain 2^%u too large", logn);
-    const size_t N = (size_t)1 << logn;
-    if (logn == 0) {
+                      unsigned logn, size_t batch, int inverse, hipStream_t s, const NttPlan* plan_in) {
+    HALO_CHECK(ntt_refusal(logn, batch));
+    if (!batch) return HALO_OK;
+    const NttPlan pl = plan_in ? *plan_in : ntt_plan_now(logn, inverse, d_in == d_out);
+    if (pl.logn != logn || pl.inverse != (inverse != 0) || pl.in_place != (d_in == d_out))
+        return set_error(HALO_EINVAL, "internal: NTT plan of another transform");
+    if (pl.needs_tmp2 && !d_tmp2) return set_error(HALO_EINVAL, "internal: NTT buffer aliasing");
+    if (!pl.npass) {
         if (d_in != d_out) HALO_HIP(hipMemcpyAsync(d_out, d_in, batch * 32, hipMemcpyDeviceToDevice, s));
         return HALO_OK;
     }
-    const std::vector<unsigned> rad = rad_in ? *rad_in : ntt_radices(logn);
     DeviceState::Twiddles* tw = nullptr;
-    HALO_CHECK(get_twiddles<F>(st, field, logn, inverse, rad, &tw, s));
-    const int P = (int)rad.size();
-    std::vector<const void*> srcs(P);
-    std::vector<void*> dsts(P);
-    dsts[P - 1] = d_out;
-    for (int p = P - 2; p >= 0; p--) dsts[p] = (dsts[p + 1] == d_out) ? d_tmp : d_out;
-    if (P > 1 && dsts[0] == d_in) {
-        if (!d_tmp2) return set_error(HALO_EINVAL, "internal: NTT buffer aliasing");
-        dsts[0] = d_tmp2;
-    }
-    for (int p = 0; p < P; p++) srcs[p] = (p == 0) ? d_in : dsts[p - 1];
-    unsigned log_ns = 0;
-    for (int p = 0; p < P; p++) {
-        const unsigned lr = rad[p];
+    HALO_CHECK(get_twiddles<F>(st, field, pl, &tw, s));
+    const void* const buf[4] = {d_in, d_out, d_tmp, d_tmp2};  // by NttBuf
+    for (unsigned p = 0; p < pl.npass; p++) {
+        const NttPassPlan& q = pl.pass[p];
         NttPassArgs a;
-        a.in = (const uint4*)srcs[p];
-        a.out = (uint4*)dsts[p];
-        a.tw = (tw->has_pass && p > 0) ? tw->pass[p].as<const uint4>() : nullptr;
+        a.in = (const uint4*)buf[(int)q.src];
+        a.out = (uint4*)buf[(int)q.dst];
+        // the roles never alias but for a one-workgroup pass (ntt_plan.hpp); the pointers may (d_in == d_tmp)
+        if (a.in == a.out && q.grid_x != 1) return set_error(HALO_EINVAL, "internal: NTT buffer aliasing");
+        a.tw = q.table ? tw->pass[p].as<const uint4>() : nullptr;
         a.tw_hi = tw->hi.as<const uint4>();
         a.tw_lo = tw->lo.as<const uint4>();
         a.stage_tw = tw->stage.as<const uint4>();
         a.logn = logn;
-        a.log_r = lr;
-        a.log_ns = log_ns;
-        a.lo_bits = (uint32_t)tw->lo_bits;
-        a.in_ark = (p == 0);
-        a.out_ark = (p == P - 1);
-        a.prune = (p == 0 && !inverse) ? ntt_pass0_prune(lr, prune) : 0u;
+        a.log_r = q.log_r;
+        a.log_ns = q.log_ns;
+        a.lo_bits = pl.lo_bits;
+        a.in_ark = q.in_ark;
+        a.out_ark = q.out_ark;
+        a.prune = q.prune;
         for (int l = 0; l < NLIMB; l++) a.out_const[l] = inverse ? F::NINV_ARK[logn][l] : F::ONE[l];
-        a.out_scaled = (a.out_ark && a.tw) ? 1u : 0u;  // (get_twiddles pre-scales the last pass's table)
-        a.stride = N;
-        const size_t NJ = N >> lr;
-        const size_t NE = lr > NTT_MAX_LOG_R_MULTI ? NTT_E_BIG : NTT_E;
-        const size_t T = std::min(NJ, NE >> lr);
-        const size_t lds = NE * NLIMB * 4;
-        dim3 grid((unsigned)(NJ / T), (unsigned)batch);
-        ProfScope prof("ntt_pass", s);
-        const bool full = (T << lr) == NE;
-        if (NE == NTT_E_BIG && full)
-            HALO_LAUNCH(prof, (k_ntt_pass<F, NTT_E_BIG, true>), grid, dim3(NTT_E_BIG / NTT_EPT), lds, s, a);
-        else if (NE == NTT_E_BIG)
-            HALO_LAUNCH(prof, (k_ntt_pass<F, NTT_E_BIG, false>), grid, dim3(NTT_E_BIG / NTT_EPT), lds, s, a);
-        else if (full)
-            HALO_LAUNCH(prof, (k_ntt_pass<F, NTT_E, true>), grid, dim3(NTT_E / NTT_EPT), lds, s, a);
-        else
-            HALO_LAUNCH(prof, (k_ntt_pass<F, NTT_E, false>), grid, dim3(NTT_E / NTT_EPT), lds, s, a);
-        HALO_HIP(hipGetLastError());
-        log_ns += lr;
+        a.out_scaled = q.out_scaled;
+        a.stride = (size_t)1 << logn;
+        HALO_CHECK(launch_ntt_pass<F>(q, batch, s, a));
     }
     return HALO_OK;
 }
 
 int ntt_device_dispatch(DeviceState* st, int field, const void* d_in, void* d_out, void* d_tmp, unsigned logn,
-                        size_t batch, int inverse, hipStream_t s, void* d_tmp2, unsigned prune,
-                        const std::vector<unsigned>* rad) {
+                        size_t batch, int inverse, hipStream_t s, void* d_tmp2, const NttPlan* plan) {
     int rc;
     DISPATCH_FIELD(field, F, {
-        rc = ntt_device<F>(st, field, d_in, d_out, d_tmp, d_tmp2, logn, batch, inverse, s, prune, rad);
+        rc = ntt_device<F>(st, field, d_in, d_out, d_tmp, d_tmp2, logn, batch, inverse, s, plan);
     });
     return rc;
 }
@@ -890,22 +833,34 @@ extern "C" int halo_interpolate(halo_field_t field, const halo_fe_t* evals, unsi
     return HALO_OK;
 }
 
+// The in-place transform of the two _dev entry points (arguments checked, batch > 0): the passes ping-pong through
+// scratch[4], and scratch[5] takes the first pass where the plan needs it, so no pass reads and writes one buffer.
+// The elements from nonzero_len on are taken as zero: what pass 0 reads of them, [nonzero_len, pl.read_end), is
+// cleared first (up to 2^ceil(lg nonzero_len) when it prunes, the whole tail otherwise).
+static int ntt_dev_in_place(halo_field_t field, void* d_data, size_t batch, const NttPlan& pl, size_t nonzero_len,
+                            void* stream) {
+    DeviceState* st = current_state();
+    if (!st) return HALO_EDEVICE;
+    std::lock_guard<std::mutex> g(st->mu);
+    const size_t N = (size_t)1 << pl.logn;
+    hipStream_t s = (hipStream_t)stream;
+    ScratchUse su(st, s);
+    HALO_CHECK(st->scratch[4].reserve(batch * N * 32));
+    HALO_CHECK(st->scratch[5].reserve(batch * N * 32));
+    if (pl.read_end > nonzero_len)
+        for (size_t b = 0; b < batch; b++)
+            HALO_HIP(hipMemsetAsync((char*)d_data + (b * N + nonzero_len) * 32, 0, (pl.read_end - nonzero_len) * 32, s));
+    return ntt_device_dispatch(st, field, d_data, d_data, st->scratch[4].ptr, pl.logn, batch, pl.inverse, s,
+                               st->scratch[5].ptr, &pl);
+}
+
 extern "C" int halo_ntt_dev(halo_field_t field, void* d_data, unsigned log_n, size_t batch, int inverse, void* stream) {
     clear_error();
     HALO_CHECK(check_field(field));
     if (!d_data) return set_error(HALO_EINVAL, "halo_ntt_dev: null buffer");
-    DeviceState* st = current_state();
-    if (!st) return HALO_EDEVICE;
-    std::lock_guard<std::mutex> g(st->mu);
-    const size_t N = (size_t)1 << log_n;
-    hipStream_t s = (hipStream_t)stream;
-    ScratchUse su(st, s);
-    // in place: the passes ping-pong through scratch (a second scratch buffer takes the first pass
-    // when the pass count is odd, so no pass reads and writes one buffer)
-    HALO_CHECK(st->scratch[4].reserve(batch * N * 32));
-    HALO_CHECK(st->scratch[5].reserve(batch * N * 32));
-    return ntt_device_dispatch(st, field, d_data, d_data, st->scratch[4].ptr, log_n, batch, inverse, s,
-                               st->scratch[5].ptr);
+    HALO_CHECK(ntt_refusal(log_n, batch));
+    if (!batch) return HALO_OK;
+    return ntt_dev_in_place(field, d_data, batch, ntt_plan_now(log_n, inverse, true), (size_t)1 << log_n, stream);
 }
 
 // Forward device NTT of data whose elements at index >= nonzero_len are zero (the prover's
@@ -916,27 +871,12 @@ extern "C" int halo_ntt_dev_zero_tail(halo_field_t field, void* d_data, unsigned
     clear_error();
     HALO_CHECK(check_field(field));
     if (!d_data) return set_error(HALO_EINVAL, "halo_ntt_dev_zero_tail: null buffer");
-    const size_t N = (size_t)1 << log_n;
-    if (nonzero_len > N) return set_error(HALO_EINVAL, "halo_ntt_dev_zero_tail: nonzero_len > N");
+    HALO_CHECK(ntt_refusal(log_n, batch));
+    if (nonzero_len > (size_t)1 << log_n) return set_error(HALO_EINVAL, "halo_ntt_dev_zero_tail: nonzero_len > N");
+    if (!batch) return HALO_OK;
     unsigned lg_nz = 0;
     while (((size_t)1 << lg_nz) < std::max<size_t>(nonzero_len, 1)) lg_nz++;
-    DeviceState* st = current_state();
-    if (!st) return HALO_EDEVICE;
-    std::lock_guard<std::mutex> g(st->mu);
-    hipStream_t s = (hipStream_t)stream;
-    ScratchUse su(st, s);
-    HALO_CHECK(st->scratch[4].reserve(batch * N * 32));
-    HALO_CHECK(st->scratch[5].reserve(batch * N * 32));
-    // the tail's contents are ignored: zero exactly what pass 0 will read beyond nonzero_len (up to
-    // 2^ceil(lg nonzero_len) when it prunes, the whole tail otherwise)
-    const std::vector<unsigned> rad = ntt_radices(log_n);  // one read: the zeroed span and the passes agree
-    const unsigned pr = log_n ? ntt_pass0_prune(rad[0], log_n - lg_nz) : 0u;
-    const size_t read_end = pr ? (N >> pr) : N;
-    if (read_end > nonzero_len)
-        for (size_t b = 0; b < batch; b++)
-            HALO_HIP(hipMemsetAsync((char*)d_data + (b * N + nonzero_len) * 32, 0, (read_end - nonzero_len) * 32, s));
-    return ntt_device_dispatch(st, field, d_data, d_data, st->scratch[4].ptr, log_n, batch, 0, s, st->scratch[5].ptr,
-                               log_n - lg_nz, &rad);
+    return ntt_dev_in_place(field, d_data, batch, ntt_plan_now(log_n, 0, true, log_n - lg_nz), nonzero_len, stream);
 }
 
 extern "C" int halo_ntt_twiddle_dev(halo_field_t field, void* d_data, unsigned log_n, size_t rows, size_t cols,
@@ -952,9 +892,10 @@ extern "C" int halo_ntt_twiddle_dev(halo_field_t field, void* d_data, unsigned l
     hipStream_t s = (hipStream_t)stream;
     const size_t cnt = rows * cols;
     const unsigned thr = 256, blocks = (unsigned)((cnt + thr - 1) / thr);
+    const NttPlan pl = ntt_plan_now(log_n, inverse, false);  // for its two-level tables; shared with the transforms'
     DISPATCH_FIELD(field, F, {
         DeviceState::Twiddles* tw = nullptr;
-        HALO_CHECK(get_twiddles<F>(st, field, log_n, inverse ? 1 : 0, ntt_radices(log_n), &tw, s));
+        HALO_CHECK(get_twiddles<F>(st, field, pl, &tw, s));
         hipLaunchKernelGGL(k_twiddle_mat<F>, dim3(blocks), dim3(thr), 0, s, (uint4*)d_data, rows, cols, row0, col0,
                            log_n, tw->lo.as<const uint4>(), tw->hi.as<const uint4>(), (uint32_t)tw->lo_bits);
     });

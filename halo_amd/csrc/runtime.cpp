@@ -185,8 +185,8 @@ static const char* const kTuneNames[TUNE_COUNT] = {"ipa_weighted", "ipa_tail",  
                                                    "decide_group_scalars", "decide_bisect",  "decide_rho_fs",
                                                    "schnorr_bisect", "schnorr_bisect_leaf", "schnorr_bisect_pass_items"};
 // ntt_big_max_log: the largest transform split into two passes on 2048-element blocks (2^17..2^this);
-// larger ones, and any below 2^17, take passes of <= 8 bits on 1024-element blocks (ntt.hip ntt_radices)
-// ntt_even_split: passes of <= 8 bits split into even radices where possible (ntt_radices)
+// larger ones, and any below 2^17, take passes of <= 8 bits on 1024-element blocks (ntt_plan.hpp ntt_split)
+// ntt_even_split: passes of <= 8 bits split into even radices where possible (ntt_split)
 // poseidon_lanes: lanes per sponge of the batched Poseidon kernels (1 or 3; 0 = by batch size, sponge_plan.hpp)
 // ipa_pair_max: weighted IPA rounds up to this many terms per side run L and R as one MSM (2^19: every
 // weighted round of a 2^20 opening; the pair's 17-bit keys sort in a 9-bit and an 8-bit pass)

@@ -112,7 +112,7 @@ struct DeviceState {
         DevBuf stage;    // stage twiddles: entry 2^s - 1 + k = omega_{2^(s+1)}^k, s < 11 (9 limbs, 48 B each)
         DevBuf pass[4];  // per-pass pre-twiddle tables (logn <= 24), see ntt.hip
         bool has_pass = false;
-        uint64_t split = 0;  // the pass split the tables were built for (ntt_radices, tuning-dependent)
+        uint64_t split = 0;  // the pass split the tables were built for (NttPlan::split_key, tuning-dependent)
     };
     std::vector<std::unique_ptr<Twiddles>> tw;
     struct RTable {

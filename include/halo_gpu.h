@@ -242,7 +242,10 @@ int halo_interpolate(halo_field_t field, const halo_fe_t* evals, unsigned log_n,
  * out has room for la + lb - 1 entries; *out_len = trimmed length. */
 int halo_poly_mul(halo_field_t field, const halo_fe_t* a, size_t la, const halo_fe_t* b, size_t lb,
                   halo_fe_t* out, size_t* out_len);
-/* Batched device NTT: `batch` contiguous transforms of size 2^log_n at d_data, in place. */
+/* Batched device NTT: `batch` contiguous transforms of size 2^log_n at d_data, in place.  log_n <= 30 and
+ * batch <= 65535 (HALO_EINVAL otherwise, before the device is looked up); batch = 0 is a success that launches
+ * nothing, as the empty shapes of halo_transpose_dev and halo_ntt_twiddle_dev are.  The same limits hold for
+ * halo_ntt_dev_zero_tail, whose nonzero_len <= 2^log_n is checked once log_n has passed. */
 int halo_ntt_dev(halo_field_t field, void* d_data, unsigned log_n, size_t batch, int inverse,
                  void* stream);
 /* Forward halo_ntt_dev for inputs that are zero from index nonzero_len on (a polynomial of degree

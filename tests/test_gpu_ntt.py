@@ -339,6 +339,98 @@ def test_ntt_zero_tail_matches_full(hal, corc, logn, nz):
     assert np.array_equal(y.cpu().numpy().view(np.uint64), corc.ntt("fp", x0))
 
 
+# ---- the pass splits behind the tuning keys (ntt_plan.hpp), at the smallest sizes that reach each branch ---------
+TUNED = [(22, 0), (22, 1), (16, 0), (16, 1)]
+_rows_cache = {}
+
+
+def tuned_rows(corc, logn):
+    """Three rows of 2^logn elements and their oracle transforms, per field and direction; computed once."""
+    if logn not in _rows_cache:
+        n = 1 << logn
+        x = rand_fe(3 * n, 7000 + logn)
+        exp = {(tag, inv): np.concatenate([corc.ntt(tag, x[b * n:(b + 1) * n], inverse=bool(inv)) for b in range(3)])
+               for tag in ("fp", "fq") for inv in (0, 1)}
+        x.setflags(write=False)
+        _rows_cache[logn] = (x, exp)
+    return _rows_cache[logn]
+
+
+def ntt_dev_rows(hal, fid, x, logn, batch, inverse):
+    import torch
+    d = torch.from_numpy(x.view(np.int64).copy()).cuda()
+    s = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    hal.check(hal.load().halo_ntt_dev(fid, ctypes.c_void_p(d.data_ptr()), logn, batch, inverse, s))
+    torch.cuda.synchronize()
+    return d.cpu().numpy().view(np.uint64)
+
+
+@pytest.mark.parametrize("logn", [9, 13, 17])
+@pytest.mark.parametrize("big,even", TUNED)
+def test_ntt_tuned_splits_vs_c_oracle(hal, corc, big, even, logn):
+    """halo_ntt_dev in place on a batch of 3 under every branch of the pass split: (22, 0) the default, (22, 1) the
+    even split of the <= 8-bit passes ([6, 3] and [8, 5] for 2^9 and 2^13), (16, .) passes of <= 8 bits where the
+    default takes two wide ones, which at 2^17 is [6, 6, 5]: three passes in place, the first through the second
+    scratch buffer.  Forward and inverse, each in both fields, every row bit for bit against the C oracle."""
+    x, exp = tuned_rows(corc, logn)
+    with hal.tuning(ntt_big_max_log=big, ntt_even_split=even):
+        for tag, fid in (("fp", 0), ("fq", 1)):
+            for inv in (0, 1):
+                assert np.array_equal(ntt_dev_rows(hal, fid, x, logn, 3, inv), exp[tag, inv]), (tag, inv)
+    assert hal.get_tuning("ntt_big_max_log") == 22 and hal.get_tuning("ntt_even_split") == 0
+
+
+def test_ntt_twiddle_cache_keyed_by_split(hal, corc):
+    """One process, 2^17: the default split [9, 8], then [6, 6, 5] under (16, 1), then the default again.  The
+    twiddle cache holds both sets of per-pass tables under their split keys and must hand each transform its own."""
+    x, exp = tuned_rows(corc, 17)
+    for knobs in ({}, dict(ntt_big_max_log=16, ntt_even_split=1), {}):
+        with hal.tuning(**knobs):
+            for inv in (0, 1):
+                assert np.array_equal(ntt_dev_rows(hal, 0, x, 17, 3, inv), exp["fp", inv]), (knobs, inv)
+
+
+@pytest.mark.parametrize("nz", [1 << 15, (1 << 15) + 1, 5])
+@pytest.mark.parametrize("big,even", [(22, 0), (16, 0)])
+def test_ntt_zero_tail_tuned_splits(hal, corc, big, even, nz):
+    """halo_ntt_dev_zero_tail at 2^17 under [9, 8] and [6, 6, 5]: a prefix of 2^15 asks pass 0 to skip two stages,
+    which radix 9 cuts to one (the stages left on a wide block must pair up) and radix 6 grants; 2^15 + 1 asks for
+    one (refused by radix 6: its first group has two stages); 5 asks for more than either pass has.  The tail holds
+    garbage; the result equals halo_ntt_dev of the zero-padded input and the oracle's."""
+    import torch
+
+    logn, N = 17, 1 << 17
+    L = hal.load()
+    x = np.zeros((N, 4), dtype=np.uint64)
+    x[:nz] = rand_fe(nz, 7100 + nz)
+    junk = rand_fe(N, 7200 + nz)
+    junk[:nz] = x[:nz]
+    with hal.tuning(ntt_big_max_log=big, ntt_even_split=even):
+        full = ntt_dev_rows(hal, 0, x, logn, 1, 0)
+        d = torch.from_numpy(junk.view(np.int64)).cuda()
+        s = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        hal.check(L.halo_ntt_dev_zero_tail(0, ctypes.c_void_p(d.data_ptr()), logn, 1, nz, s))
+        torch.cuda.synchronize()
+    got = d.cpu().numpy().view(np.uint64)
+    assert np.array_equal(got, full)
+    assert np.array_equal(got, corc.ntt("fp", x))
+
+
+def test_ntt_dev_empty_batch(hal):
+    """batch = 0: HALO_OK, nothing launched, the buffer as it was."""
+    import torch
+
+    L = hal.load()
+    x = rand_fe(8, 7300)
+    d = torch.from_numpy(x.view(np.int64).copy()).cuda()
+    p = ctypes.c_void_p(d.data_ptr())
+    hal.check(L.halo_ntt_dev(0, p, 3, 0, 0, None))
+    hal.check(L.halo_ntt_dev(1, p, 3, 0, 1, None))
+    hal.check(L.halo_ntt_dev_zero_tail(0, p, 3, 0, 4, None))
+    torch.cuda.synchronize()
+    assert np.array_equal(d.cpu().numpy().view(np.uint64), x)
+
+
 def test_ntt_dev_concurrent_streams(hal, corc):
     """halo_ntt_dev on two torch streams at once plus host-array NTTs (null stream) in between: the
     device-global NTT scratch is fenced per stream (ScratchUse), so every transform is bit-exact."""

@@ -1,6 +1,6 @@
 """Times the device NTT (halo_ntt_dev, forward + inverse pair) at several sizes; checks the round trip."""
-import ctypes, sys, time
-sys.path.insert(0, '/root/repo')
+import ctypes, os, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from halo_amd import _lib as H
 H.ensure_device(0)
